@@ -3,6 +3,13 @@
 (BASELINE.json configs[1]), inputs resident in HBM, reference-mode (fit once, excluded from timing).
 
     python bench.py --gpus N --steps K --warmup W [--workload transform|fit_transform_pooled|hm_config3|module_config5|real_tiles|reinhard_f32]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: its contract fields and the figures of the timed steps
+themselves.  ``--full`` adds everything that takes runs or processes of its own: the one-buffer loop (``roofline.device_ms_hot``),
+the real-tile record of the headline line, the collective probe of ``fit_transform_pooled``, the CPU baseline and the parity
+against the oracle (``--no-cpu`` leaves out the last two).  ``--dump-outputs DIR`` writes what the timed path returned in its last
+step as ``DIR/<name>.npy`` (see ``dump_outputs``); the inputs are seeded, the same on every run with the same arguments.
 
 For N > 1 the job is one rank per GPU over RCCL: either the driver launches this file under ``torch.distributed.run`` (WORLD_SIZE /
 RANK / LOCAL_RANK in the environment), or -- ``python bench.py --gpus N`` as it stands -- this process starts the N ranks ITSELF
@@ -22,7 +29,7 @@ One JSON line on stdout (rank 0).  Besides the contract fields it carries
                   copy ceiling).  A transform is several launches (see `kernel`); the figure prices ALL of them.
                   `traffic`: HBM bytes per call from the committed rocprofv3 PMC passes of this command, cited
                   only while the kernel sources still hash to what those passes ran (else null).
-  cpu_baseline -- the CPU oracle (a numpy port of the reference's backend="torch" path) timed on this
+  cpu_baseline -- (--full) the CPU oracle (a numpy port of the reference's backend="torch" path) timed on this
                   box's host cores over a bounded sample of the same workload (rank 0, N=1 only).
 
 ``--workload hm_config3`` (BASELINE configs[2]: HistogramMatching.transform, 64x3x1024x1024 uint8, 6 B/px), ``module_config5``
@@ -68,8 +75,15 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--workload", choices=("transform", "fit_transform_pooled", "hm_config3", "module_config5", "real_tiles", "reinhard_f32"), default="transform")
     ap.add_argument("--batches", type=int, default=2, help="different input batches the timed loop rotates over (1: one buffer)")
     ap.add_argument("--cpu-tiles", type=int, default=64, help="tiles of the workload the CPU baseline is timed on")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and the parity against the oracle) of --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: one-buffer loop, real-tile record, collective probe, CPU baseline, parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, a seeded sample past 48 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def source_hash() -> str:
@@ -189,9 +203,35 @@ def timed_loop(fn, steps: int, barrier):
     return elapsed, [ev[i].elapsed_time(ev[i + 1]) for i in range(steps)], out
 
 
+DUMP_BUDGET = 48 << 20         # bytes over all arrays of one --dump-outputs
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: the tensors the timed path returned in its last step, one ``<name>.npy`` each, float64 kept, every other type
+    as float32 (exact for uint8, bfloat16 and float16).  Smaller arrays are written whole first; an array larger than its share of
+    DUMP_BUDGET keeps a sample along its first axis (whole tiles, ascending), drawn by ``numpy.random.default_rng(0)``: the same
+    entries on every run, so two builds compare output for output."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left, items = DUMP_BUDGET, sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for k, (name, t) in enumerate(items):
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        share, item = left // (len(items) - k), (8 if dtype == torch.float64 else 4)
+        if t.dim() > 0 and t.numel() * item > share:
+            keep = max(1, share // (t[0].numel() * item))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            print(f"bench.py --dump-outputs: {name}: {keep} of {arrays[name].shape[0]} entries along axis 0, rows {rows.tolist()}", file=sys.stderr)
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def other_workload(args, dev, rank, world, barrier, max_over_ranks, real_stdout) -> None:
     """hm_config3 / module_config5 / real_tiles: the same protocol (warm-up, K timed steps over rotating batches, barrier +
-    synchronize on both sides, max over ranks), roofline on the workload's own algorithmic bytes, CPU oracle on a bounded sample."""
+    synchronize on both sides, max over ranks), roofline on the workload's own algorithmic bytes; with --full the CPU oracle on a bounded sample."""
     import numpy as np
 
     from oracle import stain_oracle as so
@@ -256,6 +296,8 @@ def other_workload(args, dev, rank, world, barrier, max_over_ranks, real_stdout)
     for i in range(args.warmup):
         out = call(batches[i % n_batches])
     elapsed, step_ms, out = timed_loop(lambda i: call(batches[i % n_batches]), args.steps, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": out})
     elapsed = max_over_ranks(elapsed)
     if rank != 0:
         return
@@ -271,7 +313,7 @@ def other_workload(args, dev, rank, world, barrier, max_over_ranks, real_stdout)
     if args.workload == "real_tiles":
         engine = norm._get_backend_impl()
         line["form"] = "four-pass (the two-pass form left its speculative path on some tiles; the backend's feedback switched)" if int(engine._classic_left) > 0 else "two-pass"
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         want = cpu_fn(cpu_sample)
         k = cpu_sample.shape[0]
         line["cpu_baseline"] = cpu_baseline_any(cpu_kind, cpu_many, cpu_params, h, w, f"the workload's first {cpu_many.shape[0]} tiles ({h}x{w} {dt_name})")
@@ -420,18 +462,21 @@ def main() -> None:
         be = MacenkoHIP(dev)
 
         def step(i):
-            return sxd.macenko_fit_transform_pooled(batches[i % n_batches], steps=be)[0]
+            return sxd.macenko_fit_transform_pooled(batches[i % n_batches], steps=be)      # (out, he, max_c)
 
         for i in range(args.warmup):
             step(i)
         elapsed, step_ms, out = timed_loop(step, args.steps, barrier)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"output": out[0], "stain_matrix": out[1], "max_conc": out[2]})
         elapsed = max_over_ranks(elapsed)
-        probe = min(args.steps, 50)
-        with sxd.collective_timer() as timer:
-            for i in range(probe):
-                step(i)
-        collective_ms = timer.ms() / probe
-        n_collectives = timer.count() // probe
+        if args.full:
+            probe = min(args.steps, 50)
+            with sxd.collective_timer() as timer:
+                for i in range(probe):
+                    step(i)
+            collective_ms = timer.ms() / probe
+            n_collectives = timer.count() // probe
         if rank == 0:
             dev_ms = sum(step_ms) / len(step_ms)
             line = {
@@ -441,12 +486,14 @@ def main() -> None:
                 "config": {"workload": f"Macenko batch-mode fit_transform, {world * TILES}x3x512x512 fp32 sharded over {world} GPU(s) with RCCL statistics exchanges (BASELINE configs[3] is this at 8 GPUs)",
                            "tiles_per_gpu": TILES, "height": HEIGHT, "width": WIDTH, "input_batches_rotated": n_batches,
                            "parallelism": f"tiles sharded over {world} GPU(s); pooled fit: 1 all-gather of (tile count, 10 fp64 moments, 48 KB sample) per rank, then per percentile stage 1 all-reduce of ~8 KB int64 counts + 1 all-gather of (2 counts, <= 32 KB candidate keys); transform local"},
-                "collective_ms": round(collective_ms, 4), "collectives_per_step": n_collectives, "backend": dist.get_backend(),
+                "backend": dist.get_backend(),
                 "roofline": {"bound": "hbm", "achieved": round(pixels * BYTES_PER_PIXEL / (dev_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": round(pixels * BYTES_PER_PIXEL / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
                              "algorithmic_bytes_per_launch": pixels * BYTES_PER_PIXEL, "device_ms_per_call": round(dev_ms, 4),
                              "kernel": "pooled fit (stats, bracket passes, pool kernels, per-group stages; host choreography with five small collectives) + transform of the local tiles"},
             }
+            if args.full:
+                line.update(collective_ms=round(collective_ms, 4), collectives_per_step=n_collectives)
             sys.stdout.flush()
             os.dup2(real_stdout, 1)
             print(json.dumps(line), flush=True)
@@ -462,12 +509,15 @@ def main() -> None:
         out = norm.transform(batches[i % n_batches])
     elapsed, step_ms, out = timed_loop(lambda i: norm.transform(batches[i % n_batches]), args.steps, barrier)
     last_batch = (args.steps - 1) % n_batches
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": out})
     elapsed = max_over_ranks(elapsed)
-    # the one-buffer figure (input resident in the Infinity Cache between calls), a shorter loop
-    hot_steps = min(args.steps, 300)
-    for _ in range(20):
-        norm.transform(batches[0])
-    _, hot_ms, _ = timed_loop(lambda i: norm.transform(batches[0]), hot_steps, barrier)
+    if args.full:
+        # the one-buffer figure (input resident in the Infinity Cache between calls), a shorter loop
+        hot_steps = min(args.steps, 300)
+        for _ in range(20):
+            norm.transform(batches[0])
+        _, hot_ms, _ = timed_loop(lambda i: norm.transform(batches[0]), hot_steps, barrier)
     dev_ms = sum(step_ms) / len(step_ms)
     dev_std = (sum((v - dev_ms) ** 2 for v in step_ms) / max(len(step_ms) - 1, 1)) ** 0.5
 
@@ -494,18 +544,19 @@ def main() -> None:
                                    else "all 7 launches of one sx_macenko_transform call in its four-pass form (stats, plane, bracket<phi>, stain, bracket<conc>, scale, reconstruct)",
                          "device_ms_per_call": round(dev_ms, 4), "device_ms_std": round(dev_std, 4), "device_ms_min": round(min(step_ms), 4),
                          "device_ms_median": round(sorted(step_ms)[len(step_ms) // 2], 4),
-                         "device_ms_hot": round(sum(hot_ms) / len(hot_ms), 4),
-                         "device_ms_hot_note": "the same call over ONE input buffer (201 MB: it stays in the 256 MiB Infinity Cache between calls), what the reference's harness would time",
                          "dominant_kernel": {"name": "pass_a_kernel", "algorithmic_bytes": pixels * 12,
                                              "note": "the call's one pass over the fp32 input (12 B/px read; it also leaves the tiles as 8-bit codes, 3 B/px, which the "
                                                      f"reconstruct pass reads instead of the floats before it writes 12 B/px); rocprofv3 averages of all four launches in {KERNEL_STATS}"}},
             "kernel_source_hash": source_hash(),
         }
-        if not os.environ.get("STAINX_BENCH_NO_REAL"):
+        if args.full:
+            line["roofline"]["device_ms_hot"] = round(sum(hot_ms) / len(hot_ms), 4)
+            line["roofline"]["device_ms_hot_note"] = "the same call over ONE input buffer (201 MB: it stays in the 256 MiB Infinity Cache between calls), what the reference's harness would time"
+        if args.full and not os.environ.get("STAINX_BENCH_NO_REAL"):
             line["real_tiles"] = real_tiles_record(dev, min(args.steps, 200), lambda: torch.cuda.synchronize(dev))
         if os.environ.get("STAINX_BENCH_REHEARSE"):
             line["rehearsal"] = "ranks share ONE GPU (gloo for the barrier and the max): a run of the N > 1 code path, not a measurement"
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             he = norm._stain_matrix.cpu().numpy()
             max_c = norm._target_max_conc.cpu().numpy()
             line["cpu_baseline"] = cpu_baseline(args.cpu_tiles, x_cpu, he, max_c)

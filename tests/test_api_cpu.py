@@ -252,3 +252,44 @@ def test_bench_gpus_n_starts_n_ranks_or_refuses():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=env, timeout=300)
     if torch.cuda.device_count() < 2:
         assert r.returncode != 0 and "refusing to time fewer GPUs" in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+def test_bench_plain_run_has_full_and_dump_flags(monkeypatch):
+    """A plain `bench.py` run leaves the extras to --full (off by default); --dump-outputs names the directory; --steps is the count."""
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and args.full is False and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.steps == 3 and args.full is True and args.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs: float32 (float64 kept), small arrays whole, a large one cut to the same whole tiles on every run, 64 MB at most."""
+    import numpy as np
+
+    import bench
+
+    big = torch.arange(64 * 3 * 512 * 512, dtype=torch.float32).reshape(64, 3, 512, 512)      # 201 MB: the headline's output
+    he = torch.tensor([[0.6, 0.2], [0.7, 0.8], [0.4, 0.6]], dtype=torch.float64)
+    codes = torch.arange(2 * 3 * 4 * 4).reshape(2, 3, 4, 4).to(torch.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"output": big, "stain_matrix": he, "codes": codes})
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert sorted(a) == ["codes", "output", "stain_matrix"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["stain_matrix"].dtype == np.float64 and np.array_equal(a["stain_matrix"], he.numpy())
+    assert a["codes"].dtype == np.float32 and np.array_equal(a["codes"], codes.numpy().astype(np.float32))
+    out = a["output"]
+    assert out.dtype == np.float32 and out.shape[1:] == (3, 512, 512) and 1 <= out.shape[0] < 64
+    rows = out[:, 0, 0, 0].astype(np.int64) // (3 * 512 * 512)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(out, big.numpy()[rows])                  # whole tiles, ascending
+    for name, v in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), v), name                  # the same sample every run

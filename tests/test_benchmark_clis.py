@@ -85,3 +85,35 @@ def test_single_method_cli(capsys):
         rc, out, err = _run(single, [method, "--batch-size", "4", "--height", "96", "--width", "64", "--runs", "2", "--data", "he" if method == "macenko" else "noise"], capsys)
         assert rc == 0, err
         assert "Result shape: (4, 3, 96, 64)" in out and "Images per second" in out and f"Method: {method}" in out
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the contract fields, none of --full's extras, and DIR/output.npy is
+    the last timed step's output (a seeded sample of whole tiles) -- checked against the oracle on two of its tiles."""
+    import subprocess
+
+    import numpy as np
+
+    from oracle import stain_oracle as so
+    from stainx_amd import synth
+
+    steps = 3
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32"
+    assert not {"cpu_baseline", "real_tiles", "max_abs_vs_oracle_0_255"} & set(line) and "device_ms_hot" not in line["roofline"]
+    out = np.load(tmp_path / "output.npy")
+    assert out.dtype == np.float32 and out.shape[1:] == (3, 512, 512) and out.nbytes <= 64 << 20
+    rows = np.sort(np.random.default_rng(0).choice(64, size=out.shape[0], replace=False))      # dump_outputs' sample
+    he, max_c = so.macenko_fit(synth.reference_tile(512, 512).numpy())
+    last = (steps - 1) % 2                                                                      # the batch the last step read
+    for k in (0, out.shape[0] - 1):
+        i = int(rows[k])
+        tile = synth.as_dtype(synth.he_tile(512, 512, 1000 + 64 * last + i, 1.0 + 0.005 * i), torch.float32)
+        want = so.macenko_transform(tile.numpy(), he, max_c)
+        assert np.abs(out[k:k + 1] - want).max() < 2.55e-2, i                                   # 0-255 scale, the smoke() tolerance

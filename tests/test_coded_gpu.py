@@ -114,8 +114,8 @@ def test_repeated_calls_on_one_workspace_alternate_kinds(be, dev):
         assert torch.equal(be.transform(a, sm, tmc, _extra_flags=TWO_PASS), want_a)
 
 
-def test_real_tissue_coded_equals_two_pass_and_plain(be, dev):
-    d = np.load("tests/golden/g11_real_images.npz")
+def test_real_tissue_coded_equals_two_pass_and_plain(be, dev, golden):
+    d = golden("g11_real_images.npz")
     imgs = torch.from_numpy(d["images_u8"])      # (6, 3, 1024, 1024)
     tiles = [imgs[i, :, y0:y0 + 256, x0:x0 + 256] for i in range(imgs.shape[0]) for (y0, x0) in ((0, 0), (768, 768), (300, 200))]
     x = (torch.stack(tiles).to(torch.float32) / 255.0).to(dev)

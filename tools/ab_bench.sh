@@ -7,7 +7,7 @@ LIBS=${LIBS:-"libstainx_prev.so libstainx_hip.so"}
 for rep in 1 2; do
   for lib in $LIBS; do
     echo -n "$lib  "
-    STAINX_HIP_LIB=$R/stainx_amd/_lib/$lib timeout -k 10 200 python3 $R/bench.py --no-cpu --steps 500 --warmup 50 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], 'median', r['device_ms_median'], 'min', r['device_ms_min'], 'hot', r['device_ms_hot'])" || exit 1
+    STAINX_HIP_LIB=$R/stainx_amd/_lib/$lib timeout -k 10 200 python3 $R/bench.py --full --no-cpu --steps 500 --warmup 50 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], 'median', r['device_ms_median'], 'min', r['device_ms_min'], 'hot', r['device_ms_hot'])" || exit 1
   done
 done
 for lib in $LIBS; do
