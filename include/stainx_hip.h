@@ -113,7 +113,30 @@ int sx_macenko_fit(const void* images_dev, int dtype, int64_t n_tiles, int64_t h
                    float* he_out_dev, float* max_c_out_dev, void* workspace_dev, size_t workspace_bytes,
                    void* stream);
 
-/* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_fit that used `workspace_dev`
+/* Stain augmentation (Tellez et al.; torchstain's MacenkoAugmentor, HistomicsTK's rgb_perturb_stain_concentration): every tile is
+ * split into its H and E concentrations C = pinv(HE_source) OD in its own stain basis (the transform's per-tile estimate, exact
+ * percentiles), the concentrations are scaled and shifted by the tile's own factors, and the tile is rebuilt.  An extension: the
+ * reference has no counterpart.
+ *   alpha_dev, beta_dev   n_tiles x 2 floats each, (H, E) per tile, DEVICE memory read by the last kernel of the call (a captured
+ *                         graph replayed after new values are written into the same buffers uses the new values)
+ *   own basis             stain_matrix_dev == target_max_conc_dev == NULL:
+ *                           C' = alpha * C + beta,                       OD' = HE_source C'
+ *   normalise and jitter  both given (a fitted reference, as for sx_macenko_transform):
+ *                           C' = alpha * (C * target_max_conc / maxC) + beta,   OD' = stain_matrix C'
+ *                         then, as the transform (the reference's Io = 240): out = clamp(240 exp(-OD'), 0, 255), cast to the output
+ *                         type.  Exactly one of the two pointers NULL is SX_ERR_BAD_ARG.
+ * Images, output and its element type follow sx_macenko_transform's rules; flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_CHANNELS_LAST,
+ * SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 (uint8 input), and SX_MACENKO_CLASSIC (a no-op: augmentation always takes the four-pass
+ * form); any other bit, SX_MACENKO_SAMPLED included, is SX_ERR_BAD_ARG.  alpha = 1, beta = 0 in normalise mode gives the bits of
+ * sx_macenko_transform(..., SX_MACENKO_CLASSIC).  The workspace needs sx_macenko_workspace_bytes_for(dtype, n_tiles, height, width,
+ * SX_MACENKO_CLASSIC) bytes.  Own-basis mode skips the concentration percentiles (three passes over the input instead of four):
+ * sx_macenko_tile_params after it reports the plane, the angles and HE_source, but no maxC (those two floats are stale). */
+int sx_macenko_augment(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                       const float* alpha_dev, const float* beta_dev,
+                       const float* stain_matrix_dev, const float* target_max_conc_dev,
+                       unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi
  *   [10..15] HE_source (3,2)  [16..17] maxC  [18] select paths taken (bit i: slot i fell back to the

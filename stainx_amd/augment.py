@@ -1,0 +1,108 @@
+"""``MacenkoAugment``: Macenko-space stain augmentation as an ``nn.Module`` (an extension: the reference has none).
+
+The H&E jitter of Tellez et al., as torchstain's ``MacenkoAugmentor``, tiatoolbox's ``StainAugmentor`` and HistomicsTK's
+``rgb_perturb_stain_concentration`` offer it: every tile is split into H and E concentrations in its own stain basis, they become
+``alpha * C + beta`` with per-tile factors ``alpha ~ U[1 - sigma1, 1 + sigma1]``, ``beta ~ U[-sigma2, sigma2]``, and the tile is
+rebuilt.  With a fitted reference (``reference=`` or ``normalizer=``) the tile is normalised to it and jittered in one call:
+``C' = alpha * (C * target_max_conc / maxC) + beta`` rebuilt with the reference's stain matrix.  One library call per batch
+(``MacenkoHIP.augment``, include/stainx_hip.h: sx_macenko_augment); the factors never leave the device.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any
+
+import torch
+import torch.nn as nn
+
+from stainx_amd.normalizers import Macenko
+
+
+class MacenkoAugment(nn.Module):
+    """Random per-tile H&E concentration jitter of CHW / NCHW tensors on an MI355X.
+
+    ``reference`` (fitted once, pooled over its tiles) or a fitted ``Macenko`` as ``normalizer`` selects normalise-and-jitter
+    mode; with neither, every tile keeps its own stain basis.  ``device=None`` follows the input tensor.  ``normalize_to_0_1``
+    (default True, as ``StainNormalizerTransform``): uint8 tiles come out as float32 in [0, 1], float tiles are divided by 255.
+    ``generator`` drives ``sample_factors``; ``forward(img, alpha, beta)`` takes explicit (N, 2) factors instead.
+    """
+
+    def __init__(self, sigma1: float = 0.2, sigma2: float = 0.2, *, reference: torch.Tensor | None = None, normalizer: Macenko | None = None,
+                 device: str | torch.device | None = None, normalize_to_0_1: bool = True, generator: torch.Generator | None = None):
+        super().__init__()
+        sigma1, sigma2 = float(sigma1), float(sigma2)
+        if not (math.isfinite(sigma1) and 0.0 <= sigma1 < 1.0):
+            raise ValueError(f"sigma1 must lie in [0, 1) (alpha ~ U[1 - sigma1, 1 + sigma1] stays positive), got {sigma1}")
+        if not (math.isfinite(sigma2) and sigma2 >= 0.0):
+            raise ValueError(f"sigma2 must be a finite value >= 0, got {sigma2}")
+        if reference is not None and normalizer is not None:
+            raise ValueError("pass either reference= or normalizer=, not both")
+        self.sigma1, self.sigma2 = sigma1, sigma2
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"MacenkoAugment runs on a CUDA (ROCm) device, got {self.device}")
+        self.normalize_to_0_1 = bool(normalize_to_0_1)
+        self.generator = generator
+        self._engines: dict[torch.device, Any] = {}
+        if normalizer is not None:
+            if not isinstance(normalizer, Macenko):
+                raise ValueError(f"normalizer must be a stainx_amd.Macenko, got {type(normalizer).__name__}")
+            if not getattr(normalizer, "_is_fitted", False):
+                raise ValueError("normalizer must be fitted (call fit() first)")
+        elif reference is not None:
+            ref = self._batch(reference)
+            target = self._target_device(ref)
+            normalizer = Macenko(device=target, backend="torch_hip").fit(ref.to(target))
+        self.normalizer = normalizer
+
+    @staticmethod
+    def _batch(img: torch.Tensor) -> torch.Tensor:
+        if img.dim() == 3:
+            img = img.unsqueeze(0)
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"MacenkoAugment expects CHW / NCHW tensors with C=3, got shape {tuple(img.shape)}")
+        return img
+
+    def _target_device(self, batch: torch.Tensor) -> torch.device:
+        device = self.device if self.device is not None else batch.device
+        if device.type != "cuda":
+            raise ValueError(f"MacenkoAugment runs on a CUDA (ROCm) device; got a tensor on {device} (pass device='cuda' or move it there)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def _engine(self, device: torch.device):
+        engine = self._engines.get(device)
+        if engine is None:
+            from stainx_amd.backends.torch_hip_backend import MacenkoHIP
+
+            engine = self._engines[device] = MacenkoHIP(device)
+        return engine
+
+    def sample_factors(self, n: int, device: str | torch.device | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(alpha, beta)``, each (n, 2) float32 on ``device``: ``alpha ~ U[1 - sigma1, 1 + sigma1]``, ``beta ~ U[-sigma2, sigma2]``
+        (exactly 1 and 0 for sigma = 0), drawn with the module's generator (on the generator's device, then moved)."""
+        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
+        draw_on = self.generator.device if self.generator is not None else device
+        u = torch.rand((2, n, 2), generator=self.generator, device=draw_on, dtype=torch.float32).to(device)
+        alpha = 1.0 + self.sigma1 * (2.0 * u[0] - 1.0)
+        beta = self.sigma2 * (2.0 * u[1] - 1.0)
+        return alpha, beta
+
+    def forward(self, img: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None) -> torch.Tensor:
+        single = img.dim() == 3
+        batch = self._batch(img)
+        device = self._target_device(batch)
+        if alpha is None or beta is None:
+            drawn = self.sample_factors(batch.shape[0], device)
+            alpha = drawn[0] if alpha is None else alpha
+            beta = drawn[1] if beta is None else beta
+        sm = tmc = None
+        if self.normalizer is not None:
+            sm, tmc = self.normalizer._stain_matrix.to(device), self.normalizer._target_max_conc.to(device)
+        out = self._engine(device).augment(batch.to(device), alpha, beta, sm, tmc, normalize_to_0_1=self.normalize_to_0_1)
+        return out.squeeze(0) if single else out
+
+    def extra_repr(self) -> str:
+        mode = "own basis" if self.normalizer is None else "normalise and jitter"
+        return f"sigma1={self.sigma1}, sigma2={self.sigma2}, mode={mode!r}, normalize_to_0_1={self.normalize_to_0_1}"

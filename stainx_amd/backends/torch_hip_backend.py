@@ -148,6 +148,60 @@ class MacenkoHIP(TorchHIPBackendBase):
         self.last_workspace = ws
         return out
 
+    def augment(self, images: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, stain_matrix: torch.Tensor | None = None,
+                target_max_conc: torch.Tensor | None = None, *, normalize_to_0_1: bool = False, channels_last: bool = False,
+                out_dtype: torch.dtype | None = None) -> torch.Tensor:
+        """Stain augmentation (an extension; include/stainx_hip.h: sx_macenko_augment): every tile's H and E concentrations, in
+        the tile's own stain basis, become ``alpha * C + beta`` (``alpha``, ``beta``: (N, 2) per tile, (H, E)) and the tile is
+        rebuilt -- with its own ``HE_source`` when no reference is given, with the fitted ``stain_matrix`` after the transform's
+        rescaling ``C * target_max_conc / maxC`` otherwise.  Images, layout and output types as in ``transform``.  The factors are
+        read on the device: a captured call replayed after new values are copied into the same tensors uses the new values."""
+        images = images.to(self.device)
+        flags = 0
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = None
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError("stain_matrix and target_max_conc go together: both (normalise and jitter) or neither (each tile's own stain basis)")
+        if channels_last:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError(f"Macenko augment with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
+        else:
+            self._check_images(images, "augment")
+        n = images.shape[0]
+        if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
+            raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+        sm = tmc = None
+        if stain_matrix is not None:
+            if tuple(stain_matrix.shape) != (3, 2):
+                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+            sm = self._f32(stain_matrix)
+            tmc = self._f32(target_max_conc).flatten()
+            if tmc.numel() != 2:
+                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        # (already float32, contiguous and on the device -- the case of a captured call's fixed buffers -- these are the tensors themselves)
+        a, b = self._f32(alpha), self._f32(beta)
+        images = images.contiguous()
+        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
+        code = _dtype_code(images)
+        if out_dtype is None:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+        with _native.on_device(self.device):
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_augment(images.data_ptr(), out.data_ptr(), code, n, h, w, a.data_ptr(), b.data_ptr(),
+                                              sm.data_ptr() if sm is not None else None, tmc.data_ptr() if tmc is not None else None,
+                                              flags, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_augment", self._lib)
+        self.last_workspace = ws
+        return out
+
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.
         Never synchronises the host with the device except to wait for an answer that is five calls old (see below)."""

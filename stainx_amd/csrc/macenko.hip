@@ -119,6 +119,10 @@ struct Geometry {
     uint32_t fused_cap;           // fused: candidate records per tile and slot
     int fused_items;              // fused: pass-A work items of the call (= reconstruct work items)
     uint32_t code_epoch;          // four passes over float tiles: non-zero = the first pass leaves 8-bit codes, the later passes read them (Coded<F>); the call's number
+    const float* aug_alpha;       // sx_macenko_augment: per tile (H, E) factors of the concentrations, n_tiles x 2, read by the reconstruct pass (null: the transform)
+    const float* aug_beta;        // sx_macenko_augment: per tile (H, E) shifts of the concentrations, n_tiles x 2
+    int own_basis;                // sx_macenko_augment without a reference: every tile is rebuilt with its own HE_source, unscaled (no maxC: the
+                                  // estimate stops after the stain stage)
 };
 
 // Every field named: the struct is filled at half a dozen entry points.
@@ -1750,7 +1754,9 @@ __device__ void bracket_item(const T* __restrict__ images, const Geometry& g, co
 // ------------------------------------------------------------------------------------------------
 // streaming stage S4: concentrations -> rescale -> reconstruct -> clamp -> cast  (torch_backend.py:452-461,560)
 // ------------------------------------------------------------------------------------------------
-template <typename T, typename O, int V, bool kUnit, int TPB, bool kInter>
+// kAug (sx_macenko_augment): the tile's own factors C' = a C + b folded in as well, and -- g.own_basis -- the tile rebuilt with its own
+// HE_source; a separate instantiation, so that the transform's kernels are the same code as without it.
+template <typename T, typename O, int V, bool kUnit, int TPB, bool kInter, bool kAug = false>
 __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O* __restrict__ out, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id,
                                  const float* __restrict__ stain_matrix, const LevelTables<T>& tb, uint4* __restrict__ stage = nullptr, const float* __restrict__ given = nullptr) {
     const int64_t chunk = g.recon_chunk ? g.recon_chunk : (g.fine_chunk ? g.fine_chunk : g.chunk);
@@ -1761,9 +1767,17 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
     // the tile's pseudo-inverse (6) and scale (2): the stage record of the launch before this one, or (fused transform) what the
     // caller has read from the stage job of the same launch
     float rec8[8];
+    const float* sm_src = stain_matrix;
     if (given) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) rec8[i] = given[i];
+    } else if (kAug && g.own_basis) {
+        // (augmentation without a reference: the stain stage's pinv, scale 1 -- the scale stage has not run -- and the tile's HE_source)
+        const StageRecord* rec = &ws.state[tile].rec[1];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) rec8[i] = get(&rec->coef[i]);
+        rec8[6] = rec8[7] = 1.0f;
+        sm_src = ws.state[tile].he;
     } else {
         const StageRecord* rec = &ws.state[tile].rec[2];
 #pragma unroll
@@ -1777,15 +1791,25 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
     //   rgb_c = 2^x_c,   x_c = sum_j M[c][j] L_j + log2(240) (1 - sum_j M[c][j]),   L_j = log2(255 x_j + 1),
     //   M = SM diag(scale) pinv      (ln2 * log2e = 1 cancels between OD = ln240 - ln2 L and exp(-y) = 2^(-y log2e))
     // 9 fma per pixel instead of 20 multiply-adds; differs from the reference's operation order by ~1e-6 relative.
+    // Augmentation (C' = a C + b, OD' = SM C') stays affine in the same domain: M = SM diag(scale a) pinv, and the shift adds
+    // -log2(e) (SM b)_c to k_c.  With a = 1 and b = 0 both are exact no-ops (s * 1.0 = s; x - (+-0) = x): an identity augmentation
+    // has the transform's bits.
     float m[3][3], k[3];
     {
         double pinv[6], sm[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             pinv[i] = (double)rec8[i];
-            sm[i] = (double)stain_matrix[i];
+            sm[i] = (double)sm_src[i];
         }
-        const double s0 = (double)rec8[6], s1 = (double)rec8[7];
+        double s0 = (double)rec8[6], s1 = (double)rec8[7];
+        double b0 = 0.0, b1 = 0.0;
+        if constexpr (kAug) {
+            s0 = s0 * (double)get(&g.aug_alpha[2 * tile]);
+            s1 = s1 * (double)get(&g.aug_alpha[2 * tile + 1]);
+            b0 = (double)get(&g.aug_beta[2 * tile]);
+            b1 = (double)get(&g.aug_beta[2 * tile + 1]);
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             double row = 0.0;
@@ -1795,7 +1819,11 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
                 m[c][j] = (float)v;
                 row += (double)m[c][j];
             }
-            k[c] = (float)(7.90689059560851852932 * (1.0 - row));      // log2(240)
+            if constexpr (kAug) {
+                k[c] = (float)(7.90689059560851852932 * (1.0 - row) - 1.44269504088896340736 * (sm[c * 2] * b0 + sm[c * 2 + 1] * b1));      // log2(240), log2(e)
+            } else {
+                k[c] = (float)(7.90689059560851852932 * (1.0 - row));      // log2(240)
+            }
         }
     }
 
@@ -2580,7 +2608,7 @@ __global__ __launch_bounds__(kStreamThreads) void bracket_kernel(const T* __rest
     bracket_item<T, V, kConc, kStreamThreads, kInter>(images, g, ws, blockIdx.x / per_tile, blockIdx.x % per_tile, blockIdx.x, &sh, tb);
 }
 
-template <typename T, typename O, int V, bool kUnit, bool kInter = false>
+template <typename T, typename O, int V, bool kUnit, bool kInter = false, bool kAug = false>
 __global__ __launch_bounds__(kStreamThreads) void reconstruct_kernel(const T* __restrict__ images, O* __restrict__ out, Geometry g, Workspace ws, const float* __restrict__ stain_matrix) {
     const int per_tile = g.recon_chunk ? g.recon_blocks : (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile);
     __shared__ LevelTables<T> tb;
@@ -2590,15 +2618,15 @@ __global__ __launch_bounds__(kStreamThreads) void reconstruct_kernel(const T* __
         if (g.code_epoch != 0u && get(&ws.code_bad[item / per_tile]) != g.code_epoch) {      // the tile is 8-bit levels: its codes in, the same float pixels out
             __shared__ LevelTables<Coded<T>> ctb;
             ctb.fill();
-            reconstruct_item<Coded<T>, O, V, kUnit, kStreamThreads, false>(reinterpret_cast<const Coded<T>*>(ws.codes), out, g, ws, item / per_tile, item % per_tile, stain_matrix, ctb);
+            reconstruct_item<Coded<T>, O, V, kUnit, kStreamThreads, false, kAug>(reinterpret_cast<const Coded<T>*>(ws.codes), out, g, ws, item / per_tile, item % per_tile, stain_matrix, ctb);
             return;
         }
     }
     if constexpr (kInter && V > 1) {
         __shared__ uint4 stage[kStreamThreads * 3];      // 3 KB per wave: store_pixels_staged()
-        reconstruct_item<T, O, V, kUnit, kStreamThreads, kInter>(images, out, g, ws, item / per_tile, item % per_tile, stain_matrix, tb, stage);
+        reconstruct_item<T, O, V, kUnit, kStreamThreads, kInter, kAug>(images, out, g, ws, item / per_tile, item % per_tile, stain_matrix, tb, stage);
     } else {
-        reconstruct_item<T, O, V, kUnit, kStreamThreads, kInter>(images, out, g, ws, item / per_tile, item % per_tile, stain_matrix, tb);
+        reconstruct_item<T, O, V, kUnit, kStreamThreads, kInter, kAug>(images, out, g, ws, item / per_tile, item % per_tile, stain_matrix, tb);
     }
 }
 
@@ -2870,6 +2898,7 @@ static int run_estimate(const T* images, const Geometry& g, const Workspace& ws,
     } else {
         hipLaunchKernelGGL((stain_kernel<T>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws);
     }
+    if (g.own_basis) return check_launch("macenko estimate");      // (sx_macenko_augment without a reference: HE_source and its pinv are all it needs)
     hipLaunchKernelGGL((bracket_kernel<T, V, true, kInter>), dim3(grid_b), dim3(kStreamThreads), 0, stream, images, g, ws);
     if (g.spread) {
         hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)g.n_tiles), dim3(512), 0, stream, g, ws, 1);
@@ -2963,10 +2992,16 @@ static int run_transform(const T* images, O* out, const Geometry& g, const Works
         gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
         items_r = (unsigned)(g.n_tiles * gr.recon_blocks);
     }
-    if (unit)
+    if (g.aug_alpha) {      // (sx_macenko_augment: the per-tile factors folded in; its own instantiations)
+        if (unit)
+            hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, true, kInter, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm);
+        else
+            hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, false, kInter, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm);
+    } else if (unit) {
         hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, true, kInter>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm);
-    else
+    } else {
         hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, false, kInter>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm);
+    }
     return check_launch("macenko reconstruct");
 }
 
@@ -3587,6 +3622,43 @@ extern "C" int sx_macenko_transform(const void* images, void* out, int dtype, in
     if (flags & SX_MACENKO_NO_CODES) g.code_epoch = 0u;
 #endif
     const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    switch (dtype) {
+        case SX_U8: return transform_typed<uint8_t>(images, out, g, ws, sm, tmc, unit, stream);
+        case SX_F16: return transform_typed<__half>(images, out, g, ws, sm, tmc, unit, stream);
+        case SX_BF16: return transform_typed<__hip_bfloat16>(images, out, g, ws, sm, tmc, unit, stream);
+        case SX_F32: return transform_typed<float>(images, out, g, ws, sm, tmc, unit, stream);
+        case SX_F64: return transform_typed<double>(images, out, g, ws, sm, tmc, unit, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// Stain augmentation: the four passes of the transform (own basis: stats, plane, angle bracket and stain stage only), the per-tile factors
+// folded into the reconstruct pass's 3x3 matrix and offset.  Never the two-pass form, so no telemetry and no routing.
+extern "C" int sx_macenko_augment(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* alpha, const float* beta, const float* sm,
+                                  const float* tmc, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!out || !alpha || !beta) return fail(SX_ERR_BAD_ARG, "out / alpha / beta pointer is null");
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise and jitter) or both null (own basis)");
+    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_augment takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
+    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
+        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    Geometry g = make_geometry(n, h * w, 0);
+    g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
+    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    g.aug_alpha = alpha;
+    g.aug_beta = beta;
+    g.own_basis = sm == nullptr ? 1 : 0;
+    // (the codes of a float32 batch as in the transform's four passes)
+    size_t codes_at = 0;
+    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
+        g.code_epoch = next_code_epoch();
+        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
+    }
+    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
     switch (dtype) {
         case SX_U8: return transform_typed<uint8_t>(images, out, g, ws, sm, tmc, unit, stream);
         case SX_F16: return transform_typed<__half>(images, out, g, ws, sm, tmc, unit, stream);
