@@ -1374,11 +1374,26 @@ template <int TPB> struct StatsScratch {
     double red[TPB / kWave][kPartial];
 };
 
+// The pixels a lane adds up in one fp32 run of the moments passes, and their order.  V > 1: a pack of V, then the lane's pack TPB * V
+// further on.  V == 1 (pointers that are not 16-byte aligned) on a tile of whole packs: the same pixels in the same order, one at a
+// time -- lane_px = PackOf<T>::n consecutive ones, then TPB * lane_px further on -- so that a tile's moments, and with them its plane
+// and everything after it, have the bits of the packed pass.  On other tiles (lane_px 1) one pixel, then TPB further on.  (The
+// diagnostic build's scalar pass A of the two-pass form still takes one pixel per lane and step: its forced two-pass form on unaligned
+// tiles of whole packs is not bit for bit the four passes.)
+template <typename T, int V>
+__device__ __forceinline__ int64_t lane_pixels(int64_t pixels) { return (V == 1 && pixels % PackOf<T>::n == 0) ? PackOf<T>::n : V; }
+template <int V, int TPB>
+__device__ __forceinline__ int64_t next_lane_pixel(int64_t p, int64_t lane_px) {
+    if constexpr (V > 1) return p + (int64_t)TPB * V;
+    else return ((p + 1) & (lane_px - 1)) != 0 ? p + 1 : p + 1 + (int64_t)TPB * lane_px - lane_px;
+}
+
 // Moments of ALL pixels of a work item (see the end of stats_item): the same fp32 runs / fp64 sums as the kept set.  Not
 // (ordinary tiles never run it).
 template <typename T, int V, int TPB, bool kInter>
 __device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img, int64_t pixels, int64_t p_begin, int64_t p_end, double* __restrict__ dst, StatsScratch<TPB>* sh) {
     constexpr int kShortRun = 32 / V > 0 ? 32 / V : 1;
+    const int64_t lane_px = lane_pixels<T, V>(pixels);
     double acc[kPartial];
 #pragma unroll
     for (int k = 0; k < kPartial; ++k) acc[k] = 0.0;
@@ -1387,7 +1402,7 @@ __device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img,
 #pragma unroll
         for (int k = 0; k < kPartial; ++k) m[k] = 0.0f;
         const int64_t run_end = min(run + (int64_t)TPB * V * kShortRun, p_end);
-        for (int64_t p = run + (int64_t)threadIdx.x * V; p < run_end; p += (int64_t)TPB * V) {
+        for (int64_t p = run + (int64_t)threadIdx.x * lane_px; p < run_end; p = next_lane_pixel<V, TPB>(p, lane_px)) {
             float u[3][V];
             load_pixels<T, V, kInter>(img, pixels, p, u);
 #pragma unroll
@@ -1468,7 +1483,8 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
     // products and the sums over 32 pixels of a lane in fp32, everything beyond in fp64: the fp32 rounding is
     // unbiased and averages out over the tile (~4e-9 on a covariance entry, measured against the fp64 covariance
     // in the tests), the cancellation in sum(xy) - sum(x)*mean(y) happens in fp64
-    constexpr int kShortRun = 32 / V > 0 ? 32 / V : 1;      // packs per fp32 run
+    constexpr int kShortRun = 32 / V > 0 ? 32 / V : 1;      // packs per fp32 run (TPB * 32 pixels, whatever V is)
+    const int64_t lane_px = lane_pixels<T, V>(g.pixels);      // (V: the packed pass's grouping, see next_lane_pixel)
     double acc[kPartial];
 #pragma unroll
     for (int k = 0; k < kPartial; ++k) acc[k] = 0.0;
@@ -1477,7 +1493,7 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
     // two-byte pixels, and a wave that waits for the load it just issued leaves the vector ALU to the three or four others)
     // Two-byte pixels only (64 x 512 x 512 bf16 in this form 145 -> 141 us): float32 / float64 are bound by the read either way, and
     // the uint8 kernel has no registers to spare for a second set of packs (256 x 224 x 224 uint8 107.5 -> 111 us with it).
-    constexpr bool kAhead = sizeof(T) == 2 && !kEmit;
+    constexpr bool kAhead = sizeof(T) == 2 && !kEmit && V > 1;
     PixelPacks<T, V, kInter> ahead;
     ahead.clear();
     if (kAhead && p_begin + (int64_t)threadIdx.x * V < p_end) ahead.load(img, g.pixels, p_begin + (int64_t)threadIdx.x * V);
@@ -1486,7 +1502,7 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
 #pragma unroll
         for (int k = 0; k < kPartial; ++k) m[k] = 0.0f;
         const int64_t run_end = min(run + (int64_t)TPB * V * kShortRun, p_end);
-        for (int64_t p = run + (int64_t)threadIdx.x * V; p < run_end; p += (int64_t)TPB * V) {
+        for (int64_t p = run + (int64_t)threadIdx.x * lane_px; p < run_end; p = next_lane_pixel<V, TPB>(p, lane_px)) {
             PixelPacks<T, V, kInter> u;
             if constexpr (kAhead) {
                 u = ahead;
@@ -2840,7 +2856,10 @@ static bool aligned_for(const void* p, size_t bytes) { return (reinterpret_cast<
 // pixels -> 4 x 10240 + 9216 (57344 -> 51200 pixel-times per CU and sweep); 448 x 448: 13 items with a quarter-sized last one ->
 // 14 x 14336.  Taken when it saves more than 3 %, on the tile sizes of even_items_size().
 static void set_chunk(Geometry& g, bool may_add_item) {
-    const int64_t unit = (int64_t)kStreamThreads * (g.vec ? g.vec_width : 1);
+    // (a tile of whole packs is rounded by its packs also where its pointers are not 16-byte aligned: the same work items, and so the
+    // same moments, as with aligned pointers -- see next_lane_pixel)
+    const bool packs = g.vec || (g.vec_width > 1 && g.pixels % g.vec_width == 0);
+    const int64_t unit = (int64_t)kStreamThreads * (packs ? g.vec_width : 1);
     const int b0 = (int)((g.pixels + kChunk - 1) / kChunk);
     int best_b = b0;
     int64_t best_chunk = 0, best_cost = 0;
