@@ -136,7 +136,32 @@ int sx_macenko_augment(const void* images_dev, void* out_dev, int dtype, int64_t
                        const float* stain_matrix_dev, const float* target_max_conc_dev,
                        unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
 
-/* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_fit that used `workspace_dev`
+/* Stain separation (torchstain's normalize(..., stains=True), HistomicsTK's color_deconvolution, tiatoolbox's get_concentrations): every
+ * tile's H and E concentrations C = pinv(HE_source) OD, with the transform's per-tile estimate (exact percentiles), as images of one
+ * stain each and / or as concentration maps.
+ *   own basis    stain_matrix_dev == target_max_conc_dev == NULL:  C' = C,                        images built with the tile's HE_source
+ *   normalised   both given (a fitted reference):                  C' = C * target_max_conc / maxC, images built with stain_matrix
+ *                Exactly one of the two pointers NULL is SX_ERR_BAD_ARG.
+ *   H = clamp(240 exp(-basis[:,0] C'_H), 0, 255), E likewise with column 1 (torchstain's (H, E) with Io = 240), cast as the transform
+ *   casts: the input dtype; float32 /255 with SX_MACENKO_NORMALIZE_0_1 on uint8, the /255 fused on float input; bf16 / f16 with
+ *   SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 on uint8.  A tile whose maxC is 0 gets an infinite scale (as the transform); the other
+ *   stain's image and concentrations are not affected by it.
+ * Outputs, each may be NULL; at least one of stains_out_dev and conc_out_dev is required (SX_ERR_BAD_ARG otherwise):
+ *   stains_out_dev      (2, N, 3, H, W) of the image element: the H images, then the E images; (2, N, H, W, 3) with SX_MACENKO_CHANNELS_LAST
+ *   conc_out_dev        (N, 2, H, W) float32, C' (H, E); (N, H, W, 2) with SX_MACENKO_CHANNELS_LAST
+ *   tile_he_out_dev     N x 6 floats, HE_source (3, 2) row-major
+ *   tile_max_c_out_dev  N x 2 floats, maxC.  Free in normalised mode; in own-basis mode it adds the concentration bracket pass and the
+ *                       scale stage that own basis otherwise skips.
+ * Flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_CHANNELS_LAST, SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 (uint8 input), SX_MACENKO_CLASSIC
+ * (a no-op: separation always takes the four-pass estimate); any other bit, SX_MACENKO_SAMPLED included, is SX_ERR_BAD_ARG.  The workspace
+ * needs sx_macenko_workspace_bytes_for(dtype, n_tiles, height, width, SX_MACENKO_CLASSIC) bytes.  The H image is the bits of
+ * sx_macenko_augment(alpha = (1, 0), beta = (0, 0)) with the same reference or none, the E image those of alpha = (0, 1), wherever the
+ * other stain's scale is finite.  sx_macenko_tile_params after it reports the estimate (own basis without tile_max_c_out_dev: no maxC). */
+int sx_macenko_separate(const void* images_dev, void* stains_out_dev, float* conc_out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                        const float* stain_matrix_dev, const float* target_max_conc_dev, float* tile_he_out_dev, float* tile_max_c_out_dev,
+                        unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi
  *   [10..15] HE_source (3,2)  [16..17] maxC  [18] select paths taken (bit i: slot i fell back to the

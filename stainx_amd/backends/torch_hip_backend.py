@@ -202,6 +202,68 @@ class MacenkoHIP(TorchHIPBackendBase):
         self.last_workspace = ws
         return out
 
+    def separate(self, images: torch.Tensor, stain_matrix: torch.Tensor | None = None, target_max_conc: torch.Tensor | None = None, *,
+                 stains: bool = True, concentrations: bool = False, max_conc: bool = False, normalize_to_0_1: bool = False,
+                 channels_last: bool = False, out_dtype: torch.dtype | None = None) -> dict[str, torch.Tensor | None]:
+        """Stain separation (include/stainx_hip.h: sx_macenko_separate): every tile's H and E concentrations ``C = pinv(HE_source) OD``
+        (the transform's per-tile estimate), in the tile's own basis when no reference is given, normalised ``C * target_max_conc /
+        maxC`` with a fitted reference.  Returns ``stains`` (2, N, 3, H, W) -- the H images, then the E images, built with the tile's
+        ``HE_source`` or the reference's ``stain_matrix`` and typed as ``transform`` types its output --, ``concentrations`` (N, 2, H, W)
+        float32, ``he`` (N, 3, 2) and ``max_c`` (N, 2); an output not asked for is None.  ``max_c`` comes with normalised mode for free;
+        in own-basis mode ``max_conc=True`` adds the two launches that compute it.  ``channels_last``: NHWC images, (2, N, H, W, 3)
+        images and (N, H, W, 2) concentrations."""
+        images = images.to(self.device)
+        if not (stains or concentrations):
+            raise ValueError("separate: ask for stains, concentrations or both")
+        flags = 0
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = None
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError("stain_matrix and target_max_conc go together: both (normalised) or neither (each tile's own stain basis)")
+        if channels_last:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError(f"Macenko separate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
+        else:
+            self._check_images(images, "separate")
+        sm = tmc = None
+        if stain_matrix is not None:
+            if tuple(stain_matrix.shape) != (3, 2):
+                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+            sm = self._f32(stain_matrix)
+            tmc = self._f32(target_max_conc).flatten()
+            if tmc.numel() != 2:
+                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        images = images.contiguous()
+        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
+        code = _dtype_code(images)
+        if out_dtype is None:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        want_max_c = max_conc or sm is not None
+        out = {
+            "stains": torch.empty((2, *images.shape), dtype=out_dtype, device=self.device) if stains else None,
+            "concentrations": torch.empty((n, h, w, 2) if channels_last else (n, 2, h, w), dtype=torch.float32, device=self.device) if concentrations else None,
+            "he": torch.empty((n, 3, 2), dtype=torch.float32, device=self.device),
+            "max_c": torch.empty((n, 2), dtype=torch.float32, device=self.device) if want_max_c else None,
+        }
+        if n == 0 or h * w == 0:
+            return out
+        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        with _native.on_device(self.device):
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_separate(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, ptr(sm), ptr(tmc),
+                                               ptr(out["he"]), ptr(out["max_c"]), flags, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_separate", self._lib)
+        self.last_workspace = ws
+        return out
+
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.
         Never synchronises the host with the device except to wait for an answer that is five calls old (see below)."""

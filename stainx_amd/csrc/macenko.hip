@@ -1903,6 +1903,162 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
 }
 
 // ------------------------------------------------------------------------------------------------
+// streaming stage S4' (sx_macenko_separate): concentrations -> the H and E images and / or the concentration maps
+// ------------------------------------------------------------------------------------------------
+// Where the outputs of one separate call go; a null pointer is an output not asked for.
+struct SeparateOut {
+    void* stains;             // (2, N, 3, H, W) or (2, N, H, W, 3) of the output element: the H images, then the E images
+    float* conc;              // (N, 2, H, W) or (N, H, W, 2) float32: C'
+    float* tile_he;           // N x 6: HE_source
+    float* tile_max_c;        // N x 2: maxC
+    const float* sm;          // the reference's stain matrix; null: every tile in its own basis (scale 1)
+};
+
+// The grey level the transform's reconstruct pass writes for rgb in [0, 255], cast to the output element by its rules (reconstruct_item).
+template <typename T, typename O, bool kUnit>
+__device__ __forceinline__ O rgb_to_output(float rgb) {
+    using S = typename Sem<T>::type;
+    if constexpr (kUnit) {
+        if constexpr (sizeof(S) == 1) return Elem<O>::store(div255_of_level((float)Elem<S>::store(rgb)));
+        else if constexpr (sizeof(S) == 8) return (double)rgb / 255.0;
+        else return Elem<O>::store(div255_of_level(Elem<S>::load(Elem<S>::store(rgb))));
+    } else if constexpr (sizeof(S) == 1 && sizeof(O) == 2) {
+        return Elem<O>::store((float)Elem<T>::store(rgb));
+    } else {
+        return Elem<O>::store(rgb);
+    }
+}
+
+// One pass over the tile: every pixel's log2 levels L_j as the reconstruct pass takes them, then whichever outputs were asked for.
+// A separate kernel (not a branch of reconstruct_item: a run-time branch there raised the transform's registers).
+// The fold, per tile in fp64, rounded to fp32 coefficients in the log2 domain:
+//   stain image i (H: i = 0, E: i = 1), the reconstruct pass's 3x3 matrix with the other stain's factor 0 -- rank 1 --
+//     M_i[c][j] = (SM[c][i] s_i) pinv[i][j],   k_i[c] = log2(240) (1 - sum_j M_i[c][j]),   rgb_c = 2^(sum_j M_i[c][j] L_j + k_i[c])
+//   (these are the very roundings of sx_macenko_augment with alpha = e_i, beta = 0: the same bits wherever the other stain's scale
+//   is finite; where it is infinite the augmentation's s * 0 is a NaN, this fold never forms it)
+//   concentrations  C'_i = s_i sum_j pinv[i][j] OD_j,  OD_j = ln240 - ln2 L_j:
+//     C'_i = sum_j A[i][j] L_j + b_i,   A[i][j] = -ln2 s_i pinv[i][j],   b_i = ln240 s_i sum_j pinv[i][j]
+// s = tmc / maxC (normalised) or 1 (own basis: SM is the tile's HE_source).
+template <typename T, typename O, int V, bool kUnit, int TPB, bool kInter>
+__device__ __forceinline__ void separate_item(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id, const SeparateOut& so,
+                                              const LevelTables<T>& tb, uint4* __restrict__ stage = nullptr) {
+    const int64_t chunk = g.recon_chunk ? g.recon_chunk : (g.fine_chunk ? g.fine_chunk : g.chunk);
+    const int64_t p_begin = (int64_t)chunk_id * chunk;
+    const int64_t p_end = min(p_begin + chunk, g.pixels);
+    const T* img = images + tile * 3 * g.pixels;
+    const GroupState& st = ws.state[tile];
+    if (chunk_id == 0 && threadIdx.x < 8) {      // the tile's estimate, as sx_macenko_tile_params reports it
+        const int i = (int)threadIdx.x;
+        if (so.tile_he && i < 6) so.tile_he[tile * 6 + i] = get(&st.he[i]);
+        if (so.tile_max_c && i >= 6) so.tile_max_c[tile * 2 + (i - 6)] = get(&st.max_c[i - 6]);
+    }
+    const bool own = so.sm == nullptr;
+    const StageRecord* rec = &st.rec[own ? 1 : 2];      // (own basis: the stain stage's pinv -- the scale stage may not have run)
+    float mh[3][3], kh[3], me[3][3], ke[3], a[2][3], b[2];
+    {
+        double pinv[6], sm[6], s[2];
+        const float* basis = own ? st.he : so.sm;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            pinv[i] = (double)get(&rec->coef[i]);
+            sm[i] = (double)get(&basis[i]);
+        }
+        s[0] = own ? 1.0 : (double)get(&rec->scale[0]);
+        s[1] = own ? 1.0 : (double)get(&rec->scale[1]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double row_h = 0.0, row_e = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                mh[c][j] = (float)(sm[c * 2] * s[0] * pinv[j]);
+                me[c][j] = (float)(sm[c * 2 + 1] * s[1] * pinv[3 + j]);
+                row_h += (double)mh[c][j];
+                row_e += (double)me[c][j];
+            }
+            kh[c] = (float)(7.90689059560851852932 * (1.0 - row_h));      // log2(240)
+            ke[c] = (float)(7.90689059560851852932 * (1.0 - row_e));
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) a[i][j] = (float)(-0.69314718055994530942 * s[i] * pinv[3 * i + j]);      // ln 2
+            b[i] = (float)(5.48063892334199 * s[i] * (pinv[3 * i] + pinv[3 * i + 1] + pinv[3 * i + 2]));      // ln 240
+        }
+    }
+    O* hem = so.stains ? static_cast<O*>(so.stains) + tile * 3 * g.pixels : nullptr;
+    O* eos = so.stains ? static_cast<O*>(so.stains) + (g.n_tiles + tile) * 3 * g.pixels : nullptr;
+    float* conc = so.conc ? so.conc + tile * 2 * g.pixels : nullptr;
+
+    for (int64_t p = p_begin + (int64_t)threadIdx.x * V; p < p_end; p += (int64_t)TPB * V) {
+        float u[3][V];
+        if constexpr (!kInter && sizeof(T) * V == 16) {      // (the call's last reader of the input: non-temporal, as in reconstruct_item)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const Pack<T, V> pk = load_pack_stream<T, V>(img + c * g.pixels + p);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    if constexpr (sizeof(T) == 1) u[c][i] = __uint_as_float((uint32_t)pk.v[i]); else u[c][i] = raw_value<T>(pk.v[i]);
+                }
+            }
+        } else {
+            load_pixels<T, V, kInter, sizeof(T) == 1>(img, g.pixels, p, u);
+        }
+        float l[3][V];
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) l[c][i] = l2_of<T>(u[c][i], tb);
+        if (hem) {      // (uniform over the launch) the H image's packs, then the E image's
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float (&m)[3][3] = s == 0 ? mh : me;
+                const float (&k)[3] = s == 0 ? kh : ke;
+                O res[3][V];
+#pragma unroll
+                for (int i = 0; i < V; ++i)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float x = fmaf(m[c][2], l[2][i], fmaf(m[c][1], l[1][i], fmaf(m[c][0], l[0][i], k[c])));
+                        res[c][i] = rgb_to_output<T, O, kUnit>(fminf(fmaxf(__builtin_amdgcn_exp2f(x), 0.0f), 255.0f));      // :459, :128
+                    }
+                O* dst = s == 0 ? hem : eos;
+                if constexpr (kInter && V > 1 && sizeof(O) * V == 16) {
+                    if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {      // wave-uniform: every lane has a pack (store_pixels_staged)
+                        store_pixels_staged<O, V>(dst, p, res, stage + (threadIdx.x / kWave) * (3 * kWave));
+                        continue;
+                    }
+                }
+                store_pixels<O, V, kInter>(dst, g.pixels, p, res);
+            }
+        }
+        if (conc) {
+            float cc[2][V];
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) cc[s][i] = fmaf(a[s][2], l[2][i], fmaf(a[s][1], l[1][i], fmaf(a[s][0], l[0][i], b[s])));
+            if constexpr (kInter) {      // (H, W, 2): the lane's 2 V values side by side
+                if constexpr (V == 1) {
+                    conc[2 * p] = cc[0][0];
+                    conc[2 * p + 1] = cc[1][0];
+                } else {
+                    float flat[2 * V];
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        flat[2 * i] = cc[0][i];
+                        flat[2 * i + 1] = cc[1][i];
+                    }
+                    store_pack_stream<float, 2 * V>(conc + 2 * p, flat);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) store_pack_stream<float, V>(conc + s * g.pixels + p, cc[s]);
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // per-tile stage A ("plane"): moments -> covariance -> plane vectors; angle brackets from the sample
 // ------------------------------------------------------------------------------------------------
 // Optical density of the sample pixels this thread owns (written by S1).
@@ -2646,6 +2802,29 @@ __global__ __launch_bounds__(kStreamThreads) void reconstruct_kernel(const T* __
     }
 }
 
+// sx_macenko_separate's streaming pass: the reconstruct pass's work items, its coded float32 tiles and its staged NHWC stores
+template <typename T, typename O, int V, bool kUnit, bool kInter>
+__global__ __launch_bounds__(kStreamThreads) void separate_kernel(const T* __restrict__ images, Geometry g, Workspace ws, SeparateOut so) {
+    const int per_tile = g.recon_chunk ? g.recon_blocks : (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile);
+    __shared__ LevelTables<T> tb;
+    tb.fill();
+    const unsigned item = blockIdx.x;
+    if constexpr (Codable<T, V, kInter>::value) {
+        if (g.code_epoch != 0u && get(&ws.code_bad[item / per_tile]) != g.code_epoch) {      // the tile is 8-bit levels: its codes in
+            __shared__ LevelTables<Coded<T>> ctb;
+            ctb.fill();
+            separate_item<Coded<T>, O, V, kUnit, kStreamThreads, false>(reinterpret_cast<const Coded<T>*>(ws.codes), g, ws, item / per_tile, item % per_tile, so, ctb);
+            return;
+        }
+    }
+    if constexpr (kInter && V > 1 && sizeof(O) * V == 16) {
+        __shared__ uint4 stage[kStreamThreads * 3];
+        separate_item<T, O, V, kUnit, kStreamThreads, kInter>(images, g, ws, item / per_tile, item % per_tile, so, tb, stage);
+    } else {
+        separate_item<T, O, V, kUnit, kStreamThreads, kInter>(images, g, ws, item / per_tile, item % per_tile, so, tb);
+    }
+}
+
 
 template <typename T>
 __global__ __launch_bounds__(kGroupThreads) void fast_kernel(const T* __restrict__ images, Geometry g, Workspace ws, const float* __restrict__ target_max_conc) {
@@ -3098,6 +3277,24 @@ static int resident_transform(const void* images, void* out, int dtype, int64_t 
 
 #endif
 
+// Small batches: with 16384-pixel work items a single 512x512 tile is 16 workgroups on 256 CUs and a bracket pass takes
+// 15 us of pure latency.  The bracket and reconstruct stages (integer counts / independent pixels: the split cannot
+// change a bit of the result) then use smaller work items -- at least two sweeps of a workgroup, aiming at ~1024 work
+// items; the moments stage keeps its fixed 16384-pixel grouping so that a tile's covariance has the same bits
+// whatever batch it arrives in.  (lane_px: pixels per lane of the streaming passes)
+static void set_fine_chunk(Geometry& g, int lane_px) {
+    if (g.n_tiles * (int64_t)g.blocks_per_tile <= 32) {      // (measured: 1 tile 89 -> 78 us, 2 tiles 90 -> 81 us; from 4 tiles on the fixed cost per work item eats the gain)
+        const int64_t floor_px = (int64_t)kStreamThreads * lane_px * 2;
+        int64_t chunk = 2048;
+        while (chunk < floor_px) chunk *= 2;
+        while (chunk * 2 < kChunk && g.n_tiles * ((g.pixels + chunk - 1) / chunk) > 1024) chunk *= 2;
+        if (chunk < kChunk) {
+            g.fine_chunk = (int)chunk;
+            g.fine_blocks = (int)((g.pixels + chunk - 1) / chunk);
+        }
+    }
+}
+
 template <typename T>
 static int transform_typed(const void* images, void* out, const Geometry& g0, const Workspace& ws, const float* sm, const float* tmc, bool unit, hipStream_t stream) {
     Geometry g = g0;
@@ -3146,21 +3343,7 @@ static int transform_typed(const void* images, void* out, const Geometry& g0, co
         g.prior_units = (int)std::min<int64_t>(std::max<int64_t>(n_sectors / 4, std::min<int64_t>(n_sectors, 64)), kPriorUnitsMax);
         g.prior_step_q16 = (unsigned)((n_sectors << 16) / g.prior_units);
     }
-    // Small batches: with 16384-pixel work items a single 512x512 tile is 16 workgroups on 256 CUs and a bracket pass takes
-    // 15 us of pure latency.  The bracket and reconstruct stages (integer counts / independent pixels: the split cannot
-    // change a bit of the result) then use smaller work items -- at least two sweeps of a workgroup, aiming at ~1024 work
-    // items; the moments stage keeps its fixed 16384-pixel grouping so that a tile's covariance has the same bits
-    // whatever batch it arrives in.
-    if (g.n_tiles * (int64_t)g.blocks_per_tile <= 32 && !g.fused) {      // (the fused launch's reconstruct items are its pass-A items) (measured: 1 tile 89 -> 78 us, 2 tiles 90 -> 81 us; from 4 tiles on the fixed cost per work item eats the gain)
-        const int64_t floor_px = (int64_t)kStreamThreads * (vec ? W : 1) * 2;
-        int64_t chunk = 2048;
-        while (chunk < floor_px) chunk *= 2;
-        while (chunk * 2 < kChunk && g.n_tiles * ((g.pixels + chunk - 1) / chunk) > 1024) chunk *= 2;
-        if (chunk < kChunk) {
-            g.fine_chunk = (int)chunk;
-            g.fine_blocks = (int)((g.pixels + chunk - 1) / chunk);
-        }
-    }
+    if (!g.fused) set_fine_chunk(g, vec ? W : 1);      // (the fused launch's reconstruct items are its pass-A items)
 #ifdef SX_STAMPS      // diagnostic builds: the reconstruct stage's work-item size from the environment (tools: A/B of its grid)
     if (const char* e = std::getenv("SX_RECON_CHUNK")) {
         const int64_t c = std::atoll(e);
@@ -3209,6 +3392,65 @@ static int transform_typed(const void* images, void* out, const Geometry& g0, co
 #endif
     return vec ? run_transform<T, T, W>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream)
                : run_transform<T, T, 1>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream);
+}
+
+// sx_macenko_separate: the four-pass estimate (own basis without maxC: stats, plane, angle bracket and stain stage only), then one
+// streaming pass.  Its pack is 16 bytes of output per lane and plane, sized by the images' element O (run_transform's VR rule); a call
+// that asks for concentrations only runs with O = float.
+template <typename T, typename O, int V, bool kUnit, bool kInter>
+static int run_separate(const T* images, const Geometry& g, const Workspace& ws, const SeparateOut& so, const float* tmc, hipStream_t stream) {
+    int rc = run_estimate<T, V, kInter>(images, g, ws, (int)g.n_tiles, 1, tmc, nullptr, nullptr, stream);
+    if (rc != SX_OK) return rc;
+    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    Geometry gr = g;
+    unsigned items = (unsigned)(g.n_tiles * (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile));
+    if (!g.fine_chunk && V > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {      // (big batches: one pack set per thread and work item, as run_transform)
+        gr.recon_chunk = kStreamThreads * VR;
+        gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
+        items = (unsigned)(g.n_tiles * gr.recon_blocks);
+    }
+    hipLaunchKernelGGL((separate_kernel<T, O, VR, kUnit, kInter>), dim3(items), dim3(kStreamThreads), 0, stream, images, gr, ws, so);
+    return check_launch("macenko separate");
+}
+
+template <typename T>
+static int separate_typed(const void* images, const Geometry& g0, const Workspace& ws, const SeparateOut& so, const float* tmc, bool unit, hipStream_t stream) {
+    Geometry g = g0;
+    const bool stains = so.stains != nullptr;
+    const bool u8_half = stains && sizeof(T) == 1 && g.out_code != 0;
+    const bool u8_unit = stains && unit && sizeof(T) == 1 && !u8_half;
+    const size_t out_elem = !stains ? sizeof(float) : (u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T)));
+    constexpr int W = PackOf<T>::n;
+    // (16-byte packs where every pointer allows them, as transform_typed decides; the scalar path otherwise)
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(so.stains, out_elem * W)) && (!so.conc || aligned_for(so.conc, 16));
+    g.vec = vec ? 1 : 0;
+    g.vec_width = W;
+    set_sampling(g, true);
+    if (!(vec && !g.interleaved && std::is_same<T, float>::value)) g.code_epoch = 0u;      // (the coded passes: planar float32 tiles in 16-byte packs)
+    set_fine_chunk(g, vec ? W : 1);
+    const T* in = static_cast<const T*>(images);
+    // (O: the images' element -- float for a call without images --, U: the fused /255; NHWC tiles have their own instantiations)
+#define SX_RUN_SEP(O, U)                                                                                                                 \
+    return g.interleaved ? (vec ? run_separate<T, O, W, U, true>(in, g, ws, so, tmc, stream) : run_separate<T, O, 1, U, true>(in, g, ws, so, tmc, stream)) \
+                         : (vec ? run_separate<T, O, W, U, false>(in, g, ws, so, tmc, stream) : run_separate<T, O, 1, U, false>(in, g, ws, so, tmc, stream));
+    if (!stains) {
+        SX_RUN_SEP(float, false)
+    }
+    if constexpr (sizeof(T) == 1) {
+        if (u8_half && g.out_code == SX_BF16) {
+            if (unit) { SX_RUN_SEP(__hip_bfloat16, true) } else { SX_RUN_SEP(__hip_bfloat16, false) }
+        }
+        if (u8_half) {
+            if (unit) { SX_RUN_SEP(__half, true) } else { SX_RUN_SEP(__half, false) }
+        }
+        if (u8_unit) {
+            SX_RUN_SEP(float, true)
+        }
+        SX_RUN_SEP(T, false)
+    } else {
+        if (unit) { SX_RUN_SEP(T, true) } else { SX_RUN_SEP(T, false) }
+    }
+#undef SX_RUN_SEP
 }
 
 template <typename T>
@@ -3684,6 +3926,41 @@ extern "C" int sx_macenko_augment(const void* images, void* out, int dtype, int6
         case SX_BF16: return transform_typed<__hip_bfloat16>(images, out, g, ws, sm, tmc, unit, stream);
         case SX_F32: return transform_typed<float>(images, out, g, ws, sm, tmc, unit, stream);
         case SX_F64: return transform_typed<double>(images, out, g, ws, sm, tmc, unit, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// Stain separation: the four passes' per-tile estimate (own basis without maxC: stats, plane, angle bracket and stain stage only), then
+// one streaming pass that writes the H and E images and / or the concentration maps.  Never the two-pass form, so no telemetry and no routing.
+extern "C" int sx_macenko_separate(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const float* sm,
+                                   const float* tmc, float* tile_he_out, float* tile_max_c_out, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!stains_out && !conc_out) return fail(SX_ERR_BAD_ARG, "stains_out and conc_out are both null: nothing to separate into");
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalised) or both null (own basis)");
+    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_separate takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
+    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
+        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    Geometry g = make_geometry(n, h * w, 0);
+    g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
+    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    g.own_basis = (sm == nullptr && tile_max_c_out == nullptr) ? 1 : 0;      // (maxC asked for in own basis: the concentration bracket and the scale stage run, without a target)
+    size_t codes_at = 0;
+    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
+        g.code_epoch = next_code_epoch();
+        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
+    }
+    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    const SeparateOut so{stains_out, conc_out, tile_he_out, tile_max_c_out, sm};
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    switch (dtype) {
+        case SX_U8: return separate_typed<uint8_t>(images, g, ws, so, tmc, unit, stream);
+        case SX_F16: return separate_typed<__half>(images, g, ws, so, tmc, unit, stream);
+        case SX_BF16: return separate_typed<__hip_bfloat16>(images, g, ws, so, tmc, unit, stream);
+        case SX_F32: return separate_typed<float>(images, g, ws, so, tmc, unit, stream);
+        case SX_F64: return separate_typed<double>(images, g, ws, so, tmc, unit, stream);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }

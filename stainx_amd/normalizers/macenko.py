@@ -1,9 +1,26 @@
 """Macenko stain normalisation (API of stainx.Macenko, incl. ``normalize_to_0_1`` and ``precision``)."""
 from __future__ import annotations
 
-from typing import Any
+from typing import Any, NamedTuple
+
+import torch
 
 from stainx_amd.normalizers._template import NormalizerTemplate
+
+
+class StainSeparation(NamedTuple):
+    """What ``Macenko.separate`` returns (an extension; torchstain's ``normalize(..., stains=True)`` returns the first two).  A field
+    that was not asked for is None.
+    ``hematoxylin``, ``eosin``: (N, 3, H, W) images of one stain each, typed as ``transform`` types its output.
+    ``concentrations``: (N, 2, H, W) float32, the (H, E) concentrations (normalised to the reference when one is used).
+    ``stain_matrices``: (N, 3, 2) float32, each tile's own stain vectors ``HE_source``.
+    ``max_concentrations``: (N, 2) float32, each tile's 99th-percentile concentrations ``maxC`` (with the reference only)."""
+
+    hematoxylin: torch.Tensor | None
+    eosin: torch.Tensor | None
+    concentrations: torch.Tensor | None
+    stain_matrices: torch.Tensor
+    max_concentrations: torch.Tensor | None
 
 
 class Macenko(NormalizerTemplate):
@@ -43,3 +60,27 @@ class Macenko(NormalizerTemplate):
         if self.output_dtype is not None:
             options["out_dtype"] = self.output_dtype
         return options
+
+    def separate(self, images: Any, *, stains: bool = True, concentrations: bool = False, own_basis: bool | None = None) -> StainSeparation:
+        """Split every tile of ``images`` (NCHW) into its hematoxylin and eosin parts, with the transform's per-tile estimate.
+
+        ``own_basis=None``: each tile's own stain basis while the normaliser is unfitted, the fitted reference once it is fitted --
+        then ``C' = C * target_max_conc / maxC`` and the images are built with the reference's stain matrix (torchstain's ``H`` and
+        ``E``).  ``own_basis=True`` forces the tile's own basis; ``False`` requires a fit.  The images follow ``normalize_to_0_1`` and
+        ``output_dtype`` as ``transform`` does.  One library call (include/stainx_hip.h: sx_macenko_separate)."""
+        if not (stains or concentrations):
+            raise ValueError("separate: ask for stains, concentrations or both")
+        if self._precision == "sampled":
+            raise ValueError("separate has no approximate form: use precision='stable' or 'fast' (both run the exact kernels)")
+        if own_basis is None:
+            own_basis = not self._is_fitted
+        elif not own_basis and not self._is_fitted:
+            raise ValueError("own_basis=False separates with the fitted reference: call fit() first")
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) != 4 or shape[1] != 3:
+            raise ValueError(f"Macenko separate expects NCHW images with C=3, got shape {shape}")
+        reference = () if own_basis else (self._stain_matrix, self._target_max_conc)
+        out = self._get_backend_impl().separate(images, *reference, stains=stains, concentrations=concentrations, **self.call_options())
+        images_out = out["stains"]
+        return StainSeparation(images_out[0] if images_out is not None else None, images_out[1] if images_out is not None else None,
+                               out["concentrations"], out["he"], out["max_c"])
