@@ -562,7 +562,9 @@ __device__ __forceinline__ void store_codes(const Geometry& g, const Workspace& 
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         uint8_t* dst = ws.codes + ((size_t)tile * 3 + c) * g.pixels + p;
-        // (plain stores: the later passes find the codes in the L2s / the Infinity Cache -- non-temporal ones made pass A 54 -> 55.6 us and the reconstruct pass 37.4 -> 41.3)
+        // (plain stores: the later passes find the codes in the L2s / the Infinity Cache -- non-temporal ones made pass A 54 -> 55.6 us and the reconstruct pass 37.4 -> 41.3;
+        // write-through ones (agent-scope dword stores from pass A, so that the boundary in front of the stage has nothing to write back) pass A 54.0 -> 55.0 and the
+        // reconstruct pass 37.4 -> 38.3, the stage unchanged: a write-through store drops the line from the L2, and a 4-byte one is a fabric write of its own)
         if constexpr (W == 1) *reinterpret_cast<uint32_t*>(dst) = word[c][0]; else *reinterpret_cast<uint2*>(dst) = make_uint2(word[c][0], word[c][1]);
     }
 }

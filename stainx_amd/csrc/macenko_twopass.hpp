@@ -127,19 +127,19 @@ __device__ __forceinline__ void st_agent(double* p, double v) {
 __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 constexpr int kPriorBins = 2048;       // fixed-range histograms of the prior stage
+constexpr int kPriorAnglePlane = 4;    // PriorScratch::hist plane of the angle histogram
 constexpr float kOpenExponent = 30.0f;  // an open bracket side's stand-in direction lies w bracket widths beyond the sample extreme, w in [1/4, 1] such that
                                         // 0.01 n + w m >= this (the wanted quantile lies beyond it with probability ~e^-that: 1e-13)
 constexpr float kOpenNear = 16.0f;      // ... used when the closed side has at least this many independent sample pixels on its near side (m)
 struct alignas(16) PriorScratch {
     double red[kGroupThreads / kWave][kPartial];
     double mom[kMoments];
-    uint32_t hist[4][kPriorBins];
+    uint32_t hist[5][kPriorBins];      // planes 0-3: the concentration rows; plane 4: the angles (a plane of its own, so that nothing is zeroed again in the middle of the chain)
     uint32_t od16[kPriorSweeps][6][kGroupThreads];      // the sample's optical densities in fp16 (a thread's quad of a sweep: 12 halves), for the second look
     uint32_t n_kept, n_all, hazard, r_max;
     float frame[9];
     float bdir[4][2];
     float bkey[4], blevel[4];          // the four boundaries as diamond keys (before an open side is given its stand-in) and their quantile levels
-    float cthr[4];
     uint32_t cmax[4];
     uint32_t open;
 };
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
         sh.n_kept = sh.n_all = sh.hazard = sh.open = sh.r_max = 0;
         sh.cmax[0] = sh.cmax[1] = sh.cmax[2] = sh.cmax[3] = 0;
     }
-    for (int i = tid; i < 4 * kPriorBins; i += kGroupThreads) (&sh.hist[0][0])[i] = 0;
+    for (int i = tid; i < 5 * kPriorBins; i += kGroupThreads) (&sh.hist[0][0])[i] = 0;
 
     // ---- first look at the sample: moments of its kept pixels (fp32 per thread: 16 pixels; fp64 beyond).  The pixels are
     // not kept in registers across the eigen step (its fp64 code needs them all): they are read again afterwards, from L2.
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
         for (int s = 0; s < kPriorSweeps; ++s)
             if ((sub_kept >> s) & 1u) {
                 const float d = diamond_angle(t1[s][s], t0[s][s]);
-                atomicAdd(&sh.hist[0][min((uint32_t)fmaxf(d * (float)(kPriorBins / 2), 0.0f), (uint32_t)(kPriorBins - 1))], 1u);
+                atomicAdd(&sh.hist[kPriorAnglePlane][min((uint32_t)fmaxf(d * (float)(kPriorBins / 2), 0.0f), (uint32_t)(kPriorBins - 1))], 1u);
             }
     }
     __syncthreads();
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
         const bool open = mv < 16 || (upper ? level >= 1.0f : level <= 0.0f);
         const float pos = fminf(fmaxf(level, 0.0f), 1.0f) * (float)max(mv - 1, 0);
         const uint32_t rank = (uint32_t)min(max((int)(upper ? ceilf(pos) : floorf(pos)), 0), max(mv - 1, 0));
-        const uint32_t b = prior_pick_bin(sh.hist[0], rank);
+        const uint32_t b = prior_pick_bin(sh.hist[kPriorAnglePlane], rank);
         if (lane == 0) {
             // the bin's outer edge (an open side: the outer edge of the sample's extreme)
             sh.bkey[wave] = upper ? (float)(b + 1) * (2.0f / kPriorBins) : (float)b * (2.0f / kPriorBins);
@@ -469,8 +469,6 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
     // keys u . th lie in [-r_max, r_max]; the wanted quantile is far up the positive side: bins over [0, r_max], the rest in bin 0
     const float r_max = __uint_as_float(sh.r_max);
     const float c_scale = r_max > 0.0f ? (float)kPriorBins / r_max : 0.0f;
-    for (int i = tid; i < kPriorBins; i += kGroupThreads) sh.hist[0][i] = 0;      // (the angle histogram has been read)
-    __syncthreads();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         float k_max = 0.0f;
@@ -486,43 +484,48 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
     }
     __syncthreads();
     SX_STAMP(st, 6);
+    // (no barrier from here on: the wave that picks a threshold writes that test's row itself, and what the other rows and the
+    // record's header need was complete at the barrier above -- waves 4 and 5 write them meanwhile)
+    const float* a0 = &sh.frame[0];
+    const float* a1 = &sh.frame[3];
+    const float* an = &sh.frame[6];
     if (wave < 4) {
         const float n_eff = fmaxf((float)ms * (spec_eff(g) / 4.0f), 4.0f);
         const float level = 0.99f - g.spec_sigmas_conc * sqrtf(0.99f * 0.01f / n_eff);
         const uint32_t rank = (uint32_t)max((int)floorf(fmaxf(level, 0.0f) * (float)max(ms - 1, 0)), 0);
         const uint32_t b = prior_pick_bin(sh.hist[wave], rank);
-        if (lane == 0) sh.cthr[wave] = (level > 0.0f && b > 0) ? g.spec_tscale * (float)b * (r_max / (float)kPriorBins) : -__builtin_huge_valf();      // the bin's lower edge
-    }
-    __syncthreads();
-    if (tid < 9) {      // one test row per thread (compile-time indices: a run-time index would send bd / cu to scratch memory)
-        const float* a0 = &sh.frame[0];
-        const float* a1 = &sh.frame[3];
-        const float* an = &sh.frame[6];
+        if (lane == 0) {
+            const float cthr = (level > 0.0f && b > 0) ? g.spec_tscale * (float)b * (r_max / (float)kPriorBins) : -__builtin_huge_valf();      // the bin's lower edge
+            float row[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)      // (compile-time indices: a run-time index would send cu to scratch memory)
+                if (wave == q) {             // u . th - T
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) row[c] = cu[q][0] * a0[c] + cu[q][1] * a1[c];
+                }
+            row[3] = cthr > -1e30f ? -cthr : 60000.0f;      // no threshold: every pixel is a candidate
+#pragma unroll
+            for (int c = 0; c < 4; ++c) put(&pr->rows[kRowConc + wave][c], __half2float(__float2half_rn(row[c])));
+        }
+    } else if (wave == 4) {      // the rows that need no threshold, one per lane
         const uint32_t open = sh.open;
         float row[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (tid == q && ((open >> q) & 1u) == 0) {      // cross(d, th) = dx th1 - dy th0; an open side keeps the zero row
+            if ((int)lane == q && ((open >> q) & 1u) == 0) {      // cross(d, th) = dx th1 - dy th0; an open side keeps the zero row
 #pragma unroll
                 for (int c = 0; c < 3; ++c) row[c] = bd[q][0] * a1[c] - bd[q][1] * a0[c];
             }
-            if (tid == kRowConc + q) {                       // u . th - T
-#pragma unroll
-                for (int c = 0; c < 3; ++c) row[c] = cu[q][0] * a0[c] + cu[q][1] * a1[c];
-                row[3] = sh.cthr[q] > -1e30f ? -sh.cthr[q] : 60000.0f;      // no threshold: every pixel is a candidate
-            }
         }
-        if (tid == kRowW) {
+        if ((int)lane == kRowW) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) row[c] = an[c];
         }
+        if (lane < 16 && (lane < (uint32_t)kRowConc || lane >= (uint32_t)kRowW)) {      // (rows 9-15 stay zero)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) put(&pr->rows[tid][c], __half2float(__float2half_rn(row[c])));
-    } else if (tid < 16) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) put(&pr->rows[tid][c], 0.0f);
-    }
-    if (tid == 0) {
+            for (int c = 0; c < 4; ++c) put(&pr->rows[lane][c], __half2float(__float2half_rn(row[c])));
+        }
+    } else if (wave == 5 && lane == 0) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             put(&pr->a0[i], sh.frame[i]);
@@ -890,7 +893,12 @@ __global__ __launch_bounds__(kStreamThreads, (Codable<T, V, kInter>::value ? 4 :
 // ------------------------------------------------------------------------------------------------
 // K2 / K3: exact order statistic of one slot from its candidates, and the proof that it is the tile's
 // ------------------------------------------------------------------------------------------------
-struct alignas(16) SlotScratch {
+// what phi_bin_setup() leaves for phi_bin_range() (below)
+struct PhiBinSetup {
+    float inv[9];          // F^-1, rows
+    float dir[2][2];       // the two boundary directions in the prior frame
+};
+struct alignas(128) SlotScratch {
     TileScratch t;                     // radix_select_stream / rank_pick machinery; t.keys is the list of the picked bin
     uint32_t keys[kLdsKeys];
     float vecs[6], pinv[6], he[6];
@@ -903,6 +911,8 @@ struct alignas(16) SlotScratch {
     uint32_t own_key;
     int partner_ok;
     uint32_t k_floor, k_ceil, n_under;      // concentration slots: keys below k_floor are counted, not ranked; keys above k_ceil share the last bin
+    PriorRecord prior;                 // the tile's prior record, fetched at the top of the kernel: the one-thread checks that sit in the chain read it from here
+    PhiBinSetup phi_bins;
 };
 
 // The slot's candidates lie in one segment per wave of pass A (+ the tile's overflow area): prefix sums of the segment fills
@@ -997,6 +1007,10 @@ __device__ __forceinline__ void for_each_candidate(const CandPrefetch<kPre>& pf,
 // The same two steps over a DENSE candidate array (pass_a_kernel<kDense>): candidate i is record i; thread t takes i = t, t + blockDim, ...
 // -- adjacent lanes read adjacent records (one wave-instruction = 1 KB).  The first kPre records of a thread are requested before the
 // count is known (the range check of the buffer descriptor answers requests beyond the tile's records with zeros).
+// (The keys' histogram is filled on the way, and adjacent records are neighbours in the image.  A walk that sends a wave's lanes to
+// records far apart -- quads of records 37 quads apart, or 128-byte lines 37 lines apart -- was built for the sake of those LDS atomics
+// and lost: the bins span only the slot's bracket, where neighbours do not share a bin, and the scattered requests cost the stage
+// 3.3 / 1.2 us -- DESIGN.md 4a.)
 template <int kPre>
 __device__ __forceinline__ void prefetch_candidates_dense(CandPrefetch<kPre>& pf, __amdgpu_buffer_rsrc_t rsrc) {
 #pragma unroll
@@ -1043,24 +1057,25 @@ __device__ __forceinline__ void dense_count(SlotScratch* sh, const Geometry& g, 
 __device__ __forceinline__ uint32_t slot_key(const SlotScratch* sh, const uint32_t* __restrict__ spill, uint32_t i) { return i < (uint32_t)kLdsKeys ? sh->keys[i] : get(&spill[i - kLdsKeys]); }
 
 // The selection's scratch words; call before the keys are produced (a barrier must lie between this and select_slot_keys).
-__device__ __forceinline__ void select_prepare(SlotScratch* sh) {
+// keep_range: sh->lo / sh->hi are set by the thread that works out the slot's checks (the bins' range is known before the keys).
+__device__ __forceinline__ void select_prepare(SlotScratch* sh, bool keep_range = false) {
     if (threadIdx.x == 0) {
-        sh->lo = 0xFFFFFFFFu;
-        sh->hi = 0u;
+        if (!keep_range) {
+            sh->lo = 0xFFFFFFFFu;
+            sh->hi = 0u;
+        }
         sh->n_list = 0;
         sh->result = 0;
         sh->n_under = 0;
     }
     for (int i = threadIdx.x; i < 512; i += blockDim.x) (&sh->t.hist_c[0][0])[i] = 0;
 }
-// The range of the keys a thread produced (the phase that makes the keys also finds their range: one sweep less)
-__device__ __forceinline__ void publish_range(SlotScratch* sh, uint32_t mn, uint32_t mx) {
-    mn = wave_min_u32(mn);
-    mx = wave_max_u32(mx);
-    if (lane_id() == 0 && mn != 0xFFFFFFFFu) {
-        atomicMin(&sh->lo, mn);
-        atomicMax(&sh->hi, mx);
-    }
+// The level-0 bins of a slot: 256 value-linear bins over [max(lo, k_floor), min(hi, k_ceil)].  One function for whoever fills the
+// level-0 histogram while the keys are made and for select_slot_keys, which goes on from that histogram.
+__device__ __forceinline__ void slot_bins(const SlotScratch* sh, uint32_t k_floor, uint32_t k_ceil, double& origin, double& scale) {
+    const uint32_t lo = max(sh->lo, k_floor), hi = max(min(sh->hi, k_ceil), lo);
+    origin = bin_origin_for(lo);
+    scale = bin_scale_for(lo, hi);
 }
 
 // exact element of 0-based rank `rank` among the n keys of the slot (n >= 1, rank < n); whole workgroup, uniform result.
@@ -1077,8 +1092,8 @@ __device__ uint32_t select_slot_keys(SlotScratch* sh, const uint32_t* __restrict
     const int wave = threadIdx.x / kWave;
     // (an ODD share: the lanes of a wave read words `share` apart, and an even stride folds them onto a fraction of the LDS banks)
     const uint32_t share = ((n + blockDim.x - 1) / blockDim.x) | 1u, i_begin = min(threadIdx.x * share, n), i_end = min(i_begin + share, n);
-    const uint32_t lo = max(sh->lo, k_floor), hi = max(min(sh->hi, k_ceil), lo);
-    double origin = bin_origin_for(lo), scale = bin_scale_for(lo, hi);      // (lo, hi: the keys' range, or the range the caller binned them over)
+    double origin, scale;      // (sh->lo, sh->hi: the keys' range, or the range the caller binned them over)
+    slot_bins(sh, k_floor, k_ceil, origin, scale);
     uint32_t k_first = k_floor, k_last = 0xFFFFFFFFu, want = rank;      // the keys still in play: k_first <= key <= k_last
     uint32_t picked = 0;
     bool by_bin = false;      // the picked bin's keys are told by bin_of(), not by a key range
@@ -1171,8 +1186,11 @@ __device__ inline void frame_coordinates(const PriorRecord* pr, const float x[3]
 }
 
 // the tile's moments summed in the order plane_stage uses (index order; bit for bit the same doubles), then the plane
-template <typename T>
-__device__ void exact_plane(const Geometry& g, const Workspace& ws, int tile, SlotScratch* sh) {
+// Two parts: exact_moments() is wave 0's and waits for memory -- it comes FIRST in the kernel, in front of that wave's candidate
+// requests (loads return in order: behind eight 16-byte requests per lane the sums arrived a microsecond later, and nothing can
+// start before them); exact_plane() starts with a barrier.
+// tail(vecs): run by thread 0 in front of the last barrier (the one-thread work that needs the plane and that everybody waits for)
+__device__ __forceinline__ void exact_moments(const Geometry& g, const Workspace& ws, int tile, SlotScratch* sh) {
     const int64_t first = (int64_t)tile * g.blocks_per_tile;
     if (threadIdx.x < kPartial) {
         double running = 0.0;
@@ -1188,6 +1206,10 @@ __device__ void exact_plane(const Geometry& g, const Workspace& ws, int tile, Sl
     }
     if (threadIdx.x == kPartial) sh->t.mom[kPartial] = (double)g.pixels;
     if (threadIdx.x > kPartial && threadIdx.x < kMoments) sh->t.mom[threadIdx.x] = 0.0;
+}
+template <typename T, class Tail>
+__device__ void exact_plane(const Geometry& g, const Workspace& ws, int tile, SlotScratch* sh, Tail tail) {
+    const int64_t first = (int64_t)tile * g.blocks_per_tile;
     __syncthreads();
     if (__builtin_expect(sh->t.mom[0] < 3.0, 0)) {      // uniform, rare: every work item of such a tile left its all-pixel sums
         __syncthreads();
@@ -1224,6 +1246,7 @@ __device__ void exact_plane(const Geometry& g, const Workspace& ws, int tile, Sl
                 put(&st.rec[0].use_all, use_all ? 1 : 0);
                 put(&st.n_sel, n_sel);
             }
+            tail(vecs);
         }
     }
     __syncthreads();
@@ -1274,6 +1297,65 @@ __device__ inline bool phi_slot_check(const PriorRecord* pr, const float (&v)[6]
     }
     if (!(check[1] > check[0])) good = false;
     return good;
+}
+
+// The key range an angle slot's candidates are binned over, known before the keys are made: the keys of the slot's two bracket
+// boundaries mapped through the exact plane -- what phi_slot_check() tests the answer against.  An open side has no boundary; the
+// prior's stand-in direction just beyond its sample's extreme (prior_kernel; the concentration rows carry it) takes its place.  A range
+// steers speed only: keys beyond it share the end bins, and select_slot_keys is exact whatever the bins are.
+// Step 1 needs the prior record alone (one thread, while the moments arrive): F^-1 and the two directions in the prior frame.
+__device__ inline void phi_bin_setup(const PriorRecord* pr, int j, PhiBinSetup* out) {
+    const float f00 = get(&pr->a0[0]), f10 = get(&pr->a0[1]), f20 = get(&pr->a0[2]);
+    const float f01 = get(&pr->a1[0]), f11 = get(&pr->a1[1]), f21 = get(&pr->a1[2]);
+    const float f02 = get(&pr->an[0]), f12 = get(&pr->an[1]), f22 = get(&pr->an[2]);
+    const uint32_t open = get(&pr->open);
+    // prior_kernel: the concentration slot perpendicular to the HIGH vector is 0 iff min_first; its rows are (s, -c) of the high
+    // bracket's directions (c, s), the other slot's (-s, c) of the low bracket's
+    const int perp_high = get(&pr->min_first) ? 0 : 1;
+    float row[2][3];
+    bool stand_in[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        stand_in[e] = ((open >> (2 * j + e)) & 1u) != 0;
+        const float* r = pr->rows[stand_in[e] ? kRowConc + 2 * (j ? perp_high : 1 - perp_high) + e : 2 * j + e];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) row[e][c] = get(&r[c]);
+    }
+    const float c00 = f11 * f22 - f12 * f21, c01 = f12 * f20 - f10 * f22, c02 = f10 * f21 - f11 * f20;
+    const float det = f00 * c00 + f01 * c01 + f02 * c02;
+    const float s = det != 0.0f ? __builtin_amdgcn_rcpf(det) : 0.0f;
+    const float inv[9] = {c00 * s, (f02 * f21 - f01 * f22) * s, (f01 * f12 - f02 * f11) * s,
+                          c01 * s, (f00 * f22 - f02 * f20) * s, (f02 * f10 - f00 * f12) * s,
+                          c02 * s, (f01 * f20 - f00 * f21) * s, (f00 * f11 - f01 * f10) * s};
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out->inv[i] = inv[i];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const float g0 = inv[0] * row[e][0] + inv[1] * row[e][1] + inv[2] * row[e][2], g1 = inv[3] * row[e][0] + inv[4] * row[e][1] + inv[5] * row[e][2];
+        // a boundary row is cross(d, th): (g0, g1) = (-dy, dx); a stand-in is the row of the slot perpendicular to this bracket's vector
+        const bool flip = stand_in[e] && j == 1;
+        out->dir[e][0] = flip ? -g1 : g1;
+        out->dir[e][1] = flip ? g0 : -g0;
+    }
+}
+// Step 2, once the exact plane is there (one thread, everybody waits for it: two small matrix products and two keys)
+__device__ inline void phi_bin_range(const PhiBinSetup* su, const float (&v)[6], uint32_t& lo, uint32_t& hi) {
+    const float* inv = su->inv;
+    const float r00 = inv[0] * v[0] + inv[1] * v[2] + inv[2] * v[4], r01 = inv[3] * v[0] + inv[4] * v[2] + inv[5] * v[4];
+    const float r10 = inv[0] * v[1] + inv[1] * v[3] + inv[2] * v[5], r11 = inv[3] * v[1] + inv[4] * v[3] + inv[5] * v[5];
+    float key[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const float dx = su->dir[e][0], dy = su->dir[e][1];
+        const float mx = r00 * dx + r01 * dy, my = r10 * dx + r11 * dy;
+        key[e] = my > 0.0f ? diamond_angle(my, mx) : (e ? 2.0f : 0.0f);
+    }
+    if (!(key[1] > key[0])) {      // (no usable range: the whole diamond, and a second level sorts it out)
+        key[0] = 0.0f;
+        key[1] = 2.0f;
+    }
+    lo = float_key(key[0]);
+    hi = float_key(key[1]);
 }
 
 // The same for a concentration slot: the cone check, the bound Theta every non-candidate stays below, and the range of the bins.
@@ -1338,11 +1420,22 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
     bool use_all;
     unsigned long long rank_other;
     {   // ------------------------------------------------ angle percentile j
+        // (first what the chain waits for: the moments, wave 0; the prior record, 96 words by 96 threads of the last waves into LDS, so
+        // that the one-thread checks below and the concentration slot's wait for no memory; the bins' directions, one thread of wave 1)
+        exact_moments(g, ws, tile, &sh);
+        if (threadIdx.x >= kGroupThreads - (int)(sizeof(PriorRecord) / 4)) {
+            const int w = threadIdx.x - (kGroupThreads - (int)(sizeof(PriorRecord) / 4));
+            reinterpret_cast<uint32_t*>(&sh.prior)[w] = get(reinterpret_cast<const uint32_t*>(pr) + w);
+        }
+        if (threadIdx.x == kWave && mode == 0) phi_bin_setup(pr, j, &sh.phi_bins);
         CandPrefetch<8> pf;
         if constexpr (kDense) prefetch_candidates_dense(pf, rsrc_phi); else prefetch_candidates(pf, g, c0);
         select_prepare(&sh);
         if constexpr (kDense) dense_count(&sh, g, ws, tile, j); else segment_prefix(&sh, g, ws, tile, j);
-        exact_plane<T>(g, ws, tile, &sh);
+        // The range of the level-0 bins is known BEFORE the keys are made (phi_bin_range), so the histogram is filled while they are made.
+        exact_plane<T>(g, ws, tile, &sh, [&](const float (&vecs)[6]) {
+            if (mode == 0) phi_bin_range(&sh.phi_bins, vecs, sh.lo, sh.hi);
+        });
 #pragma unroll
         for (int i = 0; i < 6; ++i) v[i] = sh.vecs[i];
         if (stamps) SX_STAMP(st, 9);
@@ -1355,26 +1448,25 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         uint32_t* spill = spill_area + ((size_t)tile * kSlots + j) * spill_words;
         uint32_t answer = 0, why = 1u;
         if (ok) {      // uniform
-            // the exact keys of the candidates and their range; one thread works out the proof obligations meanwhile
-            uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+            // the exact keys of the candidates, binned on the way over the range between the two mapped boundaries;
+            // one thread works out the proof obligations meanwhile
+            double origin, scale;
+            slot_bins(&sh, 0u, 0xFFFFFFFFu, origin, scale);
+            uint32_t* hist = sh.t.hist_c[0];
             auto phi_key_of = [&](uint32_t i, const float (&od)[3]) {
                 const uint32_t k = angle_key(od, v);
-                mn = min(mn, k);
-                mx = max(mx, k);
                 if (i < (uint32_t)kLdsKeys) sh.keys[i] = k; else put(&spill[i - kLdsKeys], k);
+                atomicAdd(&hist[bin_of(k, origin, scale)], 1u);
             };
             if constexpr (kDense) for_each_candidate_dense(pf, n, rsrc_phi, phi_key_of); else for_each_candidate(pf, &sh, g, c0, phi_key_of);
-            publish_range(&sh, mn, mx);
-            if (threadIdx.x == kGroupThreads - 1) sh.ok = phi_slot_check(pr, v, j, sh.check, g.spec_rot) ? 1 : 0;
+            if (threadIdx.x == kGroupThreads - 1) sh.ok = phi_slot_check(&sh.prior, v, j, sh.check, g.spec_rot) ? 1 : 0;
             __syncthreads();
             if (stamps) SX_STAMP(st, 10);
             ok = sh.ok != 0;
             why = 2u;
         }
         if (ok) {
-            // (the histogram is NOT filled on the way: consecutive candidates are neighbours in the image with nearly the same
-            // key, and a wave's LDS atomics on one bin take their turns -- 5 us against 2 us for the sweep over contiguous shares)
-            answer = select_slot_keys(&sh, spill, n, (uint32_t)(rank - below), false);
+            answer = select_slot_keys(&sh, spill, n, (uint32_t)(rank - below), true);
             const float a = key_float(answer);
             const double slack = 4e-6;
             if (sh.check[2] == 0.0 && !((double)a >= sh.check[0] + slack)) ok = false;
@@ -1406,7 +1498,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
     CandPrefetch<12> pf;
     if constexpr (kDense) prefetch_candidates_dense(pf, rsrc_conc); else prefetch_candidates(pf, g, c1);      // in flight while the partner finishes
     __syncthreads();                     // everyone is done with the first selection's scratch
-    select_prepare(&sh);
+    select_prepare(&sh, true);           // (the bins' range comes from vectors_and_check: [k_floor, k_ceil])
     if constexpr (kDense) dense_count(&sh, g, ws, tile, slot); else segment_prefix(&sh, g, ws, tile, slot);      // (wave 0)
     auto vectors_and_check = [&](uint32_t partner_key) {      // one thread
         float he[6], pinv[6];
@@ -1419,7 +1511,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         }
         double theta = 0.0;
         float hi = 0.0f;
-        const bool good = mode == 0 && conc_slot_check(pr, pinv, j, theta, hi);
+        const bool good = mode == 0 && conc_slot_check(&sh.prior, pinv, j, theta, hi);
         sh.check[0] = theta;
         sh.ok = good ? 1 : 0;
         // The answer has to reach theta (that is the proof): the four candidates in five that lie below it -- each end test
@@ -1429,6 +1521,8 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         if ((double)key_float(kf) > bound && kf > 0u) --kf;      // (the largest float <= bound; consecutive keys are consecutive floats)
         sh.k_floor = good ? kf : 0u;
         sh.k_ceil = good ? max(float_key(hi), kf) : 0xFFFFFFFFu;
+        sh.lo = sh.k_floor;
+        sh.hi = sh.k_ceil;
     };
     if (threadIdx.x == kWave) {                  // (wave 1, meanwhile) the partner's key
         unsigned long long granule = 0;
@@ -1445,7 +1539,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         reset_scratch(&sh.t);
         const uint32_t partner_key = select_whole_group<T>(images, g, tile, 1 - j, rank_other, v, use_all, &sh.t, keep);
         __syncthreads();
-        select_prepare(&sh);
+        select_prepare(&sh, true);
         if (threadIdx.x == kWave) vectors_and_check(partner_key);
         __syncthreads();
     }
@@ -1465,18 +1559,19 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
     uint32_t answer = 0;
     if (ok) {
         const uint32_t k_floor = sh.k_floor, k_ceil = sh.k_ceil;
-        uint32_t mn = 0xFFFFFFFFu, mx = 0u, under = 0u;
+        // the exact keys, those that can be the answer (>= k_floor) binned on the way over [k_floor, k_ceil]
+        uint32_t under = 0u;
+        double origin, scale;
+        slot_bins(&sh, k_floor, k_ceil, origin, scale);
+        uint32_t* hist = sh.t.hist_c[0];
         auto conc_key_of = [&](uint32_t i, const float (&od)[3]) {
             float ca, cb;
             concentration(od, pinv, ca, cb);
             const uint32_t k = float_key(j ? cb : ca);
-            mn = min(mn, k);
-            mx = max(mx, k);
-            under += k < k_floor ? 1u : 0u;
             if (i < (uint32_t)kLdsKeys) sh.keys[i] = k; else put(&spill[i - kLdsKeys], k);
+            if (k < k_floor) ++under; else atomicAdd(&hist[bin_of(k, origin, scale)], 1u);
         };
         if constexpr (kDense) for_each_candidate_dense(pf, n, rsrc_conc, conc_key_of); else for_each_candidate(pf, &sh, g, c1, conc_key_of);
-        publish_range(&sh, mn, mx);
         under = wave_total_u32(under);
         if (lane_id() == 0 && under) atomicAdd(&sh.n_under, under);
         __syncthreads();
@@ -1487,7 +1582,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         if (rank_in < n_under) {      // the answer lies below theta: the proof has failed
             ok = false;
         } else {
-            answer = select_slot_keys(&sh, spill, n, (uint32_t)(rank_in - n_under), false, nullptr, k_floor, k_ceil);
+            answer = select_slot_keys(&sh, spill, n, (uint32_t)(rank_in - n_under), true, nullptr, k_floor, k_ceil);
             const double a = (double)key_float(answer), theta = sh.check[0];
             if (!(a >= theta + 4e-6 * fabs(theta) + 1e-7)) ok = false;
         }
