@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The hot path in five lines each: the three normalisers, the nn.Module, uint8 HWC tiles as a decoder hands them over,
-the sampled `precision="fast"` mode, and how a batch is split over GPUs (one process per GPU, no collective for
-`transform`).  Run on a ROCm GPU:  python examples/normalize_tiles.py
+the sampled `precision="fast"` mode, how a batch is split over GPUs (one process per GPU, no collective for
+`transform`), and the slide-level use: one source estimate, applied to batch after batch.  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -58,6 +58,17 @@ def main() -> None:
     # 5. one stain estimate pooled over the tiles of ALL ranks (a few small collectives), identical bits on every rank
     he_pooled, max_c_pooled = sxd.macenko_fit_pooled(tiles)
     print(f"[rank {rank}] pooled fit          HE[:,0] = {[round(v, 4) for v in he_pooled[:, 0].tolist()]}  maxC = {[round(v, 4) for v in max_c_pooled.tolist()]}")
+
+    # 6. slide level: ONE source estimate for the slide (pooled over a batch of its tissue tiles), applied to that batch and to the next
+    #    one -- neighbouring tiles get the same mapping, and a call is one launch: a pixel read, a pixel written, no estimate
+    norm = Macenko(device=dev).fit(reference.to(dev))
+    slide = norm.estimate(tiles, pooled=True)                        # StainEstimate: (1, 3, 2) stain vectors, (1, 2) maxC
+    out = norm.apply(tiles, slide)
+    more = synth.he_batch(8, 256, 256, seed0=4048).to(dev)           # more tiles of the same slide: no new estimate
+    out_more = norm.apply(more, slide)
+    per_tile = norm.estimate(tiles)                                  # every tile's own estimate fed back: the transform, bit for bit
+    assert torch.equal(norm.apply(tiles, per_tile), norm.transform(tiles))
+    print(f"[rank {rank}] slide-level apply   {tuple(out.shape)} + {tuple(out_more.shape)} {out.dtype}  maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

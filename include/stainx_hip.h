@@ -161,6 +161,45 @@ int sx_macenko_separate(const void* images_dev, void* stains_out_dev, float* con
                         const float* stain_matrix_dev, const float* target_max_conc_dev, float* tile_he_out_dev, float* tile_max_c_out_dev,
                         unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Slide-level use (torchstain's fit-the-source-elsewhere, tiatoolbox's and HistomicsTK's given stain matrices): estimate the source basis
+ * in one call, apply a GIVEN basis in another.  An extension: the reference estimates per tile inside every transform.
+ *
+ * sx_macenko_estimate: the transform's per-tile estimate (four passes, exact percentiles) and nothing else -- no output pass.
+ *   tile_he_out_dev      N x 6 floats, HE_source (3, 2) row-major
+ *   tile_max_c_out_dev   N x 2 floats, maxC
+ *   tile_tissue_out_dev  N floats, the pixels the optical-density filter kept (the tile's tissue); may be NULL
+ * They are the bits sx_macenko_tile_params reports (HE_source, maxC, n_selected) after sx_macenko_transform(..., SX_MACENKO_CLASSIC) of
+ * the same batch.  Flags: SX_MACENKO_CHANNELS_LAST, SX_MACENKO_CLASSIC (a no-op); any other bit is SX_ERR_BAD_ARG.  The workspace needs
+ * sx_macenko_workspace_bytes_for(dtype, n_tiles, height, width, SX_MACENKO_CLASSIC) bytes.  (One basis pooled over a batch: sx_macenko_fit.) */
+int sx_macenko_estimate(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                        float* tile_he_out_dev, float* tile_max_c_out_dev, float* tile_tissue_out_dev,
+                        unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* sx_macenko_apply: normalise (and optionally jitter) every tile with a GIVEN source basis -- ONE kernel launch on `stream`, nothing
+ * else enqueued, no workspace: a pixel is read, a pixel is written.
+ *   source_he_dev        n_sources x 6 floats, HE_source (3, 2) row-major
+ *   source_max_c_dev     n_sources x 2 floats, maxC; not read in own-basis mode, where it may be NULL
+ *   n_sources            1 (one basis for the whole batch) or n_tiles (row t serves tile t)
+ *   alpha_dev, beta_dev  n_tiles x 2 floats each, (H, E) per tile, both or neither (neither: alpha = 1, beta = 0)
+ *   normalise            stain_matrix_dev and target_max_conc_dev given (a fitted reference, as for sx_macenko_transform):
+ *                          C = pinv(source_he) OD,  C' = alpha * (C * target_max_conc / source_max_c) + beta,  OD' = stain_matrix C'
+ *   own basis            both NULL, alpha and beta required:  C' = alpha * C + beta,  OD' = source_he C'
+ *                        then, as the transform: out = clamp(240 exp(-OD'), 0, 255), cast to the output type.
+ * Exactly one pointer of a pair NULL, n_sources other than 1 or n_tiles, own basis without factors, source_max_c_dev NULL in normalise
+ * mode: SX_ERR_BAD_ARG, before anything is enqueued.  The source, the factors and the reference are DEVICE memory read by the kernel (a
+ * captured graph replayed after new values were written into the same buffers uses the new values).  Images, output and its element
+ * type follow sx_macenko_transform's rules; flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_CHANNELS_LAST, SX_MACENKO_OUT_BF16 /
+ * SX_MACENKO_OUT_F16 (uint8 input) and SX_MACENKO_CLASSIC (a no-op); any other bit, SX_MACENKO_SAMPLED included, is SX_ERR_BAD_ARG.
+ * The pseudo-inverse is a function of the six given floats (fp64, the rank rule of lstsq(rcond=None): a rank-1 basis drops its second
+ * singular value), the scale a float32 division, so a tile's own estimate fed back -- sx_macenko_estimate's outputs, n_sources =
+ * n_tiles -- gives the bits of sx_macenko_transform(..., SX_MACENKO_CLASSIC) without factors and of sx_macenko_augment with them,
+ * wherever the tile's maxC is finite and non-zero. */
+int sx_macenko_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                     const float* source_he_dev, const float* source_max_c_dev, int64_t n_sources,
+                     const float* alpha_dev, const float* beta_dev,
+                     const float* stain_matrix_dev, const float* target_max_conc_dev,
+                     unsigned flags, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

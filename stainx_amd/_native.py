@@ -52,6 +52,8 @@ SIGNATURES = {
     "sx_macenko_transform": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_augment": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_separate": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_macenko_estimate": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_macenko_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _uint, _vp]),
     "sx_macenko_fit": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),

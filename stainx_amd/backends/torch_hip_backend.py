@@ -264,6 +264,113 @@ class MacenkoHIP(TorchHIPBackendBase):
         self.last_workspace = ws
         return out
 
+    def estimate(self, images: torch.Tensor, *, channels_last: bool = False) -> dict[str, torch.Tensor]:
+        """The transform's per-tile estimate as a call of its own (include/stainx_hip.h: sx_macenko_estimate): ``he`` (N, 3, 2),
+        ``max_c`` (N, 2) and ``tissue`` (N,) -- the pixels the optical-density filter kept -- of every tile; no output pass.  Always
+        the exact percentiles: ``precision="sampled"`` is refused."""
+        if self._precision == "sampled":
+            raise ValueError("estimate computes the exact per-tile estimate; precision='sampled' has no estimate of its own")
+        images = images.to(self.device)
+        if channels_last:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError(f"Macenko estimate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
+        else:
+            self._check_images(images, "estimate")
+        images = images.contiguous()
+        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
+        code = _dtype_code(images)
+        out = {
+            "he": torch.empty((n, 3, 2), dtype=torch.float32, device=self.device),
+            "max_c": torch.empty((n, 2), dtype=torch.float32, device=self.device),
+            "tissue": torch.empty((n,), dtype=torch.float32, device=self.device),
+        }
+        if n == 0 or h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_estimate(images.data_ptr(), code, n, h, w, out["he"].data_ptr(), out["max_c"].data_ptr(), out["tissue"].data_ptr(),
+                                               _native.MACENKO_CHANNELS_LAST if channels_last else 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_estimate", self._lib)
+        self.last_workspace = ws
+        return out
+
+    def apply(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None = None,
+              target_max_conc: torch.Tensor | None = None, *, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None,
+              normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False) -> torch.Tensor:
+        """Normalise (and optionally jitter) with a GIVEN source basis (include/stainx_hip.h: sx_macenko_apply): one kernel launch, no
+        estimate, no workspace, no host synchronisation.  ``source_he`` is (3, 2) or (1, 3, 2) -- one basis for the batch -- or
+        (N, 3, 2), ``source_max_c`` (2,), (1, 2) or (N, 2) to match.  With ``stain_matrix`` / ``target_max_conc`` the tiles are
+        normalised to that reference, ``alpha`` / ``beta`` (N, 2) jitter the concentrations on top; without a reference (own basis)
+        the factors are required, the tile is rebuilt with ``source_he`` and ``source_max_c`` is not read (it may be None).  Images,
+        layout and output types as in ``transform``.  Source, factors and reference are read on the device: a captured call replayed
+        after new values are copied into the same tensors uses the new values."""
+        images = images.to(self.device)
+        flags = 0
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = None
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError("stain_matrix and target_max_conc go together: both (normalise) or neither (the given source basis is kept)")
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together: both or neither")
+        if stain_matrix is None and alpha is None:
+            raise ValueError("apply without a reference (own basis) needs the factors alpha and beta")
+        if channels_last:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError(f"Macenko apply with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
+        else:
+            self._check_images(images, "apply")
+        n = images.shape[0]
+        he_shape = tuple(source_he.shape)
+        if he_shape == (3, 2):
+            n_sources = 1
+        elif len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n):
+            n_sources = he_shape[0]
+        else:
+            raise ValueError(f"source_he must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
+        he = self._f32(source_he)
+        mc = None
+        if source_max_c is not None:
+            if source_max_c.numel() != 2 * n_sources or (source_max_c.dim() == 2 and tuple(source_max_c.shape) != (n_sources, 2)) or source_max_c.dim() > 2:
+                raise ValueError(f"source_max_c must hold 2 values per source basis, ({n_sources}, 2), got shape {tuple(source_max_c.shape)}")
+            mc = self._f32(source_max_c)
+        elif stain_matrix is not None:
+            raise ValueError("source_max_c is required to normalise to a reference (it may be None in own-basis mode only)")
+        a = b = None
+        if alpha is not None:
+            if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
+                raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+            a, b = self._f32(alpha), self._f32(beta)
+        sm = tmc = None
+        if stain_matrix is not None:
+            if tuple(stain_matrix.shape) != (3, 2):
+                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+            sm = self._f32(stain_matrix)
+            tmc = self._f32(target_max_conc).flatten()
+            if tmc.numel() != 2:
+                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        images = images.contiguous()
+        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
+        code = _dtype_code(images)
+        if out_dtype is None:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        with _native.on_device(self.device):
+            rc = self._lib.sx_macenko_apply(images.data_ptr(), out.data_ptr(), code, n, h, w, he.data_ptr(), ptr(mc), n_sources, ptr(a), ptr(b),
+                                            ptr(sm), ptr(tmc), flags, _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_apply", self._lib)
+        return out
+
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.
         Never synchronises the host with the device except to wait for an answer that is five calls old (see below)."""

@@ -872,26 +872,11 @@ __device__ __forceinline__ void direction_from_key(uint32_t key, float& c, float
     s = (float)(y * inv);
 }
 
-// Angle percentiles (as keys) -> extreme stain vectors -> HE_source (H before E) -> its (2,3) pseudo-inverse.
-__device__ void stain_vectors_and_pinv(const float* vecs, uint32_t key_lo, uint32_t key_hi, float* he_out, float* pinv_out) {
-    float cl, sl, ch, sh;
-    direction_from_key(key_lo, cl, sl);
-    direction_from_key(key_hi, ch, sh);
-    float vmin[3], vmax[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        vmin[r] = fmaf(vecs[r * 2 + 1], sl, vecs[r * 2] * cl);                                   // :436
-        vmax[r] = fmaf(vecs[r * 2 + 1], sh, vecs[r * 2] * ch);                                   // :437
-    }
-    const bool min_first = vmin[0] > vmax[0];                                                    // :439
-    float he[6];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        he[r * 2] = min_first ? vmin[r] : vmax[r];
-        he[r * 2 + 1] = min_first ? vmax[r] : vmin[r];
-    }
-    // pseudo-inverse (2,3) of HE (3,2) in fp64 through the eigen-decomposition of HE^T HE, dropping a
-    // singular value below 3*eps_f32 of the largest (rank rule of lstsq(rcond=None), torch_backend.py:379)
+// The (2,3) pseudo-inverse of a (3,2) stain basis HE, a function of its six float32 values alone: the stain stage forms it from the
+// tile's estimate, sx_macenko_apply's prologue from the basis it is given -- the same bits from the same six floats.
+// fp64 through the eigen-decomposition of HE^T HE, dropping a singular value below 3*eps_f32 of the largest (rank rule of
+// lstsq(rcond=None), torch_backend.py:379)
+__device__ __forceinline__ void pinv_of_he(const float (&he)[6], float* pinv_out) {
     const double a = (double)he[0] * he[0] + (double)he[2] * he[2] + (double)he[4] * he[4];
     const double b = (double)he[0] * he[1] + (double)he[2] * he[3] + (double)he[4] * he[5];
     const double d = (double)he[1] * he[1] + (double)he[3] * he[3] + (double)he[5] * he[5];
@@ -928,6 +913,27 @@ __device__ void stain_vectors_and_pinv(const float* vecs, uint32_t key_lo, uint3
         pinv_out[c] = (float)(g00 * he[c * 2] + g01 * he[c * 2 + 1]);
         pinv_out[3 + c] = (float)(g01 * he[c * 2] + g11 * he[c * 2 + 1]);
     }
+}
+
+// Angle percentiles (as keys) -> extreme stain vectors -> HE_source (H before E) -> its (2,3) pseudo-inverse.
+__device__ void stain_vectors_and_pinv(const float* vecs, uint32_t key_lo, uint32_t key_hi, float* he_out, float* pinv_out) {
+    float cl, sl, ch, sh;
+    direction_from_key(key_lo, cl, sl);
+    direction_from_key(key_hi, ch, sh);
+    float vmin[3], vmax[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        vmin[r] = fmaf(vecs[r * 2 + 1], sl, vecs[r * 2] * cl);                                   // :436
+        vmax[r] = fmaf(vecs[r * 2 + 1], sh, vecs[r * 2] * ch);                                   // :437
+    }
+    const bool min_first = vmin[0] > vmax[0];                                                    // :439
+    float he[6];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        he[r * 2] = min_first ? vmin[r] : vmax[r];
+        he[r * 2 + 1] = min_first ? vmax[r] : vmin[r];
+    }
+    pinv_of_he(he, pinv_out);
 #pragma unroll
     for (int i = 0; i < 6; ++i) he_out[i] = he[i];
 }
@@ -2827,6 +2833,154 @@ __global__ __launch_bounds__(kStreamThreads) void separate_kernel(const T* __res
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// sx_macenko_apply: the reconstruct pass with a GIVEN source basis -- one launch, no workspace, no estimate
+// ------------------------------------------------------------------------------------------------
+// Everything the kernel reads besides the pixels is device memory of the caller, read by the kernel itself (a captured graph
+// replayed after new values were written into the same buffers uses the new values).
+struct ApplyArgs {
+    const float* he;          // n_sources x 6: HE_source (3,2) row-major
+    const float* max_c;       // n_sources x 2: maxC; not read in own-basis mode
+    const float* alpha;       // N x 2 factors of the concentrations, or null (with beta): none
+    const float* beta;        // N x 2 shifts
+    const float* sm;          // the reference's stain matrix; null: own basis (the tile is rebuilt with the given HE, unscaled)
+    const float* tmc;         // the reference's maximal concentrations
+    int64_t pixels;           // P = H*W
+    int chunk, blocks;        // pixels per work item, work items per tile
+    int per_tile;             // 1: source row `tile`, 0: one row for the batch
+};
+
+// A separate kernel (as separate_kernel: the transform's reconstruct instantiations stay the code they were).  Per work item:
+//   1. every thread requests its first pack set -- the addresses depend on nothing the prologue computes;
+//   2. under that latency ONE thread builds the tile's fold from the arguments: pinv_of_he() of the given HE, scale = target_max_conc /
+//      maxC in float32 as the scale stage forms it, then M and k in the log2 domain with reconstruct_item's very expressions (the
+//      factors default to alpha = 1, beta = 0, which are exact no-ops there) -- some 150 fp64 operations that the other three waves of
+//      the workgroup do not issue -- and hands the twelve floats over through LDS;
+//   3. the pixels stream through reconstruct_item's arithmetic and store paths.
+// The result does not depend on how a tile is cut into work items (independent pixels), nor on n_sources (the same six + two floats
+// give the same fold).
+template <typename T, typename O, int V, bool kUnit, bool kInter>
+__global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restrict__ images, O* __restrict__ out, ApplyArgs a) {
+    constexpr int TPB = kStreamThreads;
+    __shared__ LevelTables<T> tb;
+    __shared__ float fold[12];
+    const int64_t tile = blockIdx.x / (unsigned)a.blocks;
+    const int chunk_id = (int)(blockIdx.x % (unsigned)a.blocks);
+    const int64_t p_begin = (int64_t)chunk_id * a.chunk;
+    const int64_t p_end = min(p_begin + (int64_t)a.chunk, a.pixels);
+    const T* img = images + tile * 3 * a.pixels;
+    O* dst = out + tile * 3 * a.pixels;
+
+    // (the input is read once: planar 16-byte packs non-temporally, as in reconstruct_item)
+    auto load = [&](int64_t p, float (&u)[3][V]) {
+        if constexpr (!kInter && sizeof(T) * V == 16) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const Pack<T, V> pk = load_pack_stream<T, V>(img + c * a.pixels + p);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    if constexpr (sizeof(T) == 1) u[c][i] = __uint_as_float((uint32_t)pk.v[i]); else u[c][i] = raw_value<T>(pk.v[i]);
+                }
+            }
+        } else {
+            load_pixels<T, V, kInter, sizeof(T) == 1>(img, a.pixels, p, u);
+        }
+    };
+    int64_t p = p_begin + (int64_t)threadIdx.x * V;
+    float u[3][V];
+    if (p < p_end) load(p, u);
+
+    if (threadIdx.x == 0) {
+        const bool own = a.sm == nullptr;
+        const float* he_src = a.he + (a.per_tile ? tile * 6 : 0);
+        float he[6], rec8[8];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) he[i] = he_src[i];
+        pinv_of_he(he, rec8);
+        if (own) {
+            rec8[6] = rec8[7] = 1.0f;
+        } else {
+            const float* mc = a.max_c + (a.per_tile ? tile * 2 : 0);
+            rec8[6] = a.tmc[0] / mc[0];      // torch_backend.py:452
+            rec8[7] = a.tmc[1] / mc[1];
+        }
+        const float* sm_src = own ? he_src : a.sm;
+        // (reconstruct_item's fold, kAug form)
+        double pinv[6], sm[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            pinv[i] = (double)rec8[i];
+            sm[i] = (double)sm_src[i];
+        }
+        double s0 = (double)rec8[6], s1 = (double)rec8[7];
+        double b0 = 0.0, b1 = 0.0;
+        if (a.alpha) {
+            s0 = s0 * (double)a.alpha[2 * tile];
+            s1 = s1 * (double)a.alpha[2 * tile + 1];
+            b0 = (double)a.beta[2 * tile];
+            b1 = (double)a.beta[2 * tile + 1];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double row = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double v = sm[c * 2] * s0 * pinv[j] + sm[c * 2 + 1] * s1 * pinv[3 + j];
+                const float mf = (float)v;
+                fold[c * 3 + j] = mf;
+                row += (double)mf;
+            }
+            fold[9 + c] = (float)(7.90689059560851852932 * (1.0 - row) - 1.44269504088896340736 * (sm[c * 2] * b0 + sm[c * 2 + 1] * b1));      // log2(240), log2(e)
+        }
+    }
+    tb.fill();
+    __syncthreads();
+    float m[3][3], k[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) m[c][j] = fold[c * 3 + j];
+        k[c] = fold[9 + c];
+    }
+
+    __shared__ uint4 stage[(kInter && V > 1 && sizeof(O) * V == 16) ? kStreamThreads * 3 : 1];      // 3 KB per wave: store_pixels_staged()
+    while (p < p_end) {
+        O res[3][V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float l[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) l[c] = l2_of<T>(u[c][i], tb);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float x = fmaf(m[c][2], l[2], fmaf(m[c][1], l[1], fmaf(m[c][0], l[0], k[c])));
+                res[c][i] = rgb_to_output<T, O, kUnit>(fminf(fmaxf(__builtin_amdgcn_exp2f(x), 0.0f), 255.0f));      // :459, :128
+            }
+        }
+        const int64_t q = p;
+        p += (int64_t)TPB * V;
+        if (p < p_end) load(p, u);      // (a work item of several pack sets: the next one is on its way while this one is stored)
+        if constexpr (kInter && V > 1 && sizeof(O) * V == 16) {
+            if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {      // wave-uniform: every lane has a pack (all but a tile's last sweep)
+                store_pixels_staged<O, V>(dst, q, res, stage + (threadIdx.x / kWave) * (3 * kWave));
+                continue;
+            }
+        }
+        store_pixels<O, V, kInter>(dst, a.pixels, q, res);
+    }
+}
+
+// sx_macenko_estimate: the tile's estimate out of the workspace, as sx_macenko_tile_params reports it
+__global__ void export_estimate_kernel(const GroupState* __restrict__ state, int64_t n_groups, float* __restrict__ he_out, float* __restrict__ max_c_out, float* __restrict__ tissue_out) {
+    const int64_t gidx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (gidx >= n_groups) return;
+    const GroupState& st = state[gidx];
+    for (int i = 0; i < 6; ++i) he_out[gidx * 6 + i] = st.he[i];
+    max_c_out[gidx * 2] = st.max_c[0];
+    max_c_out[gidx * 2 + 1] = st.max_c[1];
+    if (tissue_out) tissue_out[gidx] = (float)st.n_sel;
+}
+
 
 template <typename T>
 __global__ __launch_bounds__(kGroupThreads) void fast_kernel(const T* __restrict__ images, Geometry g, Workspace ws, const float* __restrict__ target_max_conc) {
@@ -3455,6 +3609,79 @@ static int separate_typed(const void* images, const Geometry& g0, const Workspac
 #undef SX_RUN_SEP
 }
 
+// sx_macenko_apply: ONE launch.  The pack is 16 bytes of output per lane and plane (run_transform's VR rule).  A work item is ONE pack
+// set per thread on the vector paths, as in run_transform's big batches: the longer prologue does not show (one thread builds the fold
+// under the latency of the first loads), and larger work items are slower -- 64 x 512 x 512 float32: 64.9 us per call with 1 set, 65.6 with 2,
+// 68.8 with 4, 73.5 with 16; 256 x 224 x 224 bfloat16: 28.8 / 29.9 / 29.6 / 35.8.  One-byte output (uint8 in, uint8 out: 16 pixels per lane
+// and set) takes 4 sets: 22.9 us with 1, 21.8 with 4, 29.3 with 16.  The scalar path: sixteen sweeps.
+template <typename O> constexpr int apply_sets() { return sizeof(O) == 1 ? 4 : 1; }
+template <typename T, typename O, int V, bool kUnit, bool kInter>
+static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipStream_t stream) {
+    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    int sets = V == 1 ? 16 : apply_sets<O>();
+#ifdef SX_STAMPS      // diagnostic builds: pack sets per work item from the environment (tools/bench_apply.py --sets: A/B of the grid)
+    if (const char* e = std::getenv("SX_APPLY_SETS")) {
+        const int s = std::atoi(e);
+        if (s >= 1 && s <= 64) sets = s;
+    }
+#endif
+    a.chunk = kStreamThreads * VR * sets;
+    a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
+    hipLaunchKernelGGL((apply_kernel<T, O, VR, kUnit, kInter>), dim3((unsigned)(n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, out, a);
+    return check_launch("macenko apply");
+}
+
+template <typename T>
+static int apply_typed(const void* images, void* out, int64_t n_tiles, const ApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream) {
+    const bool u8_half = sizeof(T) == 1 && out_code != 0;
+    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
+    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
+    constexpr int W = PackOf<T>::n;
+    // (16-byte packs where both pointers allow them, as transform_typed decides; the scalar path otherwise)
+    const bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    const T* in = static_cast<const T*>(images);
+#define SX_RUN_APPLY(O, U)                                                                                                                                     \
+    return interleaved ? (vec ? run_apply<T, O, W, U, true>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, true>(in, static_cast<O*>(out), n_tiles, a, stream)) \
+                       : (vec ? run_apply<T, O, W, U, false>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, false>(in, static_cast<O*>(out), n_tiles, a, stream));
+    if constexpr (sizeof(T) == 1) {
+        if (u8_half && out_code == SX_BF16) {
+            if (unit) { SX_RUN_APPLY(__hip_bfloat16, true) } else { SX_RUN_APPLY(__hip_bfloat16, false) }
+        }
+        if (u8_half) {
+            if (unit) { SX_RUN_APPLY(__half, true) } else { SX_RUN_APPLY(__half, false) }
+        }
+        if (u8_unit) {
+            SX_RUN_APPLY(float, true)
+        }
+        SX_RUN_APPLY(T, false)
+    } else {
+        if (unit) { SX_RUN_APPLY(T, true) } else { SX_RUN_APPLY(T, false) }
+    }
+#undef SX_RUN_APPLY
+}
+
+// sx_macenko_estimate: the transform's four-pass estimate with its geometry (transform_typed's, four-pass form), then the export.
+template <typename T>
+static int estimate_typed(const void* images, const Geometry& g0, const Workspace& ws, float* he_out, float* max_c_out, float* tissue_out, hipStream_t stream) {
+    Geometry g = g0;
+    constexpr int W = PackOf<T>::n;
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16);
+    g.vec = vec ? 1 : 0;
+    g.vec_width = W;
+    set_sampling(g, true);
+    if (!(vec && !g.interleaved && std::is_same<T, float>::value)) g.code_epoch = 0u;      // (the coded passes: planar float32 tiles in 16-byte packs)
+    set_fine_chunk(g, vec ? W : 1);
+    const T* in = static_cast<const T*>(images);
+    // (no target: the scale stage leaves maxC in the tile's state and forms no scale)
+    const int rc = g.interleaved ? (vec ? run_estimate<T, W, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream)
+                                        : run_estimate<T, 1, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream))
+                                 : (vec ? run_estimate<T, W, false>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream)
+                                        : run_estimate<T, 1, false>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream));
+    if (rc != SX_OK) return rc;
+    hipLaunchKernelGGL(export_estimate_kernel, dim3((unsigned)((g.n_tiles + 63) / 64)), dim3(64), 0, stream, ws.state, g.n_tiles, he_out, max_c_out, tissue_out);
+    return check_launch("macenko export_estimate");
+}
+
 template <typename T>
 static int fit_typed(const void* images, const Geometry& g0, const Workspace& ws, float* he_out, float* max_c_out, hipStream_t stream) {
     Geometry g = g0;
@@ -3963,6 +4190,74 @@ extern "C" int sx_macenko_separate(const void* images, void* stains_out, float* 
         case SX_BF16: return separate_typed<__hip_bfloat16>(images, g, ws, so, tmc, unit, stream);
         case SX_F32: return separate_typed<float>(images, g, ws, so, tmc, unit, stream);
         case SX_F64: return separate_typed<double>(images, g, ws, so, tmc, unit, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// The transform's per-tile estimate as a call of its own: the four passes' estimate (existing kernels), then HE_source, maxC and the
+// kept-pixel count of every tile copied out of the workspace.  No output pass.
+extern "C" int sx_macenko_estimate(const void* images, int dtype, int64_t n, int64_t h, int64_t w, float* tile_he_out, float* tile_max_c_out, float* tile_tissue_out,
+                                   unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    if (flags & ~(SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_estimate takes SX_MACENKO_CHANNELS_LAST and SX_MACENKO_CLASSIC only", flags);
+    int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!tile_he_out || !tile_max_c_out) return fail(SX_ERR_BAD_ARG, "tile_he_out / tile_max_c_out pointer is null");
+    Geometry g = make_geometry(n, h * w, 0);
+    g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
+    // (the codes of a float32 batch as in the transform's four passes)
+    size_t codes_at = 0;
+    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
+        g.code_epoch = next_code_epoch();
+        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
+    }
+    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {
+        case SX_U8: return estimate_typed<uint8_t>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
+        case SX_F16: return estimate_typed<__half>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
+        case SX_BF16: return estimate_typed<__hip_bfloat16>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
+        case SX_F32: return estimate_typed<float>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
+        case SX_F64: return estimate_typed<double>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// Normalise (and optionally jitter) with a GIVEN source basis: apply_kernel, one launch on `stream`, nothing else enqueued, no workspace.
+extern "C" int sx_macenko_apply(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c,
+                                int64_t n_sources, const float* alpha, const float* beta, const float* sm, const float* tmc, unsigned flags, void* stream_ptr) {
+    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise) or both null (own basis)");
+    if ((alpha == nullptr) != (beta == nullptr)) return fail(SX_ERR_BAD_ARG, "alpha and beta: both given or both null");
+    if (!sm && !alpha) return fail(SX_ERR_BAD_ARG, "own basis (no stain_matrix / target_max_conc) needs the factors alpha and beta: without them the call would rebuild its input");
+    if (sm && !source_max_c) return fail(SX_ERR_BAD_ARG, "source_max_c pointer is null (it may be null in own-basis mode only)");
+    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_apply takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
+    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
+        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    ApplyArgs a{};
+    a.he = source_he;
+    a.max_c = source_max_c;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.sm = sm;
+    a.tmc = tmc;
+    a.pixels = h * w;
+    a.per_tile = n_sources == n && n != 1 ? 1 : 0;
+    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {
+        case SX_U8: return apply_typed<uint8_t>(images, out, n, a, out_code, inter, unit, stream);
+        case SX_F16: return apply_typed<__half>(images, out, n, a, out_code, inter, unit, stream);
+        case SX_BF16: return apply_typed<__hip_bfloat16>(images, out, n, a, out_code, inter, unit, stream);
+        case SX_F32: return apply_typed<float>(images, out, n, a, out_code, inter, unit, stream);
+        case SX_F64: return apply_typed<double>(images, out, n, a, out_code, inter, unit, stream);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }

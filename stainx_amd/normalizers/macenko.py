@@ -23,6 +23,17 @@ class StainSeparation(NamedTuple):
     max_concentrations: torch.Tensor | None
 
 
+class StainEstimate(NamedTuple):
+    """A source stain basis, estimated once and applied elsewhere (``Macenko.estimate`` returns it, ``Macenko.apply`` takes it).
+    ``stain_matrices``: (N, 3, 2) float32 ``HE_source`` per tile, or (1, 3, 2) for one basis pooled over a batch (a slide).
+    ``max_concentrations``: (N, 2) or (1, 2) float32, the 99th-percentile concentrations ``maxC``.
+    ``tissue_pixels``: (N,) float32, the pixels of each tile the optical-density filter kept; None for a pooled estimate."""
+
+    stain_matrices: torch.Tensor
+    max_concentrations: torch.Tensor
+    tissue_pixels: torch.Tensor | None
+
+
 class Macenko(NormalizerTemplate):
     """``normalize_to_0_1`` defaults to False here (output ~[0,255]); ``StainNormalizerTransform`` defaults it to True.
     ``precision`` takes the reference's two values, ``"stable"`` and ``"fast"``: both run the same exact kernels (fp64 covariance, exact
@@ -84,3 +95,62 @@ class Macenko(NormalizerTemplate):
         images_out = out["stains"]
         return StainSeparation(images_out[0] if images_out is not None else None, images_out[1] if images_out is not None else None,
                                out["concentrations"], out["he"], out["max_c"])
+
+    def estimate(self, images: Any, *, pooled: bool = False) -> StainEstimate:
+        """The source stain basis of ``images`` (NCHW), without transforming them: every tile's own estimate (the transform's, exact
+        percentiles), or with ``pooled=True`` ONE basis over all pixels of the batch -- the pooled fit that ``fit`` runs on a
+        reference, returned with a leading axis of 1.  The slide-level workflow: estimate once (a thumbnail, a sample of tissue
+        tiles), then ``apply`` the estimate to every tile.  Needs no ``fit()``."""
+        if self._precision == "sampled":
+            raise ValueError("estimate has no approximate form: use precision='stable' or 'fast' (both run the exact kernels)")
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) != 4 or shape[1] != 3:
+            raise ValueError(f"Macenko estimate expects NCHW images with C=3, got shape {shape}")
+        engine = self._get_backend_impl()
+        if pooled:
+            he, max_c = engine.compute_reference_stain_matrix(images)
+            return StainEstimate(he.reshape(1, 3, 2), max_c.reshape(1, 2), None)
+        out = engine.estimate(images)
+        return StainEstimate(out["he"], out["max_c"], out["tissue"])
+
+    def apply(self, images: Any, source: Any, *, alpha: Any | None = None, beta: Any | None = None, own_basis: bool = False) -> Any:
+        """Normalise ``images`` (NCHW) to the fitted reference with a GIVEN source basis instead of each tile's own estimate: one
+        kernel launch, a pixel read and a pixel written (include/stainx_hip.h: sx_macenko_apply).
+
+        ``source``: a ``StainEstimate``, a ``StainSeparation`` that carries ``max_concentrations``, or a ``(stain_matrices,
+        max_concentrations)`` pair -- (3, 2) and (2,), or with a leading axis of 1 (one basis for the batch) or N (one per tile).
+        ``alpha`` / ``beta`` (N, 2) jitter the (H, E) concentrations as ``MacenkoAugment`` does.  ``own_basis=True`` keeps the
+        source's own stain vectors (no reference, no ``fit()``, ``max_concentrations`` may be None) and requires the factors.
+        The output follows ``normalize_to_0_1`` and ``output_dtype`` as ``transform`` does."""
+        if not own_basis and not self._is_fitted:
+            raise ValueError("Must call fit() before transform()")
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together: both or neither")
+        if own_basis and alpha is None:
+            raise ValueError("own_basis=True rebuilds every tile in the source's own basis: it needs the factors alpha and beta")
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) != 4 or shape[1] != 3:
+            raise ValueError(f"Macenko apply expects NCHW images with C=3, got shape {shape}")
+        if isinstance(source, (StainEstimate, StainSeparation)):
+            he, max_c = source.stain_matrices, source.max_concentrations
+        elif isinstance(source, (tuple, list)) and len(source) == 2:
+            he, max_c = source
+        else:
+            raise ValueError("source must be a StainEstimate, a StainSeparation or a (stain_matrices, max_concentrations) pair")
+        n = shape[0]
+        he_shape = tuple(getattr(he, "shape", ()))
+        if not (he_shape == (3, 2) or (len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n))):
+            raise ValueError(f"source stain_matrices must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
+        n_sources = 1 if len(he_shape) == 2 else he_shape[0]
+        if max_c is None:
+            if not own_basis:
+                raise ValueError("source carries no max_concentrations (a separation in its own basis?): they are needed to normalise to the reference")
+        else:
+            mc_shape = tuple(getattr(max_c, "shape", ()))
+            if mc_shape != (n_sources, 2) and not (len(he_shape) == 2 and mc_shape == (2,)):
+                raise ValueError(f"source max_concentrations must have shape ({n_sources}, 2) to match stain_matrices {he_shape}, got {mc_shape}")
+        for name, factor in (("alpha", alpha), ("beta", beta)):
+            if factor is not None and tuple(getattr(factor, "shape", ())) != (n, 2):
+                raise ValueError(f"{name} must have shape (N, 2) = ({n}, 2), got {tuple(getattr(factor, 'shape', ()))}")
+        reference = () if own_basis else (self._stain_matrix, self._target_max_conc)
+        return self._get_backend_impl().apply(images, he, max_c, *reference, alpha=alpha, beta=beta, **self.call_options())
