@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The hot path in five lines each: the three normalisers, the nn.Module, uint8 HWC tiles as a decoder hands them over,
 the sampled `precision="fast"` mode, how a batch is split over GPUs (one process per GPU, no collective for
-`transform`), and the slide-level use: one source estimate, applied to batch after batch.  Run on a ROCm GPU:  python examples/normalize_tiles.py
+`transform`), the slide-level use: one source estimate, applied to batch after batch, and per-tile statistics for Reinhard and
+histogram matching on a batch of tiles from different slides.  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -69,6 +70,22 @@ def main() -> None:
     per_tile = norm.estimate(tiles)                                  # every tile's own estimate fed back: the transform, bit for bit
     assert torch.equal(norm.apply(tiles, per_tile), norm.transform(tiles))
     print(f"[rank {rank}] slide-level apply   {tuple(out.shape)} + {tuple(out_more.shape)} {out.dtype}  maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")
+
+    # 7. a batch of tiles from DIFFERENT slides (a DataLoader batch): Reinhard and histogram matching with every tile's own statistics --
+    #    still two / three launches for the batch, and a tile's result does not depend on what else is in the batch
+    mixed = torch.cat([tiles[:4], synth.noise_u8((4, 3, 256, 256), 7).to(dev)])
+    for cls in (Reinhard, HistogramMatching):
+        per_tile_norm = cls(device=dev, statistics="tile").fit(reference.to(dev))
+        out = per_tile_norm.transform(mixed)
+        assert torch.equal(per_tile_norm.transform(mixed.flip(0).contiguous()).flip(0), out)      # the same tiles among other neighbours: the same bits
+        print(f"[rank {rank}] {cls.__name__ + ' per tile':27s} {tuple(out.shape)} {out.dtype}  mean {out.float().mean().item():.2f}")
+    #    ... and a slide normalised with ONE set of LAB statistics, estimated once: one launch per batch afterwards
+    reinhard = Reinhard(device=dev).fit(reference.to(dev))
+    slide_stats = reinhard.estimate(tiles, pooled=True)              # ColorStatistics: (1, 3) mean, (1, 3) std
+    out = reinhard.apply(tiles, slide_stats)
+    out_more = reinhard.apply(more, slide_stats)
+    assert torch.equal(out, reinhard.transform(tiles))               # the pooled transform of that batch, bit for bit
+    print(f"[rank {rank}] Reinhard slide-level    {tuple(out.shape)} + {tuple(out_more.shape)}  LAB mean = {[round(v, 2) for v in slide_stats.mean[0].tolist()]}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -328,6 +328,40 @@ int sx_reinhard_apply(const void* images_dev, void* out_dev, int dtype, int64_t 
                       int64_t width, const double* sums_dev, double n_total_pixels, const float* ref_mean_dev,
                       const float* ref_std_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Per-tile source statistics (an extension: the reference pools over the batch; torchstain, tiatoolbox and HistomicsTK normalise ONE
+ * image with its own statistics).  A batch of tiles from different slides is normalised tile by tile in two streaming launches, and a
+ * tile's output does not depend on its neighbours in the batch.
+ *
+ * sx_reinhard_tile_stats: LAB mean and unbiased standard deviation of EVERY tile in one statistics pass (the tile's last arrival
+ *   finishes the tile, in a fixed order).  tile_mean_out_dev, tile_std_out_dev: N x 3 floats each.  A tile of one pixel has std NaN.
+ * sx_reinhard_transform_tiles: that pass, then the apply pass with every tile's OWN statistics.  tile_mean_out_dev / tile_std_out_dev
+ *   receive them (both or neither; exactly one NULL is SX_ERR_BAD_ARG).  Two streaming launches and the clearing launch of the plain
+ *   pooled call: any workspace contents are accepted, and a workspace that was READY is left ready, so the call may alternate with
+ *   sx_reinhard_transform_ready on one workspace.
+ * Both need sx_reinhard_tiles_workspace_bytes() bytes (at least the pooled size; for float32 with room for the 8-bit codes -- a call
+ * on a workspace without that room runs without them, same bits).
+ *
+ * sx_reinhard_apply_stats: normalise with GIVEN source statistics -- ONE kernel launch on `stream`, nothing else enqueued, no
+ *   workspace: a pixel is read, a pixel is written.
+ *   source_mean_dev, source_std_dev   n_sources x 3 floats each (LAB on the reference's 0..255 scale, as sx_reinhard_fit writes them)
+ *   n_sources                         1 (a slide's statistics for the whole batch) or n_tiles (row t serves tile t); anything else is
+ *                                     SX_ERR_BAD_ARG
+ *   The statistics and the reference are DEVICE memory read by the kernel (a captured graph replayed after new values were written
+ *   into the same buffers uses the new values).  The arithmetic per pixel is the pooled apply pass's, a function of the float32
+ *   statistics: sx_reinhard_fit's outputs with n_sources = 1 give the bits of sx_reinhard_transform, sx_reinhard_tile_stats' outputs
+ *   with n_sources = n_tiles those of sx_reinhard_transform_tiles. */
+size_t sx_reinhard_tiles_workspace_bytes(int dtype, int64_t n_tiles, int64_t height, int64_t width);
+int sx_reinhard_tile_stats(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                           float* tile_mean_out_dev, float* tile_std_out_dev, void* workspace_dev, size_t workspace_bytes,
+                           void* stream);
+int sx_reinhard_transform_tiles(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                                int64_t width, const float* ref_mean_dev, const float* ref_std_dev,
+                                float* tile_mean_out_dev, float* tile_std_out_dev, void* workspace_dev,
+                                size_t workspace_bytes, void* stream);
+int sx_reinhard_apply_stats(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                            int64_t width, const float* source_mean_dev, const float* source_std_dev, int64_t n_sources,
+                            const float* ref_mean_dev, const float* ref_std_dev, void* stream);
+
 /* ---------------------------------------------------------------- Histogram matching -------------
  * Replaces stainx_cuda_torch.histogram_matching (bindings.cpp:31) with the numerics of
  * HistogramMatchingTorch (torch_backend.py:134-301).  `channels_last` != 0: images are (N,H,W,3).
@@ -376,6 +410,19 @@ int sx_hm_counts(const void* images_dev, int dtype, int64_t n_tiles, int64_t hei
 int sx_hm_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                 int channels_last, const unsigned long long* counts_dev, double n_total_pixels,
                 const float* ref_hist_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* One histogram and one LUT per TILE against the one reference (an extension: the reference pools the source histogram over the
+ * batch; scikit-image's match_histograms, tiatoolbox and HistomicsTK match ONE image).  Three launches and one clear whatever
+ * n_tiles is: histogram pass into a 3 x 256 set of integer counters per tile, 3 x n_tiles LUT workgroups (the pooled LUT arithmetic,
+ * with the tile's pixels), apply pass with the tile's own LUT.  Tile t's output is bit for bit sx_hm_transform of tile t alone.
+ *   tile_counts_out_dev  n_tiles x 3 x 256 uint32, the histograms as counted; may be NULL
+ *   tile_lut_out_dev     n_tiles x 3 x 256 floats, the float LUTs; may be NULL
+ * The workspace needs sx_hm_tiles_workspace_bytes() bytes (the pooled Tables first: the status word lies where
+ * sx_hm_workspace_status_offset() says).  Any workspace contents are accepted; the call leaves the workspace READY. */
+size_t sx_hm_tiles_workspace_bytes(int64_t n_tiles, int64_t height, int64_t width);
+int sx_hm_transform_tiles(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                          int channels_last, const float* ref_hist_dev, uint32_t* tile_counts_out_dev,
+                          float* tile_lut_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,12 @@ SIGNATURES = {
     "sx_reinhard_workspace_init": (_int, [_vp, _sz, _vp]),
     "sx_reinhard_workspace_status_offset": (_sz, []),
     "sx_reinhard_transform_ready": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "sx_reinhard_tiles_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
+    "sx_reinhard_tile_stats": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "sx_reinhard_transform_tiles": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sx_reinhard_apply_stats": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "sx_hm_tiles_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "sx_hm_transform_tiles": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_hm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "sx_hm_fit": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
     "sx_hm_transform": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),

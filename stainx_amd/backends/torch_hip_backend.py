@@ -719,6 +719,82 @@ class ReinhardHIP(TorchHIPBackendBase):
         _native.check(rc, "sx_reinhard_transform_ready")
         return out
 
+    # ---- per-tile statistics, given statistics (include/stainx_hip.h: sx_reinhard_tile_stats ...) ---------
+    def _tiles_workspace(self, n: int, h: int, w: int, code: int) -> torch.Tensor:
+        # a workspace of its own: the pooled transform's "last shape" bookkeeping (see _workspace) is not touched by the per-tile calls
+        scratch = self.__dict__.get("_tile_scratch")
+        if scratch is None:
+            scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
+        return scratch.get(int(self._lib.sx_reinhard_tiles_workspace_bytes(code, n, h, w)), self.device)
+
+    def tile_statistics(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """LAB mean and unbiased standard deviation of every tile: two (N, 3) float32 tensors, one statistics pass."""
+        images = images.to(self.device)
+        self._check(images)
+        images = images.contiguous()
+        n, _, h, w = images.shape
+        mean = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        std = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        if images.numel() == 0:
+            return mean, std
+        with _native.on_device(self.device):
+            ws = self._tiles_workspace(n, h, w, _dtype_code(images))
+            rc = self._lib.sx_reinhard_tile_stats(images.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_reinhard_tile_stats")
+        return mean, std
+
+    def transform_tiles(self, images: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor, *, return_statistics: bool = False):
+        """Every tile normalised with its OWN statistics (two streaming launches for the batch).  With ``return_statistics`` also the
+        tiles' (N, 3) mean and standard deviation."""
+        images = images.to(self.device)
+        self._check(images)
+        images = images.contiguous()
+        mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
+        if mean.numel() != 3 or std.numel() != 3:
+            raise ValueError("reference_mean / reference_std must have 3 elements")
+        n, _, h, w = images.shape
+        out = torch.empty_like(images)
+        tile_mean = tile_std = None
+        if return_statistics:
+            tile_mean = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            tile_std = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        if images.numel() != 0:
+            with _native.on_device(self.device):
+                ws = self._tiles_workspace(n, h, w, _dtype_code(images))
+                rc = self._lib.sx_reinhard_transform_tiles(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
+                                                           None if tile_mean is None else tile_mean.data_ptr(), None if tile_std is None else tile_std.data_ptr(),
+                                                           ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_reinhard_transform_tiles")
+        return (out, tile_mean, tile_std) if return_statistics else out
+
+    def apply_statistics(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor) -> torch.Tensor:
+        """Normalise with GIVEN source statistics, (1, 3) for the whole batch or (N, 3) per tile: one launch, no workspace."""
+        images = images.to(self.device)
+        self._check(images)
+        n, _, h, w = images.shape
+        if source_mean.dim() == 1:
+            source_mean = source_mean.unsqueeze(0)
+        if source_std.dim() == 1:
+            source_std = source_std.unsqueeze(0)
+        for name, t in (("source_mean", source_mean), ("source_std", source_std)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
+                raise ValueError(f"{name} must be (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
+        if source_mean.shape[0] != source_std.shape[0]:
+            raise ValueError(f"source_mean and source_std must have the same number of rows, got {source_mean.shape[0]} and {source_std.shape[0]}")
+        images = images.contiguous()
+        mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
+        if mean.numel() != 3 or std.numel() != 3:
+            raise ValueError("reference_mean / reference_std must have 3 elements")
+        src_mean, src_std = self._f32(source_mean), self._f32(source_std)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        with _native.on_device(self.device):
+            rc = self._lib.sx_reinhard_apply_stats(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, src_mean.data_ptr(), src_std.data_ptr(),
+                                                   int(src_mean.shape[0]), mean.data_ptr(), std.data_ptr(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_reinhard_apply_stats")
+        return out
 
     # ---- batch statistics pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_sums(self, images: torch.Tensor) -> torch.Tensor:
@@ -854,6 +930,36 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         self._check_ready_call(rc, "sx_hm_transform_ready")
         self.last_workspace = ws
         return out
+
+    # ---- one histogram and one LUT per tile (include/stainx_hip.h: sx_hm_transform_tiles) ------------------
+    def transform_tiles(self, images: torch.Tensor, reference_histogram) -> torch.Tensor:
+        """Every tile matched to the reference with its OWN histogram: three launches for the batch, tile t's bits those of
+        ``transform(images[t:t+1])``."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        ref = self._stack_reference(reference_histogram, 3)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        with _native.on_device(self.device):
+            # a workspace of its own (the call clears what it needs): the zeroed scratch of the pooled calls is not touched
+            scratch = self.__dict__.get("_tile_scratch")
+            if scratch is None:
+                scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
+            ws = scratch.get(int(self._lib.sx_hm_tiles_workspace_bytes(n, h, w)), self.device)
+            rc = self._lib.sx_hm_transform_tiles(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), ref.data_ptr(), None, None,
+                                                 ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_transform_tiles")
+        self._last_tiles = (ws, int(n), int(self._lib.sx_hm_workspace_bytes(n, h, w)))
+        return out
+
+    def tile_tables(self) -> dict[str, torch.Tensor]:
+        """Integer source histograms (N,3,256) and float LUTs (N,3,256) of the last per-tile transform."""
+        ws, n, base = self._last_tiles
+        words = n * 3 * 256
+        counts = ws[base + 4 * words: base + 8 * words].view(torch.int32).reshape(n, 3, 256).cpu().long()
+        lut = ws[base + 8 * words: base + 12 * words].view(torch.float32).reshape(n, 3, 256).cpu()
+        return {"counts": counts, "lut": lut}
 
     # ---- source histogram pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_counts(self, images: torch.Tensor) -> torch.Tensor:

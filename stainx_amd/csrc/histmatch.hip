@@ -116,13 +116,20 @@ __global__ __launch_bounds__(kThreads) void histogram_kernel(const T* __restrict
 constexpr int kLastCopies = 16;
 constexpr int kLastChunk = 65536;       // elements (bytes for uint8) per workgroup; a multiple of 3 * V is not needed: the channel follows e % 3
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void histogram_last_kernel(const T* __restrict__ images, int64_t total, uint32_t* __restrict__ counts) {
+// kPerTile: `total` is the elements of ONE tile (a multiple of V: a pack never straddles two tiles, and a tile starts on channel 0),
+// workgroup b takes chunk b % chunks_per_tile of tile b / chunks_per_tile and adds into that tile's set of `counts` ([n][3][256]).
+template <typename T, bool kPerTile = false>
+__global__ __launch_bounds__(kThreads) void histogram_last_kernel(const T* __restrict__ images, int64_t total, uint32_t* __restrict__ counts, int chunks_per_tile = 1) {
     __shared__ uint32_t hist[3][kBins][kLastCopies];
     for (int i = threadIdx.x; i < 3 * kBins * kLastCopies; i += kThreads) (&hist[0][0][0])[i] = 0;
     __syncthreads();
     constexpr int V = VecOf<T>::n;
-    const int64_t begin = (int64_t)blockIdx.x * kLastChunk, end = min(begin + (int64_t)kLastChunk, total);
+    const int64_t tile = kPerTile ? blockIdx.x / chunks_per_tile : 0;
+    if constexpr (kPerTile) {
+        images += tile * total;
+        counts += tile * 3 * kBins;
+    }
+    const int64_t begin = (int64_t)(kPerTile ? blockIdx.x % chunks_per_tile : blockIdx.x) * kLastChunk, end = min(begin + (int64_t)kLastChunk, total);
     const int copy = threadIdx.x & (kLastCopies - 1);
     for (int64_t e = begin + (int64_t)threadIdx.x * V; e < end; e += (int64_t)kThreads * V) {
         const Pack<T, V> pk = *reinterpret_cast<const Pack<T, V>*>(images + e);
@@ -220,17 +227,21 @@ __device__ __forceinline__ float lut_value(float s, const float* ref_cdf) {
     if (s >= ref_cdf[kBins - 1]) v = 255.0f;                                          // :269, :280
     return fminf(fmaxf(v, 0.0f), 255.0f);                                             // :281
 }
+// (the LUT value in the output element: what the apply pass stores)
+template <typename T>
+__device__ __forceinline__ T typed_value(float v) {
+    if constexpr (sizeof(T) == 1) {
+        return (uint8_t)v;                                                            // stays 0..255, truncated
+    } else {
+        const float unit = fminf(fmaxf(v / 255.0f, 0.0f), 1.0f);                      // :291, :296
+        if constexpr (sizeof(T) == 8) return (double)unit; else return Elem<T>::store(unit);
+    }
+}
 template <typename T>
 __device__ __forceinline__ void lut_entry(Tables* __restrict__ tab, int c, int t, float s, const float* ref_cdf) {
     const float v = lut_value(s, ref_cdf);
     tab->lut[c][t] = v;
-    if constexpr (sizeof(T) == 1) {
-        tab->typed_lut[c][t] = pack_elem<uint8_t>((uint8_t)v);                        // stays 0..255, truncated
-    } else {
-        const float unit = fminf(fmaxf(v / 255.0f, 0.0f), 1.0f);                      // :291, :296
-        if constexpr (sizeof(T) == 8) tab->typed_lut[c][t] = pack_elem<double>((double)unit);
-        else tab->typed_lut[c][t] = pack_elem<T>(Elem<T>::store(unit));
-    }
+    tab->typed_lut[c][t] = pack_elem<T>(typed_value<T>(v));
 }
 
 // running sum in double rounded per entry (:236): the order is torch.cumsum's, so one thread per table walks it -- sixteen
@@ -259,9 +270,30 @@ __device__ __forceinline__ void running_sum(const float* term, float* cdf) {
 // arrive last does the rest -- to save this launch and its boundary.  Same bits, and slower: 121 against 114 us per call.  Every one of
 // the 3072 workgroups then waits for its counter adds to be acknowledged and for a ticket from ONE address before it may leave its
 // CU: the histogram launch went from 36 to 57 us, more than this kernel's 8.8 us and the boundary together.)
-template <typename T>
-__global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, const unsigned long long* __restrict__ counts, const bool local, const float* __restrict__ ref_hist, double num_pixels) {
-    const int c = blockIdx.x, t = threadIdx.x;
+// Per-tile form (sx_hm_transform_tiles): behind the Tables, one 3 x 256 set per tile of live counters, of the histogram as counted, of the
+// float LUT and of the LUT in the output element (eight bytes reserved per entry, elements of T stored densely).  The live counters
+// come first: one clear covers the pooled ones and them.
+struct TileAreas {
+    uint32_t* counts;       // [n][3][256] live, consumed by the LUT launch
+    uint32_t* counted;      // [n][3][256]
+    float* lut;             // [n][3][256]
+    void* typed;            // [n][3][256] of the output element
+    uint32_t* counts_out;   // the caller's copies (may be null)
+    float* lut_out;
+};
+static size_t tile_area_bytes(int64_t n) { return (size_t)n * 3 * kBins * (3 * sizeof(uint32_t) + sizeof(uint64_t)); }
+static TileAreas tile_areas(void* ws, int64_t n, uint32_t* counts_out, float* lut_out) {
+    char* base = static_cast<char*>(ws) + sizeof(Tables);
+    const size_t words = (size_t)n * 3 * kBins;
+    return TileAreas{reinterpret_cast<uint32_t*>(base), reinterpret_cast<uint32_t*>(base + 4 * words), reinterpret_cast<float*>(base + 8 * words), base + 12 * words, counts_out, lut_out};
+}
+
+// kPerTile: workgroup b serves channel b % 3 of tile b / 3 -- 3N independent chains, the reference's (which does not depend on the tile)
+// beside each -- with the tile's own counters and tables; num_pixels is the pixels of ONE tile.
+template <typename T, bool kPerTile = false>
+__global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, const unsigned long long* __restrict__ counts, const bool local, const float* __restrict__ ref_hist, double num_pixels, TileAreas tiles = TileAreas{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
+    const int c = kPerTile ? blockIdx.x % 3 : blockIdx.x, t = threadIdx.x;
+    const size_t tile_entry = kPerTile ? ((size_t)blockIdx.x * kBins + t) : 0;      // (tile * 3 + c) * 256 + t
     __shared__ float src_cdf[kBins], ref_cdf[kBins];
     __shared__ float src_term[kBins], ref_term[kBins];
     __shared__ float ref_denom_s;
@@ -277,9 +309,17 @@ __global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, co
     // (the local histogram is read as it was counted; counts pooled over ranks arrive widened to 64 bits)
     unsigned long long count;
     if (local) {
-        const uint32_t mine = tab->counts[c][t];
-        tab->counts[c][t] = 0;      // consumed: the next call's histogram pass starts from zero
-        tab->counted[c][t] = mine;
+        uint32_t mine;
+        if constexpr (kPerTile) {
+            mine = tiles.counts[tile_entry];
+            tiles.counts[tile_entry] = 0;
+            tiles.counted[tile_entry] = mine;
+            if (tiles.counts_out) tiles.counts_out[tile_entry] = mine;
+        } else {
+            mine = tab->counts[c][t];
+            tab->counts[c][t] = 0;      // consumed: the next call's histogram pass starts from zero
+            tab->counted[c][t] = mine;
+        }
         count = mine;
         // the counters of a call add up to its pixels -- unless the workspace was not ready (see Tables)
         const double wave_total = wave_sum((double)mine);      // (integers below 2^53: exact)
@@ -301,7 +341,14 @@ __global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, co
     if (t == 0) running_sum(src_term, src_cdf);
     else if (t == 64) running_sum(ref_term, ref_cdf);
     __syncthreads();
-    lut_entry<T>(tab, c, t, src_cdf[t], ref_cdf);
+    if constexpr (kPerTile) {
+        const float v = lut_value(src_cdf[t], ref_cdf);
+        tiles.lut[tile_entry] = v;
+        if (tiles.lut_out) tiles.lut_out[tile_entry] = v;
+        static_cast<T*>(tiles.typed)[tile_entry] = typed_value<T>(v);
+    } else {
+        lut_entry<T>(tab, c, t, src_cdf[t], ref_cdf);
+    }
 }
 
 // Planar layout, 16-byte packs: a workgroup takes one chunk of ONE channel plane, so a single 256-bin histogram is live
@@ -318,7 +365,8 @@ constexpr int kPlaneChunk = 65536;      // elements of one plane per workgroup
 constexpr int kPlaneThreads = 512;
 constexpr int kAhead = 2;               // packs loaded before the first of them is counted
 
-template <typename T>
+// kPerTile: `counts` is [n][3][256] and plane p adds into the set of its tile p / 3.
+template <typename T, bool kPerTile = false>
 __global__ __launch_bounds__(kPlaneThreads) void histogram_planar_kernel(const T* __restrict__ images, Layout lay, int chunks_per_plane, uint32_t* __restrict__ counts) {
     __shared__ uint32_t hist[kBins][kCopies];
     for (int i = threadIdx.x; i < kBins * kCopies; i += kPlaneThreads) (&hist[0][0])[i] = 0;
@@ -349,7 +397,7 @@ __global__ __launch_bounds__(kPlaneThreads) void histogram_planar_kernel(const T
         uint32_t sum = 0;
 #pragma unroll
         for (int k = 0; k < kCopies; ++k) sum += hist[t][(t + k) & (kCopies - 1)];
-        if (sum) atomicAdd(&counts[channel * kBins + t], sum);
+        if (sum) atomicAdd(&counts[(kPerTile ? (plane / 3) * 3 * kBins : 0) + channel * kBins + t], sum);
     }
 }
 
@@ -382,6 +430,60 @@ __global__ __launch_bounds__(kThreads) void apply_kernel(const T* __restrict__ i
             store_pack_stream<T, V>(out + e, res.v);      // non-temporal: written once, not read again by this library
         } else {
             out[e] = lut[lay.channel_of(e)][grey_level<T>(images[e])];
+        }
+    }
+}
+
+// ---- per-tile form: the fallback histogram (single elements: odd sizes, unaligned views) and the apply pass ----------------------------
+// workgroup b counts share b % blocks_per_tile of tile b / blocks_per_tile, one LDS sub-histogram per wave as histogram_kernel()
+template <typename T>
+__global__ __launch_bounds__(kThreads) void histogram_tile_kernel(const T* __restrict__ images, Layout lay, int blocks_per_tile, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t hist[kWaves][3][kBins];
+    for (int i = threadIdx.x; i < kWaves * 3 * kBins; i += kThreads) (&hist[0][0][0])[i] = 0;
+    __syncthreads();
+    uint32_t(*mine)[kBins] = hist[threadIdx.x / kWave];
+    const int64_t tile = blockIdx.x / blocks_per_tile, per_tile = 3 * lay.pixels;
+    const T* src = images + tile * per_tile;
+    for (int64_t e = (int64_t)(blockIdx.x % blocks_per_tile) * kThreads + threadIdx.x; e < per_tile; e += (int64_t)blocks_per_tile * kThreads)
+        atomicAdd(&mine[lay.channel_of(e)][grey_level<T>(src[e])], 1u);      // (e inside the tile: a tile starts on channel 0 in both layouts)
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) s += (&hist[w][0][0])[i];
+        if (s) atomicAdd(&counts[tile * 3 * kBins + i], s);
+    }
+}
+
+// A workgroup applies ONE tile's LUT (from the tile's typed table into LDS) to one chunk of that tile.  Back to front like apply_kernel():
+// workgroup 0 takes the last chunk of the last tile, and a chunk is walked from its end.
+constexpr int kTilePacks = 16;      // packs (or single elements) per thread and chunk
+template <typename T, bool kVec>
+__global__ __launch_bounds__(kThreads) void apply_tiles_kernel(const T* __restrict__ images, T* __restrict__ out, Layout lay, int chunks_per_tile, const T* __restrict__ typed) {
+    constexpr int V = kVec ? VecOf<T>::n : 1;
+    constexpr int64_t kChunk = (int64_t)kThreads * V * kTilePacks;
+    const int64_t work = (int64_t)gridDim.x - 1 - blockIdx.x;
+    const int64_t tile = work / chunks_per_tile, chunk = work % chunks_per_tile, per_tile = 3 * lay.pixels;
+    __shared__ T lut[3][kBins];
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) (&lut[0][0])[i] = typed[tile * 3 * kBins + i];
+    __syncthreads();
+    const T* src = images + tile * per_tile;
+    T* dst = out + tile * per_tile;
+    const int64_t begin = chunk * kChunk, end = min(begin + kChunk, per_tile);      // (vector path: per_tile % V == 0, so is end - begin)
+    for (int64_t e0 = (int64_t)threadIdx.x * V; e0 < end - begin; e0 += (int64_t)kThreads * V) {
+        const int64_t e = end - V - e0;
+        if constexpr (kVec) {
+            const Pack<T, V> pk = *reinterpret_cast<const Pack<T, V>*>(src + e);
+            Pack<T, V> res;
+            int c = lay.channel_of(e);
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                res.v[i] = lut[c][grey_level<T>(pk.v[i])];
+                if (lay.channels_last) c = c == 2 ? 0 : c + 1;
+            }
+            store_pack_stream<T, V>(dst + e, res.v);
+        } else {
+            dst[e] = lut[lay.channel_of(e)][grey_level<T>(src[e])];
         }
     }
 }
@@ -476,6 +578,39 @@ static int run(const void* images, void* out, int64_t n, int64_t h, int64_t w, i
     return check_launch("histogram transform");
 }
 
+// One histogram and one LUT per tile: clear, histogram pass, 3N LUT workgroups, apply pass
+template <typename T>
+static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, uint32_t* counts_out, float* lut_out, void* ws, hipStream_t stream) {
+    Layout lay{n, h * w, channels_last};
+    Tables* tab = static_cast<Tables*>(ws);
+    const TileAreas areas = tile_areas(ws, n, counts_out, lut_out);
+    const T* in = static_cast<const T*>(images);
+    constexpr int V = VecOf<T>::n;
+    const int64_t per_tile = 3 * lay.pixels;
+    // vector path: 16-byte aligned bases, and a pack crosses neither a channel plane nor a tile
+    const bool vec = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (channels_last ? (per_tile % V == 0) : (lay.pixels % V == 0));
+    // (the pooled live counters and the status word with the tiles' counters: any contents in, a READY workspace out)
+    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + sizeof(uint32_t) * (size_t)n * 3 * kBins, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    if (vec && !channels_last) {
+        const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
+        hipLaunchKernelGGL((histogram_planar_kernel<T, true>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, areas.counts);
+    } else if (vec) {
+        const int chunks_per_tile = (int)((per_tile + kLastChunk - 1) / kLastChunk);
+        hipLaunchKernelGGL((histogram_last_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, per_tile, areas.counts, chunks_per_tile);
+    } else {
+        const int blocks_per_tile = (int)std::min<int64_t>((per_tile + kThreads * 4 - 1) / (kThreads * 4), 64);
+        hipLaunchKernelGGL((histogram_tile_kernel<T>), dim3((unsigned)(n * blocks_per_tile)), dim3(kThreads), 0, stream, in, lay, blocks_per_tile, areas.counts);
+    }
+    hipLaunchKernelGGL((lut_kernel<T, true>), dim3((unsigned)(3 * n)), dim3(kBins), 0, stream, tab, nullptr, true, ref_hist, (double)lay.pixels, areas);
+    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kTilePacks;
+    const int chunks_per_tile = (int)((per_tile + chunk - 1) / chunk);
+    if (vec)
+        hipLaunchKernelGGL((apply_tiles_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, static_cast<T*>(out), lay, chunks_per_tile, static_cast<const T*>(areas.typed));
+    else
+        hipLaunchKernelGGL((apply_tiles_kernel<T, false>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, static_cast<T*>(out), lay, chunks_per_tile, static_cast<const T*>(areas.typed));
+    return check_launch("histogram transform (per tile)");
+}
+
 static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, unsigned long long* counts_out, const unsigned long long* counts_in, double n_total, void* ws, size_t ws_bytes, void* stream_ptr, bool ready = false) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
@@ -553,4 +688,29 @@ extern "C" int sx_hm_apply(const void* images, void* out, int dtype, int64_t n, 
     if (!out || !counts || !ref_hist) return fail(SX_ERR_BAD_ARG, "out / counts / ref_hist pointer is null");
     if (!(n_total_pixels >= 1.0)) return fail(SX_ERR_BAD_ARG, "n_total_pixels must be >= 1");
     return histmatch::dispatch(images, out, dtype, n, h, w, channels_last, ref_hist, nullptr, nullptr, counts, n_total_pixels, ws, ws_bytes, stream);
+}
+
+// One histogram and one LUT per TILE against the one reference (scikit-image's match_histograms, tiatoolbox and HistomicsTK work on ONE
+// image): the pooled kernels with a set of counters and tables per tile behind the pooled Tables.
+extern "C" size_t sx_hm_tiles_workspace_bytes(int64_t n, int64_t h, int64_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
+}
+
+extern "C" int sx_hm_transform_tiles(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, uint32_t* tile_counts_out, float* tile_lut_out, void* ws, size_t ws_bytes, void* stream_ptr) {
+    if (!images || !out || !ref_hist) return fail(SX_ERR_BAD_ARG, "images / out / ref_hist pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
+    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    const size_t need = histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {
+        case SX_U8: return histmatch::run_tiles<uint8_t>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
+        case SX_F16: return histmatch::run_tiles<__half>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
+        case SX_BF16: return histmatch::run_tiles<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
+        case SX_F32: return histmatch::run_tiles<float>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
+        default: return histmatch::run_tiles<double>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
+    }
 }

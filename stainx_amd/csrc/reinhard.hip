@@ -258,7 +258,9 @@ struct Geometry {
     int blocks_per_tile, chunk;
 };
 
-template <typename T, int V>
+// kPerTile: every tile is finished by ITS last arrival -- the same fixed-order reduction over the tile's own partial sums -- and its mean
+// and standard deviation go to row `tile` of mean_out / std_out (N x 3 each, required); the State is not touched.
+template <typename T, int V, bool kPerTile = false>
 __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restrict__ images, Geometry g, State* __restrict__ st, double* __restrict__ partial, unsigned int* __restrict__ tile_arrivals, float* __restrict__ mean_out, float* __restrict__ std_out, double* __restrict__ sums_out, unsigned int call, Codes codes = Codes{nullptr, nullptr, 0u}) {
     const int64_t tile = blockIdx.x / g.blocks_per_tile;
     const int chunk_id = blockIdx.x % g.blocks_per_tile;
@@ -328,19 +330,21 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
         if (__hip_atomic_fetch_add(mine, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)g.blocks_per_tile - 1) {
             __hip_atomic_store(mine, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next call on this workspace
             // (one tile: its last arrival is the call's -- a fit on a reference tile is launch-bound, every dependent round trip shows)
-            last = g.n_tiles == 1 || __hip_atomic_fetch_add(&st->arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)g.n_tiles - 1;
+            if constexpr (kPerTile) last = true;
+            else last = g.n_tiles == 1 || __hip_atomic_fetch_add(&st->arrivals, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)g.n_tiles - 1;
         }
     }
     __syncthreads();
     if (!last) return;
-    // last workgroup: every thread sums the partials of the workgroups b = t, t+256, ... (in that order), then a fixed
-    // reduction tree joins the threads -- deterministic for a given grid, and the loads run in parallel instead of
+    // last workgroup (of the call, or of its tile): every thread sums the partials of the workgroups b = t, t+256, ... (in that order), then a
+    // fixed reduction tree joins the threads -- deterministic for a given grid, and the loads run in parallel instead of
     // one dependent chain over all workgroups
+    const unsigned b_first = kPerTile ? (unsigned)(tile * g.blocks_per_tile) : 0u, b_end = kPerTile ? b_first + (unsigned)g.blocks_per_tile : gridDim.x;
     {
         double mine[kSums];
 #pragma unroll
         for (int k = 0; k < kSums; ++k) mine[k] = 0.0;
-        for (unsigned b = threadIdx.x; b < gridDim.x; b += kStreamThreads) {
+        for (unsigned b = b_first + threadIdx.x; b < b_end; b += kStreamThreads) {
 #pragma unroll
             for (int k = 0; k < kSums; ++k) mine[k] += __hip_atomic_load(&partial[(int64_t)b * kSums + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -363,38 +367,49 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
     __syncthreads();
     if (threadIdx.x < 3) {
         const int c = threadIdx.x;
-        const double n = (double)g.n_tiles * (double)g.pixels;
+        const double n = kPerTile ? (double)g.pixels : (double)g.n_tiles * (double)g.pixels;
         const double m = red[0][c] / n;
         const double var = n > 1.0 ? (red[0][3 + c] - red[0][c] * m) / (n - 1.0) : __longlong_as_double(0x7ff8000000000000ll);   // torch.std of one value is nan
-        const float mean = (float)((double)lab_scale(c) * m + (double)lab_offset(c)), sd = (float)((double)lab_scale(c) * sqrt(fmax(var, 0.0)));
-        st->mean[c] = mean;
-        st->stdv[c] = sd;
-        if (mean_out) {
-            mean_out[c] = mean;
-            std_out[c] = sd;
+        const float mean = (float)((double)lab_scale(c) * m + (double)lab_offset(c)), sd = (float)((double)lab_scale(c) * sqrt(kPerTile && !(n > 1.0) ? var : fmax(var, 0.0)));      // (per tile: the nan of a one-pixel tile is kept)
+        if constexpr (kPerTile) {
+            mean_out[tile * 3 + c] = mean;
+            std_out[tile * 3 + c] = sd;
+        } else {
+            st->mean[c] = mean;
+            st->stdv[c] = sd;
+            if (mean_out) {
+                mean_out[c] = mean;
+                std_out[c] = sd;
+            }
         }
     }
-    if (threadIdx.x == 0) {
-        st->arrivals = 0;   // ready for the next call on this workspace
-        st->stats_of_call = call;
+    if constexpr (!kPerTile) {
+        if (threadIdx.x == 0) {
+            st->arrivals = 0;   // ready for the next call on this workspace
+            st->stats_of_call = call;
+        }
     }
 }
 
-template <typename T, int V>
-__global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, State* __restrict__ st, const float* __restrict__ ref_mean, const float* __restrict__ ref_std, unsigned int call, Codes codes = Codes{nullptr, nullptr, 0u}) {
+// One work item of the apply pass: the chunk blockIdx.x names, normalised with the float32 source statistics src_mean / src_std (three
+// floats each).  The pooled pass reads them from the State, the per-tile and given-statistics passes from the tile's row: one body, so
+// equal statistics give equal bits whichever entry point they came through.
+// (`before_statistics` runs where the pooled pass checks its workspace: behind the index arithmetic, in front of the first read of the statistics)
+template <typename T, int V, class Prologue>
+__device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g, const float* src_mean, const float* src_std, const float* ref_mean, const float* ref_std, Codes codes, Prologue before_statistics) {
     const int64_t tile = blockIdx.x / g.blocks_per_tile;
     const int chunk_id = blockIdx.x % g.blocks_per_tile;
     const int64_t p_begin = (int64_t)chunk_id * g.chunk, p_end = min(p_begin + g.chunk, g.pixels);
     const T* img = images + tile * 3 * g.pixels;
     T* dst = out + tile * 3 * g.pixels;
-    if (call != 0 && blockIdx.x == 0 && threadIdx.x == 0 && st->stats_of_call != call) atomicOr(&st->status, 1u);      // (see State)
+    before_statistics();
     // lab' = (lab - mu) / (sd + 1e-8) * rs + rm per channel (:349) with lab = S e + O, then fy = (L' / 2.55 + 16) / 116,
     // fx = (a' - 128) / 500 + fy, fz = fy - (b' - 128) / 200:   f' = k e + c per channel, k = rs / (sd + 1e-8)
     float k[3], cst[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const double kc = (double)ref_std[c] / ((double)st->stdv[c] + 1e-8);      // (one division per channel, reused for every pixel)
-        const double shifted = ((double)lab_offset(c) - (double)st->mean[c]) * kc + (double)ref_mean[c];      // lab' at e = 0
+        const double kc = (double)ref_std[c] / ((double)src_std[c] + 1e-8);      // (one division per channel, reused for every pixel)
+        const double shifted = ((double)lab_offset(c) - (double)src_mean[c]) * kc + (double)ref_mean[c];      // lab' at e = 0
         k[c] = (float)kc;
         cst[c] = (float)(c == 0 ? (shifted / 2.55 + 16.0) / 116.0 : (shifted - 128.0) / (double)lab_scale(c));
     }
@@ -460,6 +475,20 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
 #pragma unroll
         for (int c = 0; c < 3; ++c) store_pack_stream<T, V>(dst + c * g.pixels + p, res[c]);
     }
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, State* __restrict__ st, const float* __restrict__ ref_mean, const float* __restrict__ ref_std, unsigned int call, Codes codes = Codes{nullptr, nullptr, 0u}) {
+    apply_chunk<T, V>(images, out, g, st->mean, st->stdv, ref_mean, ref_std, codes, [&] {
+        if (call != 0 && blockIdx.x == 0 && threadIdx.x == 0 && st->stats_of_call != call) atomicOr(&st->status, 1u);      // (see State)
+    });
+}
+
+// The apply pass with source statistics from device arrays: row 0 for every tile (per_tile == 0) or row `tile` (per_tile == 1)
+template <typename T, int V>
+__global__ __launch_bounds__(kStreamThreads) void apply_stats_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, const float* __restrict__ src_mean, const float* __restrict__ src_std, int per_tile, const float* __restrict__ ref_mean, const float* __restrict__ ref_std, Codes codes = Codes{nullptr, nullptr, 0u}) {
+    const int64_t row = per_tile ? blockIdx.x / g.blocks_per_tile : 0;
+    apply_chunk<T, V>(images, out, g, src_mean + row * 3, src_std + row * 3, ref_mean, ref_std, codes, [] {});
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -567,6 +596,89 @@ static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t
     }
 }
 
+// ---- per-tile statistics, given statistics ------------------------------------------------------------------------------------------
+// The per-tile calls keep the pooled workspace's layout (State, arrival counters, partial sums: a READY workspace stays ready) and put
+// the tiles' statistics -- N x 3 means, then N x 3 standard deviations -- behind it, the codes of a float32 batch behind those.
+// (They lie where the partial sums of the finest grid -- one sweep per work item -- would end: the pooled size follows sweeps_for() and
+// shrinks where a larger batch takes more sweeps; this one never decreases with the batch.)
+static size_t tile_stat_bytes(int64_t n) { return align_up(sizeof(float) * 6 * (size_t)n, 256); }
+static size_t tile_stat_offset(int64_t n, int64_t pixels) {
+    const size_t finest = (size_t)((pixels + (int64_t)kStreamThreads * 4 - 1) / ((int64_t)kStreamThreads * 4));
+    return align_up(sizeof(State), 256) + counter_bytes(n) + align_up(sizeof(double) * kSums * finest * (size_t)n, 256);
+}
+static size_t tiles_workspace_bytes(int64_t n, int64_t pixels) { return tile_stat_offset(n, pixels) + tile_stat_bytes(n); }
+
+template <typename T>
+static bool vector_path(const void* images, const void* out, int64_t pixels) {
+    return (pixels % 4 == 0) && (reinterpret_cast<uintptr_t>(images) % (sizeof(T) * 4) == 0) && (!out || reinterpret_cast<uintptr_t>(out) % (sizeof(T) * 4) == 0);
+}
+
+// statistics pass with a finish per tile; with `out` the apply pass with the tile's own row
+template <typename T>
+static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, float* mean_out, float* std_out, void* ws, size_t ws_bytes, hipStream_t stream) {
+    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    State* st = static_cast<State*>(ws);
+    unsigned int* tile_arrivals = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + align_up(sizeof(State), 256));
+    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(tile_arrivals) + counter_bytes(n));
+    char* behind = static_cast<char*>(ws) + tile_stat_offset(n, g.pixels);
+    if (!mean_out) {      // (both or neither: checked by the entry points)
+        mean_out = reinterpret_cast<float*>(behind);
+        std_out = mean_out + 3 * n;
+    }
+    const bool vec = vector_path<T>(images, out, g.pixels);
+    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
+    const T* in = static_cast<const T*>(images);
+    Codes codes{nullptr, nullptr, 0u};
+    if (std::is_same<T, float>::value && vec && out && coded_size(n, g.pixels) && ws_bytes >= tiles_workspace_bytes(n, g.pixels) + coded_bytes(n, g.pixels)) {
+        char* base = behind + tile_stat_bytes(n);
+        codes.bad = reinterpret_cast<unsigned int*>(base);
+        codes.planes = reinterpret_cast<uint8_t*>(base + align_up(sizeof(unsigned int) * (size_t)n, 256));
+        codes.epoch = ++g_code_epoch;
+        if (codes.epoch == 0u) codes.epoch = ++g_code_epoch;
+    }
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st, tile_arrivals, n);
+    if (vec)
+        hipLaunchKernelGGL((stats_kernel<T, 4, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, codes);
+    else
+        hipLaunchKernelGGL((stats_kernel<T, 1, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u});
+    if (out) {
+        if (vec)
+            hipLaunchKernelGGL((apply_stats_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, 1, ref_mean, ref_std, codes);
+        else
+            hipLaunchKernelGGL((apply_stats_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, 1, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
+    }
+    return check_launch("reinhard (per tile)");
+}
+
+static int dispatch_tiles(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* rm, const float* rs, float* mo, float* so, void* ws, size_t ws_bytes, void* stream_ptr) {
+    if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    const size_t need = tiles_workspace_bytes(n, h * w);
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {
+        case SX_U8: return run_tiles<uint8_t>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
+        case SX_F16: return run_tiles<__half>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
+        case SX_BF16: return run_tiles<__hip_bfloat16>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
+        case SX_F32: return run_tiles<float>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
+        default: return run_tiles<double>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
+    }
+}
+
+// the apply pass alone, with the caller's statistics: one launch
+template <typename T>
+static int run_apply_stats(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* ref_mean, const float* ref_std, hipStream_t stream) {
+    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
+    if (vector_path<T>(images, out, g.pixels))
+        hipLaunchKernelGGL((apply_stats_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
+    else
+        hipLaunchKernelGGL((apply_stats_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
+    return check_launch("reinhard (given statistics)");
+}
+
 }  // namespace reinhard
 }  // namespace sx
 
@@ -620,4 +732,41 @@ extern "C" int sx_reinhard_apply(const void* images, void* out, int dtype, int64
     if (!out || !sums || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "out / sums / ref_mean / ref_std pointer is null");
     if (!(n_total_pixels >= 1.0)) return fail(SX_ERR_BAD_ARG, "n_total_pixels must be >= 1");
     return reinhard::dispatch(images, out, dtype, n, h, w, ref_mean, ref_std, nullptr, nullptr, nullptr, sums, n_total_pixels, ws, ws_bytes, stream);
+}
+
+// Per-tile source statistics (torchstain's, tiatoolbox's, HistomicsTK's Reinhard works on ONE image): the pooled statistics pass with a
+// finish per tile, and the pooled apply pass's arithmetic on the tile's own row.
+extern "C" size_t sx_reinhard_tiles_workspace_bytes(int dtype, int64_t n, int64_t h, int64_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    size_t need = reinhard::tiles_workspace_bytes(n, h * w);
+    if (dtype == SX_F32 && reinhard::coded_size(n, h * w)) need += reinhard::coded_bytes(n, h * w);
+    return need;
+}
+
+extern "C" int sx_reinhard_tile_stats(const void* images, int dtype, int64_t n, int64_t h, int64_t w, float* tile_mean_out, float* tile_std_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!tile_mean_out || !tile_std_out) return fail(SX_ERR_BAD_ARG, "tile_mean_out / tile_std_out pointer is null");
+    return reinhard::dispatch_tiles(images, nullptr, dtype, n, h, w, nullptr, nullptr, tile_mean_out, tile_std_out, ws, ws_bytes, stream);
+}
+
+extern "C" int sx_reinhard_transform_tiles(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, float* tile_mean_out, float* tile_std_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!out || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "out / ref_mean / ref_std pointer is null");
+    if ((tile_mean_out == nullptr) != (tile_std_out == nullptr)) return fail(SX_ERR_BAD_ARG, "tile_mean_out and tile_std_out: both or neither");
+    return reinhard::dispatch_tiles(images, out, dtype, n, h, w, ref_mean, ref_std, tile_mean_out, tile_std_out, ws, ws_bytes, stream);
+}
+
+extern "C" int sx_reinhard_apply_stats(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, void* stream_ptr) {
+    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
+    if (!source_mean || !source_std || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / ref_mean / ref_std pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const int per_tile = n_sources == n && n != 1 ? 1 : 0;
+    switch (dtype) {
+        case SX_U8: return reinhard::run_apply_stats<uint8_t>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        case SX_F16: return reinhard::run_apply_stats<__half>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        case SX_BF16: return reinhard::run_apply_stats<__hip_bfloat16>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        case SX_F32: return reinhard::run_apply_stats<float>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        case SX_F64: return reinhard::run_apply_stats<double>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
 }
