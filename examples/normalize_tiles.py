@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The hot path in five lines each: the three normalisers, the nn.Module, uint8 HWC tiles as a decoder hands them over,
 the sampled `precision="fast"` mode, how a batch is split over GPUs (one process per GPU, no collective for
-`transform`), the slide-level use: one source estimate, applied to batch after batch, and per-tile statistics for Reinhard and
-histogram matching on a batch of tiles from different slides.  Run on a ROCm GPU:  python examples/normalize_tiles.py
+`transform`), the slide-level use: one source estimate, applied to batch after batch, per-tile statistics for Reinhard and
+histogram matching on a batch of tiles from different slides, and their tissue masks for tiles with slide background.  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -14,7 +14,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from stainx_amd import HistogramMatching, Macenko, Reinhard, StainNormalizerTransform, synth  # noqa: E402
+from stainx_amd import HistogramMatching, Macenko, Reinhard, StainNormalizerTransform, synth, tissue_mask  # noqa: E402
 from stainx_amd import distributed as sxd  # noqa: E402
 from stainx_amd.backends.torch_hip_backend import MacenkoHIP  # noqa: E402
 
@@ -86,6 +86,18 @@ def main() -> None:
     out_more = reinhard.apply(more, slide_stats)
     assert torch.equal(out, reinhard.transform(tiles))               # the pooled transform of that batch, bit for bit
     print(f"[rank {rank}] Reinhard slide-level    {tuple(out.shape)} + {tuple(out_more.shape)}  LAB mean = {[round(v, 2) for v in slide_stats.mean[0].tolist()]}")
+
+    # 8. tiles with slide background (edge tiles, sparse tiles, thumbnails): statistics over the TISSUE only, the glass left as it is.
+    #    mask="luminosity" applies the rule L* / 100 < 0.8 in every kernel; an explicit mask (a segmentation) replaces it for one call
+    edge = synth.background_stripes(batch[:6]).to(dev)               # tile i: a stripe of glass i / 5 of its width
+    mask, counts = tissue_mask(edge, luminosity_threshold=0.8)       # (N, H, W) uint8 and (N,) tissue pixels, on the device
+    for cls in (Reinhard, HistogramMatching):
+        masked = cls(device=dev, statistics="tile", mask="luminosity").fit(reference.to(dev))
+        out = masked.transform(edge)
+        glass = (mask == 0).unsqueeze(1).expand_as(edge)
+        assert torch.equal(out[glass], edge[glass])                  # background: the bits of the input
+        assert torch.equal(cls(device=dev, statistics="tile").fit(reference.to(dev)).transform(edge, mask=mask), out)      # the rule == its own mask
+        print(f"[rank {rank}] {cls.__name__ + ' tissue only':27s} {tuple(out.shape)} {out.dtype}  tissue share per tile {[round(c / (256 * 256), 2) for c in counts.tolist()]}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

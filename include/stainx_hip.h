@@ -424,6 +424,71 @@ int sx_hm_transform_tiles(const void* images_dev, void* out_dev, int dtype, int6
                           int channels_last, const float* ref_hist_dev, uint32_t* tile_counts_out_dev,
                           float* tile_lut_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- Tissue masks ---------------------
+ * An extension for Reinhard and histogram matching (HistomicsTK's reinhard(mask_out=), staintools' LuminosityThresholdTissueLocator,
+ * tiatoolbox): statistics -- LAB mean / standard deviation, histograms -- over TISSUE pixels only, and background pixels written with
+ * the bits of the input.  The unmasked entry points above are untouched.  Everywhere below:
+ *   mask_dev               const uint8_t, n_tiles x height x width, non-zero = tissue (one value per pixel: a pixel's three channels are
+ *                          in or out together), or NULL: the rule
+ *   luminosity_threshold   the rule: a pixel is tissue iff L* / 100 < luminosity_threshold (0.8: staintools' and tiatoolbox's default),
+ *                          L* of the pixel's unit value (u8 / 255, floats as they are) by the Reinhard section's colour conversion
+ *                          (0.8 <-> 204 on its 0..255 scale).  L* is monotone in the linear-light luminance Y, so every kernel compares
+ *                          Y with one constant derived on the host, by ONE device function: all entry points agree on every pixel.
+ *                          Outside (0, 1) -- NaN included -- is SX_ERR_BAD_ARG; not read when mask_dev is given.
+ * A tile (or pooled batch) with fewer than two tissue pixels has no statistics: mean and standard deviation NaN, and every apply pass
+ * copies a tile through whose row of statistics holds a NaN.  The tissue edge is a hard edge: no smoothing.
+ *
+ * sx_tissue_mask: the rule as a call of its own, one streaming pass (and a clear of the counts).  mask_out_dev: n_tiles x height x
+ *   width bytes, 1 / 0; tile_counts_out_dev: n_tiles uint64 tissue pixels per tile; either may be NULL, not both.  channels_last != 0:
+ *   images are (N,H,W,3). */
+int sx_tissue_mask(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                   double luminosity_threshold, uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
+
+/* Reinhard.  per_tile != 0: every tile its own statistics (N rows, a tile's result does not depend on its neighbours); per_tile == 0: one
+ * set pooled over the tissue of the whole batch (one row).  Workspace: sx_reinhard_masked_workspace_bytes(); any contents are accepted
+ * and a workspace that was READY (sx_reinhard_transform_ready) is left ready, so the calls may alternate with that one and with
+ * sx_reinhard_transform_tiles on one workspace.
+ * sx_reinhard_stats_masked: the statistics pass alone.  mean_out_dev, std_out_dev: rows x 3 floats (required); counts_out_dev: rows
+ *   uint64 tissue pixels, may be NULL.  With every pixel tissue the rows are bit for bit those of sx_reinhard_tile_stats /
+ *   sx_reinhard_fit (same grid, same reduction order; the divisor is the exact integer count).
+ * sx_reinhard_transform_masked: that pass, then the apply pass: two streaming launches and the clearing launch.  mean_out_dev /
+ *   std_out_dev: both or neither (exactly one NULL is SX_ERR_BAD_ARG); counts_out_dev may be NULL.
+ * sx_reinhard_apply_stats_masked: sx_reinhard_apply_stats with a mask -- ONE launch on `stream`, nothing else enqueued, no workspace;
+ *   statistics, reference and mask are DEVICE memory read by the kernel (a captured graph replayed after new values were written into
+ *   the same buffers uses the new values).  A tissue pixel gets exactly the bits the unmasked apply pass gives with those statistics. */
+size_t sx_reinhard_masked_workspace_bytes(int dtype, int64_t n_tiles, int64_t height, int64_t width);
+int sx_reinhard_stats_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                             const uint8_t* mask_dev, double luminosity_threshold, int per_tile, float* mean_out_dev,
+                             float* std_out_dev, unsigned long long* counts_out_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream);
+int sx_reinhard_transform_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                                 int64_t width, const float* ref_mean_dev, const float* ref_std_dev, const uint8_t* mask_dev,
+                                 double luminosity_threshold, int per_tile, float* mean_out_dev, float* std_out_dev,
+                                 unsigned long long* counts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int sx_reinhard_apply_stats_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                                   int64_t width, const float* source_mean_dev, const float* source_std_dev, int64_t n_sources,
+                                   const float* ref_mean_dev, const float* ref_std_dev, const uint8_t* mask_dev,
+                                   double luminosity_threshold, void* stream);
+
+/* Histogram matching, NCHW and NHWC.  The three 256-bin histograms count tissue pixels only, and the LUT arithmetic takes the TISSUE count
+ * as its number of pixels (the sum of a channel's histogram); a tissue pixel gets its LUT value, a background pixel the bits of its
+ * input (floats are not quantised).  Pixel-wise kernels: each pass reads the pixels (and the mask, where one is given) and nothing
+ * else.  One clear, the histogram pass, the LUT launch, the apply pass.  Workspace: sx_hm_masked_workspace_bytes(); any contents are
+ * accepted and the workspace is left READY (the status word lies where sx_hm_workspace_status_offset says: bit 0 is set when a
+ * channel's total does not agree with the tissue pixels counted).
+ * sx_hm_fit_masked: the normalised tissue histograms of the whole batch, 3 x 256 floats; tissue_count_out_dev: one uint64, may be NULL.
+ * sx_hm_transform_masked: per_tile != 0: one histogram and one LUT per tile (sets = n_tiles); per_tile == 0: one pooled over the tissue
+ *   of the batch (sets = 1).  tile_counts_out_dev: sets x 3 x 256 uint32 histograms as counted; tile_lut_out_dev: sets x 3 x 256 floats;
+ *   tissue_counts_out_dev: sets uint64; each may be NULL. */
+size_t sx_hm_masked_workspace_bytes(int64_t n_tiles, int64_t height, int64_t width);
+int sx_hm_fit_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                     const uint8_t* mask_dev, double luminosity_threshold, float* hist_out_dev,
+                     unsigned long long* tissue_count_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int sx_hm_transform_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                           int channels_last, const float* ref_hist_dev, const uint8_t* mask_dev, double luminosity_threshold,
+                           int per_tile, uint32_t* tile_counts_out_dev, float* tile_lut_out_dev,
+                           unsigned long long* tissue_counts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

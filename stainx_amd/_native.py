@@ -99,6 +99,15 @@ SIGNATURES = {
     "sx_hm_fit_ready": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
     "sx_hm_transform_ready": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
     "sx_hm_counts_ready": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
+    # tissue masks: `mask_dev` may be None (the luminosity rule with the double that follows it)
+    "sx_tissue_mask": (_int, [_vp, _int, _i64, _i64, _i64, _int, _c.c_double, _vp, _vp, _vp]),
+    "sx_reinhard_masked_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
+    "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sx_reinhard_apply_stats_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _c.c_double, _vp]),
+    "sx_hm_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "sx_hm_fit_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "sx_hm_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

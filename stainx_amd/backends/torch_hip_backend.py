@@ -52,6 +52,33 @@ class TorchHIPBackendBase:
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
 
+def _mask_bytes(mask: torch.Tensor | None, device: torch.device) -> torch.Tensor | None:
+    """An explicit tissue mask as the dense (N, H, W) uint8 tensor the library reads (bool: the same bytes; no copy where it is dense already)."""
+    if mask is None:
+        return None
+    mask = mask.to(device)
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def tissue_mask_native(images: torch.Tensor, luminosity_threshold: float, channels_last: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """``stainx_amd.tissue_mask`` behind its checks: (N, H, W) uint8 mask and (N,) int64 tissue counts (include/stainx_hip.h: sx_tissue_mask)."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images = images.to(base.device).contiguous()
+    n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return mask, counts
+    with _native.on_device(base.device):
+        rc = base._lib.sx_tissue_mask(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), float(luminosity_threshold), mask.data_ptr(),
+                                      counts.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_tissue_mask")
+    return mask, counts
+
+
 class MacenkoHIP(TorchHIPBackendBase):
     """Macenko transform / fit on the GPU (numerics of MacenkoTorch, torch_backend.py:358-560)."""
 
@@ -796,6 +823,95 @@ class ReinhardHIP(TorchHIPBackendBase):
         _native.check(rc, "sx_reinhard_apply_stats")
         return out
 
+    # ---- tissue masks (include/stainx_hip.h: sx_reinhard_stats_masked ...) --------------------------------
+    def _masked_workspace(self, n: int, h: int, w: int, code: int) -> torch.Tensor:
+        scratch = self.__dict__.get("_masked_scratch")
+        if scratch is None:
+            scratch = self.__dict__.setdefault("_masked_scratch", _native.Scratch())
+        return scratch.get(int(self._lib.sx_reinhard_masked_workspace_bytes(code, n, h, w)), self.device)
+
+    def masked_statistics(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float, *, per_tile: bool):
+        """LAB mean / unbiased standard deviation over TISSUE pixels -- ``mask`` (N, H, W) uint8, or None: the luminosity rule -- of every
+        tile (``per_tile``: (N, 3) each) or pooled over the batch ((1, 3) each), and the tissue counts (int64).  Fewer than two tissue
+        pixels: a row of NaN."""
+        images = images.to(self.device)
+        self._check(images)
+        images = images.contiguous()
+        n, _, h, w = images.shape
+        rows = n if per_tile else 1
+        mean = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        std = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        counts = torch.zeros((rows,), dtype=torch.int64, device=self.device)
+        if images.numel() == 0:
+            return mean.fill_(float("nan")), std.fill_(float("nan")), counts
+        mask = _mask_bytes(mask, self.device)
+        with _native.on_device(self.device):
+            ws = self._masked_workspace(n, h, w, _dtype_code(images))
+            rc = self._lib.sx_reinhard_stats_masked(images.data_ptr(), _dtype_code(images), n, h, w, None if mask is None else mask.data_ptr(), float(luminosity_threshold),
+                                                    int(per_tile), mean.data_ptr(), std.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_reinhard_stats_masked")
+        return mean, std, counts
+
+    def transform_masked(self, images: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float, *,
+                         per_tile: bool, return_statistics: bool = False):
+        """Tissue pixels normalised with the statistics of the tissue (per tile, or pooled over the batch), background pixels copied: two
+        streaming launches.  With ``return_statistics`` also mean, std and the tissue counts."""
+        images = images.to(self.device)
+        self._check(images)
+        images = images.contiguous()
+        mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
+        if mean.numel() != 3 or std.numel() != 3:
+            raise ValueError("reference_mean / reference_std must have 3 elements")
+        n, _, h, w = images.shape
+        rows = n if per_tile else 1
+        out = torch.empty_like(images)
+        src_mean = src_std = counts = None
+        if return_statistics:
+            src_mean = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+            src_std = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+            counts = torch.zeros((rows,), dtype=torch.int64, device=self.device)
+        if images.numel() != 0:
+            mask = _mask_bytes(mask, self.device)
+            with _native.on_device(self.device):
+                ws = self._masked_workspace(n, h, w, _dtype_code(images))
+                rc = self._lib.sx_reinhard_transform_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
+                                                            None if mask is None else mask.data_ptr(), float(luminosity_threshold), int(per_tile),
+                                                            None if src_mean is None else src_mean.data_ptr(), None if src_std is None else src_std.data_ptr(),
+                                                            None if counts is None else counts.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_reinhard_transform_masked")
+        return (out, src_mean, src_std, counts) if return_statistics else out
+
+    def apply_statistics_masked(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor,
+                                mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
+        """``apply_statistics`` with a tissue mask: one launch; background pixels, and tiles whose row of statistics holds a NaN, are copied."""
+        images = images.to(self.device)
+        self._check(images)
+        n, _, h, w = images.shape
+        if source_mean.dim() == 1:
+            source_mean = source_mean.unsqueeze(0)
+        if source_std.dim() == 1:
+            source_std = source_std.unsqueeze(0)
+        for name, t in (("source_mean", source_mean), ("source_std", source_std)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
+                raise ValueError(f"{name} must be (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
+        if source_mean.shape[0] != source_std.shape[0]:
+            raise ValueError(f"source_mean and source_std must have the same number of rows, got {source_mean.shape[0]} and {source_std.shape[0]}")
+        images = images.contiguous()
+        mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
+        if mean.numel() != 3 or std.numel() != 3:
+            raise ValueError("reference_mean / reference_std must have 3 elements")
+        src_mean, src_std = self._f32(source_mean), self._f32(source_std)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        mask = _mask_bytes(mask, self.device)
+        with _native.on_device(self.device):
+            rc = self._lib.sx_reinhard_apply_stats_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, src_mean.data_ptr(), src_std.data_ptr(),
+                                                          int(src_mean.shape[0]), mean.data_ptr(), std.data_ptr(), None if mask is None else mask.data_ptr(),
+                                                          float(luminosity_threshold), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_reinhard_apply_stats_masked")
+        return out
+
     # ---- batch statistics pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_sums(self, images: torch.Tensor) -> torch.Tensor:
         """6 fp64 values: per channel sum and sum of squares of (LAB - 128) over this rank's pixels."""
@@ -960,6 +1076,55 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         counts = ws[base + 4 * words: base + 8 * words].view(torch.int32).reshape(n, 3, 256).cpu().long()
         lut = ws[base + 8 * words: base + 12 * words].view(torch.float32).reshape(n, 3, 256).cpu()
         return {"counts": counts, "lut": lut}
+
+    # ---- tissue masks (include/stainx_hip.h: sx_hm_fit_masked, sx_hm_transform_masked) ----------------------
+    def _masked_workspace(self, n: int, h: int, w: int) -> torch.Tensor:
+        scratch = self.__dict__.get("_masked_scratch")
+        if scratch is None:
+            scratch = self.__dict__.setdefault("_masked_scratch", _native.Scratch())
+        return scratch.get(int(self._lib.sx_hm_masked_workspace_bytes(n, h, w)), self.device)
+
+    def compute_reference_histograms_masked(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> list[torch.Tensor]:
+        """``compute_reference_histograms`` over TISSUE pixels only (``mask`` (N, H, W) uint8, or None: the luminosity rule)."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        hists = torch.empty((3, 256), dtype=torch.float32, device=self.device)
+        count = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        mask = _mask_bytes(mask, self.device)
+        with _native.on_device(self.device):
+            ws = self._masked_workspace(n, h, w)
+            rc = self._lib.sx_hm_fit_masked(images.data_ptr(), _dtype_code(images), n, h, w, int(last), None if mask is None else mask.data_ptr(), float(luminosity_threshold),
+                                            hists.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_fit_masked")
+        self.last_workspace = ws
+        self.last_tissue_count = count
+        return [hists[c] for c in range(3)]
+
+    def transform_masked(self, images: torch.Tensor, reference_histogram, mask: torch.Tensor | None, luminosity_threshold: float, *, per_tile: bool,
+                         return_tables: bool = False):
+        """Tissue pixels matched with the histogram(s) of the tissue -- one per tile, or one pooled over the batch --, background pixels
+        copied with the bits of the input.  With ``return_tables`` also a dict: ``counts`` (sets, 3, 256) int32 histograms as counted,
+        ``lut`` (sets, 3, 256) float LUTs, ``tissue`` (sets,) int64 tissue pixels (sets = N per tile, 1 pooled)."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        ref = self._stack_reference(reference_histogram, 3)
+        out = torch.empty_like(images)
+        sets = n if per_tile else 1
+        tables = None
+        if return_tables:
+            tables = {"counts": torch.zeros((sets, 3, 256), dtype=torch.int32, device=self.device), "lut": torch.zeros((sets, 3, 256), dtype=torch.float32, device=self.device),
+                      "tissue": torch.zeros((sets,), dtype=torch.int64, device=self.device)}
+        if images.numel() != 0:
+            mask = _mask_bytes(mask, self.device)
+            with _native.on_device(self.device):
+                ws = self._masked_workspace(n, h, w)
+                rc = self._lib.sx_hm_transform_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), ref.data_ptr(),
+                                                      None if mask is None else mask.data_ptr(), float(luminosity_threshold), int(per_tile),
+                                                      None if tables is None else tables["counts"].data_ptr(), None if tables is None else tables["lut"].data_ptr(),
+                                                      None if tables is None else tables["tissue"].data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_hm_transform_masked")
+            self.last_workspace = ws
+        return (out, tables) if return_tables else out
 
     # ---- source histogram pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_counts(self, images: torch.Tensor) -> torch.Tensor:

@@ -14,6 +14,7 @@
 // typed LUT, 16-byte loads and stores, writes the final dtype directly (the reference's native path
 // takes three more passes: histogram_matching.cu:153-166).
 #include "common.hpp"
+#include "tissue.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -290,8 +291,11 @@ static TileAreas tile_areas(void* ws, int64_t n, uint32_t* counts_out, float* lu
 
 // kPerTile: workgroup b serves channel b % 3 of tile b / 3 -- 3N independent chains, the reference's (which does not depend on the tile)
 // beside each -- with the tile's own counters and tables; num_pixels is the pixels of ONE tile.
-template <typename T, bool kPerTile = false>
-__global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, const unsigned long long* __restrict__ counts, const bool local, const float* __restrict__ ref_hist, double num_pixels, TileAreas tiles = TileAreas{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
+// kMasked (the tissue forms; always with a set per tile, one set for a pooled call): num_pixels is the TISSUE count -- the sum of the
+// channel's own counters -- and the ready-state check compares that sum with the tissue pixels the histogram pass counted for the set
+// (every channel with that one count: the three totals agree with each other and with the mask).
+template <typename T, bool kPerTile, bool kMasked>
+__device__ __forceinline__ void lut_body(Tables* __restrict__ tab, const unsigned long long* __restrict__ counts, const bool local, const float* __restrict__ ref_hist, double num_pixels, TileAreas tiles, const uint32_t* __restrict__ tissue_counts, unsigned long long* __restrict__ tissue_out) {
     const int c = kPerTile ? blockIdx.x % 3 : blockIdx.x, t = threadIdx.x;
     const size_t tile_entry = kPerTile ? ((size_t)blockIdx.x * kBins + t) : 0;      // (tile * 3 + c) * 256 + t
     __shared__ float src_cdf[kBins], ref_cdf[kBins];
@@ -326,10 +330,22 @@ __global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, co
         __shared__ double parts[kBins / kWave];
         if (lane_id() == 0) parts[t / kWave] = wave_total;
         __syncthreads();
+        __shared__ double total_s;
         if (t == 0) {
             double total = 0.0;
             for (int w = 0; w < kBins / kWave; ++w) total += parts[w];
-            if (total != num_pixels) atomicOr(&tab->status, 1u);
+            if constexpr (kMasked) {
+                const uint32_t set = blockIdx.x / 3;
+                if (total != (double)tissue_counts[set]) atomicOr(&tab->status, 1u);
+                if (c == 0 && tissue_out) tissue_out[set] = (unsigned long long)total;
+                total_s = total;
+            } else {
+                if (total != num_pixels) atomicOr(&tab->status, 1u);
+            }
+        }
+        if constexpr (kMasked) {
+            __syncthreads();
+            num_pixels = total_s;
         }
     } else {
         count = counts[c * kBins + t];
@@ -349,6 +365,15 @@ __global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, co
     } else {
         lut_entry<T>(tab, c, t, src_cdf[t], ref_cdf);
     }
+}
+
+template <typename T, bool kPerTile = false>
+__global__ __launch_bounds__(kBins) void lut_kernel(Tables* __restrict__ tab, const unsigned long long* __restrict__ counts, const bool local, const float* __restrict__ ref_hist, double num_pixels, TileAreas tiles = TileAreas{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}) {
+    lut_body<T, kPerTile, false>(tab, counts, local, ref_hist, num_pixels, tiles, nullptr, nullptr);
+}
+template <typename T>
+__global__ __launch_bounds__(kBins) void lut_masked_kernel(Tables* __restrict__ tab, const float* __restrict__ ref_hist, TileAreas tiles, const uint32_t* __restrict__ tissue_counts, unsigned long long* __restrict__ tissue_out) {
+    lut_body<T, true, true>(tab, nullptr, true, ref_hist, 0.0, tiles, tissue_counts, tissue_out);
 }
 
 // Planar layout, 16-byte packs: a workgroup takes one chunk of ONE channel plane, so a single 256-bin histogram is live
@@ -488,6 +513,171 @@ __global__ __launch_bounds__(kThreads) void apply_tiles_kernel(const T* __restri
     }
 }
 
+// ---- tissue masks: pixel-wise kernels ---------------------------------------------------------------------------------------------------
+// The rule needs a pixel's three channels, and the planar kernels above see one channel plane per workgroup.  The masked forms are
+// therefore PIXEL-WISE in both layouts: a thread holds one 16-byte pack of each of the three planes (planar) or three consecutive packs
+// (interleaved) -- VP = 16 / sizeof(T) whole pixels --, decides each pixel once (the caller's mask bytes, or the rule of tissue.hpp on the
+// pixel's linear-light values: a 256-entry table for uint8) and counts / replaces the three elements of a tissue pixel.  Three
+// histograms are live: 16 bank-striped copies of each (48 KB, the layout of histogram_last_kernel).  No mask is written or read in
+// the rule form: each pass reads the pixels and nothing else.  (DESIGN.md 5c weighs this against a mask written first.)
+constexpr int kMaskTrips = 8;      // packs per thread and work item
+
+// (the layout is a template argument: with a run-time branch between the two pack forms the compiler keeps the pixels in scratch memory)
+template <typename T, int VP, bool kLast>
+__device__ __forceinline__ void load_pixels(const T* __restrict__ tile, int64_t pixels, int64_t p, T (&v)[3][VP]) {
+    if constexpr (VP == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][0] = tile[kLast ? p * 3 + c : c * pixels + p];
+    } else if constexpr (kLast) {
+        const Pack<T, VP> first = *reinterpret_cast<const Pack<T, VP>*>(tile + 3 * p), second = *reinterpret_cast<const Pack<T, VP>*>(tile + 3 * p + VP),
+                          third = *reinterpret_cast<const Pack<T, VP>*>(tile + 3 * p + 2 * VP);
+#pragma unroll
+        for (int k = 0; k < 3 * VP; ++k) v[k % 3][k / 3] = k < VP ? first.v[k % VP] : k < 2 * VP ? second.v[k % VP] : third.v[k % VP];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const Pack<T, VP> pk = *reinterpret_cast<const Pack<T, VP>*>(tile + c * pixels + p);
+#pragma unroll
+            for (int i = 0; i < VP; ++i) v[c][i] = pk.v[i];
+        }
+    }
+}
+template <typename T, int VP, bool kLast>
+__device__ __forceinline__ void store_pixels(T* __restrict__ tile, int64_t pixels, int64_t p, const T (&v)[3][VP]) {
+    if constexpr (VP == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tile[kLast ? p * 3 + c : c * pixels + p] = v[c][0];
+    } else if constexpr (kLast) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            T piece[VP];
+#pragma unroll
+            for (int i = 0; i < VP; ++i) piece[i] = v[(j * VP + i) % 3][(j * VP + i) / 3];
+            store_pack_stream<T, VP>(tile + 3 * p + j * VP, piece);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) store_pack_stream<T, VP>(tile + c * pixels + p, v[c]);
+    }
+}
+// bit i: pixel i of the pack is tissue (uniform branch: a call has a mask or it has none)
+template <typename T, int VP>
+__device__ __forceinline__ uint32_t pixel_bits(const tissue::Source& tis, int64_t pixel_index, const T (&v)[3][VP], const LinearTable& table) {
+    uint32_t in = 0u;
+    if (tis.mask) {
+        if constexpr (VP == 1) {
+            in = tis.mask[pixel_index] ? 1u : 0u;
+        } else {
+            const Pack<uint8_t, VP> m = *reinterpret_cast<const Pack<uint8_t, VP>*>(tis.mask + pixel_index);
+#pragma unroll
+            for (int i = 0; i < VP; ++i) in |= m.v[i] ? (1u << i) : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VP; ++i)
+            in |= tissue::is_tissue(tissue::linear_of<T>(v[0][i], table), tissue::linear_of<T>(v[1][i], table), tissue::linear_of<T>(v[2][i], table), tis.y_cut) ? (1u << i) : 0u;
+    }
+    return in;
+}
+
+// workgroup b: work item b % chunks_per_tile of tile b / chunks_per_tile; its counts go to set `tile` (per_tile) or set 0 of `counts`
+// ([sets][3][256]), its tissue pixels to the set's word of `tissue_counts`
+template <typename T, bool kVec, bool kLast>
+__global__ __launch_bounds__(kThreads) void histogram_masked_kernel(const T* __restrict__ images, Layout lay, int chunks_per_tile, int per_tile, tissue::Source tis, uint32_t* __restrict__ counts, uint32_t* __restrict__ tissue_counts) {
+    constexpr int VP = kVec ? VecOf<T>::n : 1;
+    __shared__ uint32_t hist[3][kBins][kLastCopies];
+    __shared__ LinearTable table;
+    for (int i = threadIdx.x; i < 3 * kBins * kLastCopies; i += kThreads) (&hist[0][0][0])[i] = 0;
+    if constexpr (sizeof(T) == 1) table.fill();
+    __syncthreads();
+    const int64_t tile = blockIdx.x / chunks_per_tile;
+    const int64_t set = per_tile ? tile : 0;
+    const T* src = images + tile * 3 * lay.pixels;
+    const int64_t begin = (int64_t)(blockIdx.x % chunks_per_tile) * kThreads * VP * kMaskTrips, end = min(begin + (int64_t)kThreads * VP * kMaskTrips, lay.pixels);
+    const int copy = threadIdx.x & (kLastCopies - 1);
+    uint32_t mine = 0;
+    for (int64_t p = begin + (int64_t)threadIdx.x * VP; p < end; p += (int64_t)kThreads * VP) {
+        T v[3][VP];
+        load_pixels<T, VP, kLast>(src, lay.pixels, p, v);
+        const uint32_t in = pixel_bits<T, VP>(tis, tile * lay.pixels + p, v, table);
+        mine += (uint32_t)__builtin_popcount(in);
+#pragma unroll
+        for (int i = 0; i < VP; ++i) {
+            if ((in >> i) & 1u) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) atomicAdd(&hist[c][grey_level<T>(v[c][i])][copy], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) {      // thread t adds up the copies of bin t of each channel, starting at its own bank
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < kLastCopies; ++k) sum += (&hist[0][0][0])[i * kLastCopies + ((threadIdx.x + k) & (kLastCopies - 1))];
+        if (sum) atomicAdd(&counts[set * 3 * kBins + i], sum);
+    }
+    const uint32_t wave_tissue = wave_total_u32(mine);
+    if (lane_id() == 0 && wave_tissue) atomicAdd(&tissue_counts[set], wave_tissue);
+}
+
+// a tissue pixel gets its LUT values, a background pixel the bits of its input elements (floats are not quantised)
+template <typename T, bool kVec, bool kLast>
+__global__ __launch_bounds__(kThreads) void apply_masked_kernel(const T* __restrict__ images, T* __restrict__ out, Layout lay, int chunks_per_tile, int per_tile, tissue::Source tis, const T* __restrict__ typed) {
+    constexpr int VP = kVec ? VecOf<T>::n : 1;
+    // (uint8: a fourth row, the identity, and the row chosen by arithmetic on the pixel's bit -- sixteen pixels' selects on compare masks
+    // do not fit the scalar registers)
+    __shared__ T lut[sizeof(T) == 1 ? 4 : 3][kBins];
+    __shared__ LinearTable table;
+    const int64_t tile = blockIdx.x / chunks_per_tile;
+    const int64_t set = per_tile ? tile : 0;
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) (&lut[0][0])[i] = typed[set * 3 * kBins + i];
+    if constexpr (sizeof(T) == 1) {
+        for (int i = threadIdx.x; i < kBins; i += kThreads) lut[3][i] = (T)i;
+        table.fill();
+    }
+    __syncthreads();
+    const T* src = images + tile * 3 * lay.pixels;
+    T* dst = out + tile * 3 * lay.pixels;
+    const int64_t begin = (int64_t)(blockIdx.x % chunks_per_tile) * kThreads * VP * kMaskTrips, end = min(begin + (int64_t)kThreads * VP * kMaskTrips, lay.pixels);
+    for (int64_t p = begin + (int64_t)threadIdx.x * VP; p < end; p += (int64_t)kThreads * VP) {
+        T v[3][VP];
+        load_pixels<T, VP, kLast>(src, lay.pixels, p, v);
+        const uint32_t in = pixel_bits<T, VP>(tis, tile * lay.pixels + p, v, table);
+#pragma unroll
+        for (int i = 0; i < VP; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (sizeof(T) == 1) v[c][i] = lut[3 - (int)((in >> i) & 1u) * (3 - c)][grey_level<T>(v[c][i])];
+                else v[c][i] = (in >> i) & 1u ? lut[c][grey_level<T>(v[c][i])] : v[c][i];
+            }
+        store_pixels<T, VP, kLast>(dst, lay.pixels, p, v);
+    }
+}
+
+// fit: the pooled tissue histogram of set 0, normalised as normalise_kernel() does
+__global__ void normalise_masked_kernel(Tables* __restrict__ tab, uint32_t* __restrict__ counts, uint32_t* __restrict__ counted, const uint32_t* __restrict__ tissue_counts, float* __restrict__ hist_out, unsigned long long* __restrict__ tissue_out) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    __shared__ float total_s;
+    __shared__ float raw[kBins];
+    __shared__ double parts[kBins / kWave];
+    const uint32_t count = counts[c * kBins + t];
+    counts[c * kBins + t] = 0;      // consumed
+    counted[c * kBins + t] = count;
+    raw[t] = (float)count;
+    const double wave_total = wave_sum((double)count);
+    if (lane_id() == 0) parts[t / kWave] = wave_total;
+    __syncthreads();
+    if (t == 0) {
+        double total = 0.0;
+        for (int w = 0; w < kBins / kWave; ++w) total += parts[w];
+        if (total != (double)tissue_counts[0]) atomicOr(&tab->status, 1u);
+        if (c == 0 && tissue_out) tissue_out[0] = (unsigned long long)total;
+        total_s = torch_sum_256([&](int b) { return raw[b]; }) + 1e-8f;
+    }
+    __syncthreads();
+    hist_out[c * kBins + t] = raw[t] / total_s;
+}
+
 #ifdef SX_DIAG
 }  // namespace histmatch
 }  // namespace sx
@@ -611,6 +801,63 @@ static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_
     return check_launch("histogram transform (per tile)");
 }
 
+// The masked calls: behind the Tables one tissue counter per set, then the per-tile areas of `sets` sets (a pooled call: one set).  One
+// clear covers the pooled live counters, the status word, the tissue counters and the sets' live counters: any contents in, READY out.
+static size_t masked_tissue_bytes(int64_t n) { return (sizeof(uint32_t) * (size_t)n + 255) / 256 * 256; }
+static size_t masked_workspace_bytes(int64_t n) { return workspace_bytes() + masked_tissue_bytes(n) + tile_area_bytes(n); }
+
+template <typename T>
+static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, tissue::Source tis, bool per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, hipStream_t stream) {
+    Layout lay{n, h * w, channels_last};
+    Tables* tab = static_cast<Tables*>(ws);
+    const int64_t sets = per_tile ? n : 1;
+    uint32_t* tissue_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + sizeof(Tables));
+    const TileAreas areas = tile_areas(static_cast<char*>(ws) + masked_tissue_bytes(n), sets, counts_out, lut_out);
+    const T* in = static_cast<const T*>(images);
+    constexpr int V = VecOf<T>::n;
+    // vector path: 16-byte aligned bases, whole packs of pixels per tile, a pack's mask bytes aligned
+    const bool vec = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (lay.pixels % V == 0) && (reinterpret_cast<uintptr_t>(tis.mask) % V == 0);
+    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + masked_tissue_bytes(n) + sizeof(uint32_t) * (size_t)sets * 3 * kBins, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kMaskTrips;
+    const int chunks_per_tile = (int)((lay.pixels + chunk - 1) / chunk);
+    const unsigned grid = (unsigned)(n * chunks_per_tile);
+#define SX_HM_MASKED_LAUNCH(kernel, ...)                                                                                                  \
+    if (vec && channels_last) hipLaunchKernelGGL((kernel<T, true, true>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);            \
+    else if (vec) hipLaunchKernelGGL((kernel<T, true, false>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);                       \
+    else if (channels_last) hipLaunchKernelGGL((kernel<T, false, true>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);             \
+    else hipLaunchKernelGGL((kernel<T, false, false>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);
+    SX_HM_MASKED_LAUNCH(histogram_masked_kernel, in, lay, chunks_per_tile, per_tile ? 1 : 0, tis, areas.counts, tissue_counts)
+    if (hist_out) {
+        hipLaunchKernelGGL(normalise_masked_kernel, dim3(3), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, tissue_counts, hist_out, tissue_out);
+        return check_launch("histogram fit (tissue mask)");
+    }
+    hipLaunchKernelGGL((lut_masked_kernel<T>), dim3((unsigned)(3 * sets)), dim3(kBins), 0, stream, tab, ref_hist, areas, tissue_counts, tissue_out);
+    SX_HM_MASKED_LAUNCH(apply_masked_kernel, in, static_cast<T*>(out), lay, chunks_per_tile, per_tile ? 1 : 0, tis, static_cast<const T*>(areas.typed))
+#undef SX_HM_MASKED_LAUNCH
+    return check_launch("histogram transform (tissue mask)");
+}
+
+static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, const uint8_t* mask, double threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, size_t ws_bytes, void* stream_ptr) {
+    if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
+    if (!mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
+    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    const size_t need = masked_workspace_bytes(n);
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(threshold)};
+    const bool tiles = per_tile != 0;
+    switch (dtype) {
+        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+        case SX_F16: return run_masked<__half>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+        case SX_F32: return run_masked<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+        default: return run_masked<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+    }
+}
+
 static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, unsigned long long* counts_out, const unsigned long long* counts_in, double n_total, void* ws, size_t ws_bytes, void* stream_ptr, bool ready = false) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
@@ -713,4 +960,20 @@ extern "C" int sx_hm_transform_tiles(const void* images, void* out, int dtype, i
         case SX_F32: return histmatch::run_tiles<float>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
         default: return histmatch::run_tiles<double>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
     }
+}
+
+// ---- tissue masks: histograms over tissue pixels only, background pixels copied (an extension) --------------------------------------------
+extern "C" size_t sx_hm_masked_workspace_bytes(int64_t n, int64_t h, int64_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return histmatch::masked_workspace_bytes(n);
+}
+
+extern "C" int sx_hm_fit_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const uint8_t* mask, double luminosity_threshold, float* hist_out, unsigned long long* tissue_count_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!hist_out) return fail(SX_ERR_BAD_ARG, "hist_out pointer is null");
+    return histmatch::dispatch_masked(images, nullptr, dtype, n, h, w, channels_last, nullptr, hist_out, mask, luminosity_threshold, 0, nullptr, nullptr, tissue_count_out, ws, ws_bytes, stream);
+}
+
+extern "C" int sx_hm_transform_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, const uint8_t* mask, double luminosity_threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_counts_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!out || !ref_hist) return fail(SX_ERR_BAD_ARG, "out / ref_hist pointer is null");
+    return histmatch::dispatch_masked(images, out, dtype, n, h, w, channels_last, ref_hist, nullptr, mask, luminosity_threshold, per_tile, counts_out, lut_out, tissue_counts_out, ws, ws_bytes, stream);
 }

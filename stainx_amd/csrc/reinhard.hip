@@ -9,6 +9,7 @@
 // LAB is recomputed in pass 2 instead of being stored: 24 VALU-cheap transcendentals per pixel are
 // cheaper than a 12 B/px round trip through HBM.
 #include "common.hpp"
+#include "tissue.hpp"
 #include <algorithm>
 #include <atomic>
 #include <cstddef>
@@ -33,30 +34,8 @@ struct alignas(256) State {
 };
 
 // Divisions by the colour-space constants are multiplications by their reciprocals (<= 1 ulp from the reference's
-// divisions, far inside the 1e-4 tolerance); pow goes through v_log_f32 / v_exp_f32; x > 0.  The BARE instructions: every pow whose
-// result is used has a normal argument and a normal result (colour values and their powers are >= 3e-3), and the range handling of
-// exp2f / __log2f -- compare, select, rescale: ~8 instructions per pow, nine pows per pixel in the apply pass -- only matters for
-// denormals (apply 689 -> 526 vector instructions per four pixels; 146 -> 130 us per call, max error against the oracle unchanged
-// at 1.2e-5, tools/check_reinhard_error.py).  A branch that is not taken may see log(0) or log(negative): its value is dropped.
-__device__ __forceinline__ float fast_pow(float x, float e) { return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)); }
-
-// (The piecewise functions stay `cond ? pow : line`: the compiler keeps an exec-mask branch around each logarithm / exponential pair,
-// six per pixel in the apply pass.  Computing both pieces and selecting removes 170 scalar instructions and 50 s_nop per four pixels
-// and is no faster -- 134 against 130 us per call: both passes are bound by the vector instruction count, 448 per four pixels of which
-// 70 are quarter-rate logarithms / exponentials, and the select form has nine more.)
-__device__ __forceinline__ float srgb_to_linear(float v) {      // torch_backend.py:28-29
-    return v > 0.04045f ? fast_pow((v + 0.055f) * (1.0f / 1.055f), 2.4f) : v * (1.0f / 12.92f);
-}
-
-// uint8 pixels take one of 256 values per channel: their linear-light value comes from a table in LDS (filled with the very
-// expression above, so every pixel gets the bits it got before) instead of a division, a logarithm and an exponential each.
-struct LinearTable {
-    float lin[256];
-    __device__ __forceinline__ void fill() {
-        for (int t = threadIdx.x; t < 256; t += blockDim.x) lin[t] = srgb_to_linear(Elem<uint8_t>::load((uint8_t)t));
-        __syncthreads();
-    }
-};
+// divisions, far inside the 1e-4 tolerance).  fast_pow(), srgb_to_linear() and the LinearTable of uint8 pixels live in tissue.hpp:
+// the tissue rule of the masked forms is written there, once, on the same linear-light values.
 
 // 8-bit CODES of float32 tiles (round 4; the Macenko transform's Coded<F>, macenko.hip): a float tile made from a decoded image holds
 // float(k) / 255 for a grey level k in every element.  The statistics pass checks that for every element -- table entry k holds the
@@ -175,6 +154,15 @@ __device__ __forceinline__ void lin_to_e(const float (&lin)[V][3], const MatrixL
     }
 }
 template <typename T, int V>
+__device__ __forceinline__ void pack_to_lin(const float (&u)[3][V], const LinearTable* table, float (&lin)[V][3]) {
+#pragma unroll
+    for (int i = 0; i < V; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if constexpr (sizeof(T) == 1) lin[i][c] = table->lin[(int)u[c][i]]; else lin[i][c] = srgb_to_linear(u[c][i]);
+        }
+}
+template <typename T, int V>
 __device__ __forceinline__ void pack_to_e(const float (&u)[3][V], const LinearTable* table, const MatrixLane& fwd, float (&e)[V][3]) {
     float lin[V][3];
 #pragma unroll
@@ -184,6 +172,26 @@ __device__ __forceinline__ void pack_to_e(const float (&u)[3][V], const LinearTa
             if constexpr (sizeof(T) == 1) lin[i][c] = table->lin[(int)u[c][i]]; else lin[i][c] = srgb_to_linear(u[c][i]);
         }
     lin_to_e<V>(lin, fwd, e);
+}
+// The masked forms: which of the pack's V pixels are tissue (bit i: pixel i) -- the caller's mask bytes (one 32-bit word for a pack of
+// four) or the rule on the pack's linear-light values.  Uniform branch: a call has a mask or it has none.
+template <int V>
+__device__ __forceinline__ uint32_t tissue_bits(const tissue::Source& tis, int64_t pixel_index, const float (&lin)[V][3]) {
+    uint32_t in = 0u;
+    if (tis.mask) {
+        if constexpr (V == 4) {
+            const uint32_t word = *reinterpret_cast<const uint32_t*>(tis.mask + pixel_index);
+#pragma unroll
+            for (int i = 0; i < V; ++i) in |= ((word >> (8 * i)) & 0xFFu) ? (1u << i) : 0u;
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) in |= tis.mask[pixel_index + i] ? (1u << i) : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < V; ++i) in |= tissue::is_tissue(lin[i][0], lin[i][1], lin[i][2], tis.y_cut) ? (1u << i) : 0u;
+    }
+    return in;
 }
 // the statistics pass of a coded call: the pack's linear-light values from the code table where every element of the wave's packs is a
 // grey level, by the expression (and the tile marked) where not; the codes to the tile's planes
@@ -260,15 +268,26 @@ struct Geometry {
 
 // kPerTile: every tile is finished by ITS last arrival -- the same fixed-order reduction over the tile's own partial sums -- and its mean
 // and standard deviation go to row `tile` of mean_out / std_out (N x 3 each, required); the State is not touched.
-template <typename T, int V, bool kPerTile = false>
-__global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restrict__ images, Geometry g, State* __restrict__ st, double* __restrict__ partial, unsigned int* __restrict__ tile_arrivals, float* __restrict__ mean_out, float* __restrict__ std_out, double* __restrict__ sums_out, unsigned int call, Codes codes = Codes{nullptr, nullptr, 0u}) {
+// kMasked (the tissue forms): sums over tissue pixels only and the exact tissue count as a seventh partial; the finishing workgroup divides
+// by the count (fewer than two tissue pixels: mean and standard deviation NaN), writes it to counts_out and -- pooled form -- leaves
+// the one row in mean_out / std_out without touching the State's statistics.  Same grid, same reduction order: with every pixel
+// tissue the sums, and so the statistics, have the unmasked form's bits.
+// (the masked form's two arguments; the unmasked instantiations take an empty struct and compile as before)
+template <bool kMasked> struct MaskArgs {};
+template <> struct MaskArgs<true> {
+    tissue::Source tis;
+    unsigned long long* counts_out;      // [N] or [1]; may be null
+};
+template <typename T, int V, bool kPerTile = false, bool kMasked = false>
+__global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restrict__ images, Geometry g, State* __restrict__ st, double* __restrict__ partial, unsigned int* __restrict__ tile_arrivals, float* __restrict__ mean_out, float* __restrict__ std_out, double* __restrict__ sums_out, unsigned int call, Codes codes = Codes{nullptr, nullptr, 0u}, MaskArgs<kMasked> masked = MaskArgs<kMasked>{}) {
+    constexpr int kSums = kMasked ? reinhard::kSums + 1 : reinhard::kSums;
     const int64_t tile = blockIdx.x / g.blocks_per_tile;
     const int chunk_id = blockIdx.x % g.blocks_per_tile;
     const int64_t p_begin = (int64_t)chunk_id * g.chunk, p_end = min(p_begin + g.chunk, g.pixels);
     const T* img = images + tile * 3 * g.pixels;
     __shared__ LinearTable table;
     if constexpr (sizeof(T) == 1) table.fill();
-    constexpr bool kCodable = std::is_same<T, float>::value && V == 4;
+    constexpr bool kCodable = std::is_same<T, float>::value && V == 4 && !kMasked;      // (the masked forms run without the codes)
     __shared__ CodeLinTable code_table;
     const bool coding = kCodable && codes.epoch != 0u;      // (uniform over the launch)
     if constexpr (kCodable) {
@@ -285,7 +304,17 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
         for (int c = 0; c < 3; ++c) load_for_lab<T, V>(img + c * g.pixels + p, u[c]);
         float s[3] = {0, 0, 0}, q[3] = {0, 0, 0};
         float e[V][3];
-        if constexpr (kCodable) {
+        if constexpr (kMasked) {
+            float lin[V][3];
+            pack_to_lin<T, V>(u, &table, lin);
+            const uint32_t in = tissue_bits<V>(masked.tis, tile * g.pixels + p, lin);
+            lin_to_e<V>(lin, fwd, e);
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e[i][c] = (in >> i) & 1u ? e[i][c] : 0.0f;      // (+ 0 and fma(0, 0, q) are exact: background adds nothing)
+            acc[6] += (double)__builtin_popcount(in);
+        } else if constexpr (kCodable) {
             if (coding) pack_to_e_coding<V>(u, code_table, codes, tile, g.pixels, p, fwd, e); else pack_to_e<T, V>(u, &table, fwd, e);
         } else {
             pack_to_e<T, V>(u, &table, fwd, e);
@@ -367,11 +396,17 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
     __syncthreads();
     if (threadIdx.x < 3) {
         const int c = threadIdx.x;
-        const double n = kPerTile ? (double)g.pixels : (double)g.n_tiles * (double)g.pixels;
+        const double n = kMasked ? red[0][kSums - 1] : kPerTile ? (double)g.pixels : (double)g.n_tiles * (double)g.pixels;
         const double m = red[0][c] / n;
         const double var = n > 1.0 ? (red[0][3 + c] - red[0][c] * m) / (n - 1.0) : __longlong_as_double(0x7ff8000000000000ll);   // torch.std of one value is nan
-        const float mean = (float)((double)lab_scale(c) * m + (double)lab_offset(c)), sd = (float)((double)lab_scale(c) * sqrt(kPerTile && !(n > 1.0) ? var : fmax(var, 0.0)));      // (per tile: the nan of a one-pixel tile is kept)
-        if constexpr (kPerTile) {
+        float mean = (float)((double)lab_scale(c) * m + (double)lab_offset(c)), sd = (float)((double)lab_scale(c) * sqrt((kPerTile || kMasked) && !(n > 1.0) ? var : fmax(var, 0.0)));      // (per tile: the nan of a one-pixel tile is kept)
+        if constexpr (kMasked) {
+            if (!(n > 1.0)) mean = sd;      // fewer than two tissue pixels: no statistics (every apply pass copies such a tile through)
+            const int64_t row = kPerTile ? tile : 0;
+            mean_out[row * 3 + c] = mean;
+            std_out[row * 3 + c] = sd;
+            if (c == 0 && masked.counts_out) masked.counts_out[row] = (unsigned long long)n;
+        } else if constexpr (kPerTile) {
             mean_out[tile * 3 + c] = mean;
             std_out[tile * 3 + c] = sd;
         } else {
@@ -386,7 +421,7 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
     if constexpr (!kPerTile) {
         if (threadIdx.x == 0) {
             st->arrivals = 0;   // ready for the next call on this workspace
-            st->stats_of_call = call;
+            if constexpr (!kMasked) st->stats_of_call = call;
         }
     }
 }
@@ -395,8 +430,10 @@ __global__ __launch_bounds__(kStreamThreads) void stats_kernel(const T* __restri
 // floats each).  The pooled pass reads them from the State, the per-tile and given-statistics passes from the tile's row: one body, so
 // equal statistics give equal bits whichever entry point they came through.
 // (`before_statistics` runs where the pooled pass checks its workspace: behind the index arithmetic, in front of the first read of the statistics)
-template <typename T, int V, class Prologue>
-__device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g, const float* src_mean, const float* src_std, const float* ref_mean, const float* ref_std, Codes codes, Prologue before_statistics) {
+// kMasked (the tissue forms): a tissue pixel gets exactly the value above, a background pixel the bits of the input element; a row of
+// statistics that holds a NaN (fewer than two tissue pixels) copies the whole tile through.  No seam smoothing: a hard edge.
+template <typename T, int V, bool kMasked = false, class Prologue>
+__device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g, const float* src_mean, const float* src_std, const float* ref_mean, const float* ref_std, Codes codes, Prologue before_statistics, tissue::Source tis = tissue::Source{nullptr, 0.0f}) {
     const int64_t tile = blockIdx.x / g.blocks_per_tile;
     const int chunk_id = blockIdx.x % g.blocks_per_tile;
     const int64_t p_begin = (int64_t)chunk_id * g.chunk, p_end = min(p_begin + g.chunk, g.pixels);
@@ -406,6 +443,11 @@ __device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g,
     // lab' = (lab - mu) / (sd + 1e-8) * rs + rm per channel (:349) with lab = S e + O, then fy = (L' / 2.55 + 16) / 116,
     // fx = (a' - 128) / 500 + fy, fz = fy - (b' - 128) / 200:   f' = k e + c per channel, k = rs / (sd + 1e-8)
     float k[3], cst[3];
+    bool through = false;      // (masked forms: no statistics for this tile)
+    if constexpr (kMasked) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) through = through || !(src_std[c] == src_std[c]) || !(src_mean[c] == src_mean[c]);
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const double kc = (double)ref_std[c] / ((double)src_std[c] + 1e-8);      // (one division per channel, reused for every pixel)
@@ -417,7 +459,7 @@ __device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g,
     if constexpr (sizeof(T) == 1) table.fill();
     const MatrixLane fwd = forward_matrix(), inv = inverse_matrix();
     // a tile of grey levels (see Codes): its codes in -- four bytes per lane and plane, the linear-light values from the table -- the same float pixels out
-    constexpr bool kCodable = std::is_same<T, float>::value && V == 4;
+    constexpr bool kCodable = std::is_same<T, float>::value && V == 4 && !kMasked;
     __shared__ UnitLinearTable unit_table;
     bool coded = false;
     if constexpr (kCodable) {
@@ -442,7 +484,22 @@ __device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g,
                 have_e = true;
             }
         }
-        if (!have_e) {
+        Pack<T, V> kept[kMasked ? 3 : 1];      // (masked forms: the input elements as they are, for the background)
+        uint32_t in = 0u;
+        if constexpr (kMasked) {
+            float u[3][V];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (V == 1) kept[c].v[0] = img[c * g.pixels + p]; else kept[c] = load_pack_stream<T, V>(img + c * g.pixels + p);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    if constexpr (sizeof(T) == 1) u[c][i] = raw_value<T>(kept[c].v[i]); else u[c][i] = Elem<T>::load(kept[c].v[i]);
+                }
+            }
+            pack_to_lin<T, V>(u, &table, lin);
+            in = through ? 0u : tissue_bits<V>(tis, tile * g.pixels + p, lin);
+            lin_to_e<V>(lin, fwd, e);
+        } else if (!have_e) {
             float u[3][V];
 #pragma unroll
             for (int c = 0; c < 3; ++c) load_for_lab_last<T, V>(img + c * g.pixels + p, u[c]);
@@ -468,6 +525,9 @@ __device__ __forceinline__ void apply_chunk(const T* images, T* out, Geometry g,
                     res[c][i] = Elem<T>::store(fminf(fmaxf(back[c] * 255.0f, 0.0f), 255.0f));   // :125, :131
                 else
                     res[c][i] = Elem<T>::store(back[c]);
+                if constexpr (kMasked) {
+                    if (!((in >> i) & 1u)) res[c][i] = kept[c].v[i];
+                }
             }
         }
         // (non-temporal: the output is not read again by this library and leaves no dirty lines for the next reader to wait on --
@@ -489,6 +549,13 @@ template <typename T, int V>
 __global__ __launch_bounds__(kStreamThreads) void apply_stats_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, const float* __restrict__ src_mean, const float* __restrict__ src_std, int per_tile, const float* __restrict__ ref_mean, const float* __restrict__ ref_std, Codes codes = Codes{nullptr, nullptr, 0u}) {
     const int64_t row = per_tile ? blockIdx.x / g.blocks_per_tile : 0;
     apply_chunk<T, V>(images, out, g, src_mean + row * 3, src_std + row * 3, ref_mean, ref_std, codes, [] {});
+}
+
+// the tissue form of the apply pass with given statistics: one launch, statistics, reference and mask read on the device
+template <typename T, int V>
+__global__ __launch_bounds__(kStreamThreads) void apply_stats_masked_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, const float* __restrict__ src_mean, const float* __restrict__ src_std, int per_tile, const float* __restrict__ ref_mean, const float* __restrict__ ref_std, tissue::Source tis) {
+    const int64_t row = per_tile ? blockIdx.x / g.blocks_per_tile : 0;
+    apply_chunk<T, V, true>(images, out, g, src_mean + row * 3, src_std + row * 3, ref_mean, ref_std, Codes{nullptr, nullptr, 0u}, [] {}, tis);
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -679,6 +746,143 @@ static int run_apply_stats(const void* images, void* out, int64_t n, int64_t h, 
     return check_launch("reinhard (given statistics)");
 }
 
+// ---- tissue masks -----------------------------------------------------------------------------------------------------------------
+// The masked calls keep the per-tile calls' layout -- State, arrival counters, partial sums, then the statistics -- with SEVEN partial
+// sums per work item of the finest grid (the seventh: the tissue count); a READY workspace stays ready.
+static size_t masked_stat_offset(int64_t n, int64_t pixels) {
+    const size_t finest = (size_t)((pixels + (int64_t)kStreamThreads * 4 - 1) / ((int64_t)kStreamThreads * 4));
+    return align_up(sizeof(State), 256) + counter_bytes(n) + align_up(sizeof(double) * (kSums + 1) * finest * (size_t)n, 256);
+}
+static size_t masked_workspace_bytes(int64_t n, int64_t pixels) { return std::max(masked_stat_offset(n, pixels) + tile_stat_bytes(n), tiles_workspace_bytes(n, pixels)); }
+
+template <typename T>
+static bool masked_vector_path(const void* images, const void* out, const uint8_t* mask, int64_t pixels) {
+    return vector_path<T>(images, out, pixels) && reinterpret_cast<uintptr_t>(mask) % 4 == 0;      // (a pack's mask bytes: one 32-bit word)
+}
+
+// masked statistics (a finish per tile, or one for the batch), then with `out` the masked apply pass with those rows
+template <typename T>
+static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, tissue::Source tis, bool per_tile, float* mean_out, float* std_out, unsigned long long* counts_out, void* ws, hipStream_t stream) {
+    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    State* st = static_cast<State*>(ws);
+    unsigned int* tile_arrivals = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + align_up(sizeof(State), 256));
+    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(tile_arrivals) + counter_bytes(n));
+    if (!mean_out) {      // (both or neither: checked by the entry points)
+        mean_out = reinterpret_cast<float*>(static_cast<char*>(ws) + masked_stat_offset(n, g.pixels));
+        std_out = mean_out + 3 * n;
+    }
+    const bool vec = masked_vector_path<T>(images, out, tis.mask, g.pixels);
+    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
+    const T* in = static_cast<const T*>(images);
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st, tile_arrivals, n);
+    if (vec && per_tile)
+        hipLaunchKernelGGL((stats_kernel<T, 4, true, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
+    else if (vec)
+        hipLaunchKernelGGL((stats_kernel<T, 4, false, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
+    else if (per_tile)
+        hipLaunchKernelGGL((stats_kernel<T, 1, true, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
+    else
+        hipLaunchKernelGGL((stats_kernel<T, 1, false, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
+    if (out) {
+        if (vec)
+            hipLaunchKernelGGL((apply_stats_masked_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, per_tile ? 1 : 0, ref_mean, ref_std, tis);
+        else
+            hipLaunchKernelGGL((apply_stats_masked_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, per_tile ? 1 : 0, ref_mean, ref_std, tis);
+    }
+    return check_launch("reinhard (tissue mask)");
+}
+
+static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* rm, const float* rs, const uint8_t* mask, double threshold, int per_tile, float* mo, float* so, unsigned long long* co, void* ws, size_t ws_bytes, void* stream_ptr) {
+    if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    if (!mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
+    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    const size_t need = masked_workspace_bytes(n, h * w);
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(threshold)};
+    const bool tiles = per_tile != 0;
+    switch (dtype) {
+        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
+        case SX_F16: return run_masked<__half>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
+        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
+        case SX_F32: return run_masked<float>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
+        default: return run_masked<double>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
+    }
+}
+
+template <typename T>
+static int run_apply_stats_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* ref_mean, const float* ref_std, tissue::Source tis, hipStream_t stream) {
+    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
+    if (masked_vector_path<T>(images, out, tis.mask, g.pixels))
+        hipLaunchKernelGGL((apply_stats_masked_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, tis);
+    else
+        hipLaunchKernelGGL((apply_stats_masked_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, tis);
+    return check_launch("reinhard (given statistics, tissue mask)");
+}
+
+// sx_tissue_mask: the rule as a call of its own.  Workgroup b takes share b % blocks_per_tile of tile b / blocks_per_tile; a thread a pack
+// of four pixels (planar tiles of whole packs at aligned addresses) or single pixels; mask bytes 1 / 0 and the tile's tissue count.
+constexpr int kMaskBlocksPerTile = 64;
+template <typename T, int V>
+__global__ __launch_bounds__(kStreamThreads) void tissue_mask_kernel(const T* __restrict__ images, int64_t pixels, int channels_last, int blocks_per_tile, float y_cut, uint8_t* __restrict__ mask_out, unsigned long long* __restrict__ counts_out) {
+    __shared__ LinearTable table;
+    if constexpr (sizeof(T) == 1) table.fill();
+    const int64_t tile = blockIdx.x / blocks_per_tile;
+    const T* img = images + tile * 3 * pixels;
+    const int64_t plane = channels_last ? 1 : pixels, step = channels_last ? 3 : 1;      // element (p, c) of a tile: p * step + c * plane
+    unsigned int mine = 0;
+    for (int64_t p = ((int64_t)(blockIdx.x % blocks_per_tile) * kStreamThreads + threadIdx.x) * V; p < pixels; p += (int64_t)blocks_per_tile * kStreamThreads * V) {
+        T v[3][V];
+        if constexpr (V == 1) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][0] = img[p * step + c * plane];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const Pack<T, V> pk = *reinterpret_cast<const Pack<T, V>*>(img + c * pixels + p);      // (planar only)
+#pragma unroll
+                for (int i = 0; i < V; ++i) v[c][i] = pk.v[i];
+            }
+        }
+        uint8_t m[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            m[i] = tissue::is_tissue(tissue::linear_of<T>(v[0][i], table), tissue::linear_of<T>(v[1][i], table), tissue::linear_of<T>(v[2][i], table), y_cut) ? 1 : 0;
+            mine += m[i];
+        }
+        if (mask_out) store_pack<uint8_t, V>(mask_out + tile * pixels + p, m);
+    }
+    if (counts_out) {
+        __shared__ unsigned int parts[kStreamThreads / kWave];
+        const unsigned int total = wave_total_u32(mine);
+        if (lane_id() == 0) parts[threadIdx.x / kWave] = total;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long sum = 0;
+            for (int k = 0; k < kStreamThreads / kWave; ++k) sum += parts[k];
+            if (sum) atomicAdd(&counts_out[tile], sum);
+        }
+    }
+}
+
+template <typename T>
+static int run_tissue_mask(const void* images, int64_t n, int64_t h, int64_t w, int channels_last, float y_cut, uint8_t* mask_out, unsigned long long* counts_out, hipStream_t stream) {
+    const int64_t pixels = h * w;
+    if (counts_out && hipMemsetAsync(counts_out, 0, sizeof(unsigned long long) * (size_t)n, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    const bool vec = !channels_last && pixels % 4 == 0 && reinterpret_cast<uintptr_t>(images) % (sizeof(T) * 4) == 0 && reinterpret_cast<uintptr_t>(mask_out) % 4 == 0;
+    const int per_block = kStreamThreads * (vec ? 4 : 1);
+    const int blocks_per_tile = (int)std::min<int64_t>((pixels + per_block - 1) / per_block, kMaskBlocksPerTile);
+    const unsigned grid = (unsigned)(n * blocks_per_tile);
+    if (vec)
+        hipLaunchKernelGGL((tissue_mask_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), pixels, channels_last, blocks_per_tile, y_cut, mask_out, counts_out);
+    else
+        hipLaunchKernelGGL((tissue_mask_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), pixels, channels_last, blocks_per_tile, y_cut, mask_out, counts_out);
+    return check_launch("tissue mask");
+}
+
 }  // namespace reinhard
 }  // namespace sx
 
@@ -767,6 +971,61 @@ extern "C" int sx_reinhard_apply_stats(const void* images, void* out, int dtype,
         case SX_BF16: return reinhard::run_apply_stats<__hip_bfloat16>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
         case SX_F32: return reinhard::run_apply_stats<float>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
         case SX_F64: return reinhard::run_apply_stats<double>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// ---- tissue masks (an extension: HistomicsTK's reinhard(mask_out=), staintools' LuminosityThresholdTissueLocator) ------------------------------
+extern "C" int sx_tissue_mask(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, double luminosity_threshold, uint8_t* mask_out, unsigned long long* tile_counts_out, void* stream_ptr) {
+    if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
+    if (!mask_out && !tile_counts_out) return fail(SX_ERR_BAD_ARG, "mask_out and tile_counts_out are both null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes");
+    if (n > 0x7fffffffll / reinhard::kMaskBlocksPerTile) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
+    if (!tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const float y_cut = tissue::y_cut_of(luminosity_threshold);
+    switch (dtype) {
+        case SX_U8: return reinhard::run_tissue_mask<uint8_t>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
+        case SX_F16: return reinhard::run_tissue_mask<__half>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
+        case SX_BF16: return reinhard::run_tissue_mask<__hip_bfloat16>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
+        case SX_F32: return reinhard::run_tissue_mask<float>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
+        case SX_F64: return reinhard::run_tissue_mask<double>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+extern "C" size_t sx_reinhard_masked_workspace_bytes(int dtype, int64_t n, int64_t h, int64_t w) {
+    (void)dtype;
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    return reinhard::masked_workspace_bytes(n, h * w);
+}
+
+extern "C" int sx_reinhard_stats_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const uint8_t* mask, double luminosity_threshold, int per_tile, float* mean_out, float* std_out, unsigned long long* counts_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!mean_out || !std_out) return fail(SX_ERR_BAD_ARG, "mean_out / std_out pointer is null");
+    return reinhard::dispatch_masked(images, nullptr, dtype, n, h, w, nullptr, nullptr, mask, luminosity_threshold, per_tile, mean_out, std_out, counts_out, ws, ws_bytes, stream);
+}
+
+extern "C" int sx_reinhard_transform_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, const uint8_t* mask, double luminosity_threshold, int per_tile, float* mean_out, float* std_out, unsigned long long* counts_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!out || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "out / ref_mean / ref_std pointer is null");
+    if ((mean_out == nullptr) != (std_out == nullptr)) return fail(SX_ERR_BAD_ARG, "mean_out and std_out: both or neither");
+    return reinhard::dispatch_masked(images, out, dtype, n, h, w, ref_mean, ref_std, mask, luminosity_threshold, per_tile, mean_out, std_out, counts_out, ws, ws_bytes, stream);
+}
+
+extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
+    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
+    if (!source_mean || !source_std || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / ref_mean / ref_std pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
+    if (!mask && !tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const int per_tile = n_sources == n && n != 1 ? 1 : 0;
+    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(luminosity_threshold)};
+    switch (dtype) {
+        case SX_U8: return reinhard::run_apply_stats_masked<uint8_t>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
+        case SX_F16: return reinhard::run_apply_stats_masked<__half>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
+        case SX_BF16: return reinhard::run_apply_stats_masked<__hip_bfloat16>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
+        case SX_F32: return reinhard::run_apply_stats_masked<float>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
+        case SX_F64: return reinhard::run_apply_stats_masked<double>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }

@@ -5,6 +5,7 @@ from typing import Any, NamedTuple
 
 import torch
 
+from stainx_amd import masks
 from stainx_amd.normalizers._template import NormalizerTemplate
 
 STATISTICS_MODES = ("batch", "tile")
@@ -23,25 +24,59 @@ class Reinhard(NormalizerTemplate):
     """``statistics="batch"`` (the default, the reference's behaviour): the source mean / standard deviation are pooled over the whole
     batch.  ``statistics="tile"`` (an extension; what torchstain, tiatoolbox and HistomicsTK do with ONE image): every tile of a batch
     is normalised with its own statistics, still in two streaming launches, and its output does not depend on its neighbours in the
-    batch.  ``fit`` is the same in both modes."""
+    batch.  ``fit`` is the same in both modes.
+
+    ``mask="luminosity"`` (an extension, opt-in; HistomicsTK's ``reinhard(mask_out=)``, staintools' and tiatoolbox's tissue locator): the
+    statistics -- of the reference in ``fit``, of the source in ``transform`` / ``estimate`` -- are taken over TISSUE pixels only (a pixel
+    is tissue iff L* / 100 < ``luminosity_threshold``), and background pixels are written with the bits of the input.  Every method also
+    takes ``mask=`` for one call: an explicit uint8 / bool tensor (N, H, W) or (N, 1, H, W) on the device, non-zero = tissue, which
+    replaces the rule (also on a normaliser built with ``mask=None``).  A tile (``statistics="tile"``) or batch with fewer than two tissue
+    pixels has no statistics (NaN) and passes through unchanged.  The tissue edge is a hard edge: there is no seam smoothing and no
+    ``background=`` switch.  ``mask=None`` is the unmasked library, bit for bit."""
 
     engine = "ReinhardHIP"
     fitted_slots = ("_reference_mean", "_reference_std")      # LAB (3,) each, float32 on the device
 
-    def __init__(self, device: Any | None = None, backend: str | None = None, statistics: str = "batch"):
+    def __init__(self, device: Any | None = None, backend: str | None = None, statistics: str = "batch", mask: str | None = None,
+                 luminosity_threshold: float = masks.DEFAULT_LUMINOSITY_THRESHOLD):
         if statistics not in STATISTICS_MODES:
             raise ValueError(f"statistics must be 'batch' or 'tile', got {statistics!r}")
         self.statistics = statistics
+        self.mask = masks.check_mask_mode(mask)
+        self.luminosity_threshold = masks.check_threshold(luminosity_threshold)
         super().__init__(device=device, backend=backend)
 
     def learn(self, engine, images):
         return engine.compute_reference_mean_std(images)
 
-    def transform(self, images: Any) -> Any:
-        if self.statistics == "batch":
-            return super().transform(images)
+    def _masking(self, images: Any, mask: Any, what: str) -> tuple[bool, Any]:
+        """(masked call?, explicit mask or None), checked against the images before any GPU work."""
+        if mask is None and self.mask is None:
+            return False, None
+        n, _, h, w = self._check_images(images, what)
+        return masks.resolve(self.mask, mask, n, h, w, self.device)
+
+    def fit(self, images: Any, mask: Any = None) -> "Reinhard":
+        """``mask``: the reference's tissue (a tensor), for this call; a normaliser built with ``mask="luminosity"`` applies the rule."""
+        masked, explicit = self._masking(images, mask, "fit")
+        if not masked:
+            return super().fit(images)
+        mean, std, _ = self._get_backend_impl().masked_statistics(images, explicit, self.luminosity_threshold, per_tile=False)
+        self._reference_mean, self._reference_std = mean[0], std[0]
+        self._is_fitted = True
+        return self
+
+    def fit_transform(self, images: Any, mask: Any = None) -> Any:
+        return self.fit(images, mask=mask).transform(images, mask=mask)
+
+    def transform(self, images: Any, mask: Any = None) -> Any:
+        masked, explicit = self._masking(images, mask, "transform")
         if not self._is_fitted:
             raise ValueError("Must call fit() before transform()")
+        if masked:
+            return self._get_backend_impl().transform_masked(images, *self.arguments(), explicit, self.luminosity_threshold, per_tile=self.statistics == "tile")
+        if self.statistics == "batch":
+            return super().transform(images)
         return self._get_backend_impl().transform_tiles(images, *self.arguments())
 
     @staticmethod
@@ -51,24 +86,32 @@ class Reinhard(NormalizerTemplate):
             raise ValueError(f"Reinhard {what} expects NCHW images with C=3, got shape {shape}")
         return shape
 
-    def estimate(self, images: Any, *, pooled: bool = False) -> ColorStatistics:
+    def estimate(self, images: Any, *, pooled: bool = False, mask: Any = None) -> ColorStatistics:
         """The LAB statistics of ``images`` (NCHW), without transforming them: every tile's own, (N, 3) each, in one statistics pass --
         or with ``pooled=True`` ONE set over all pixels of the batch, (1, 3) each (what ``fit`` computes on a reference).  The
-        slide-level workflow: estimate once (a thumbnail, a sample of tissue tiles), then ``apply`` it to every tile.  Needs no ``fit()``."""
+        slide-level workflow: estimate once (a thumbnail, a sample of tissue tiles), then ``apply`` it to every tile.  Needs no ``fit()``.
+        With a mask (the normaliser's rule, or ``mask=`` for this call) the statistics are those of the tissue pixels; a tile (or pooled
+        batch) with fewer than two of them gets a row of NaN, which ``apply`` treats as "copy the tile through"."""
         self._check_images(images, "estimate")
+        masked, explicit = self._masking(images, mask, "estimate")
         engine = self._get_backend_impl()
+        if masked:
+            mean, std, _ = engine.masked_statistics(images, explicit, self.luminosity_threshold, per_tile=not pooled)
+            return ColorStatistics(mean, std)
         if pooled:
             mean, std = engine.compute_reference_mean_std(images)
             return ColorStatistics(mean.reshape(1, 3), std.reshape(1, 3))
         return ColorStatistics(*engine.tile_statistics(images))
 
-    def apply(self, images: Any, source: Any) -> Any:
+    def apply(self, images: Any, source: Any, mask: Any = None) -> Any:
         """Normalise ``images`` (NCHW) to the fitted reference with GIVEN source statistics: one kernel launch, a pixel read and a pixel
         written (include/stainx_hip.h: sx_reinhard_apply_stats).  ``source``: a ``ColorStatistics`` or a ``(mean, std)`` pair -- (3,),
-        (1, 3) (one set for the batch) or (N, 3) (row t serves tile t)."""
+        (1, 3) (one set for the batch) or (N, 3) (row t serves tile t).  With a mask (the normaliser's rule, or ``mask=`` for this call)
+        still one launch: tissue pixels get exactly the unmasked result, background pixels -- and tiles whose row holds a NaN -- are copied."""
         if not self._is_fitted:
             raise ValueError("Must call fit() before transform()")
         n = self._check_images(images, "apply")[0]
+        masked, explicit = self._masking(images, mask, "apply")
         if isinstance(source, (tuple, list)) and len(source) == 2:      # (a ColorStatistics is a tuple of two)
             mean, std = source
         else:
@@ -81,4 +124,6 @@ class Reinhard(NormalizerTemplate):
             shapes.append(1 if len(shape) == 1 else shape[0])
         if shapes[0] != shapes[1]:
             raise ValueError(f"source mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
+        if masked:
+            return self._get_backend_impl().apply_statistics_masked(images, mean, std, *self.arguments(), explicit, self.luminosity_threshold)
         return self._get_backend_impl().apply_statistics(images, mean, std, *self.arguments())

@@ -59,3 +59,16 @@ def noise_u8(shape: tuple[int, ...], seed: int) -> torch.Tensor:
     """Uniform uint8 noise, ``(rand*255).round()`` -- what the reference tests use for Reinhard / HM."""
     gen = torch.Generator().manual_seed(int(seed))
     return (torch.rand(*shape, generator=gen) * 255).round().to(torch.uint8)
+
+
+def background_stripes(tiles_u8: torch.Tensor, seed: int = 77) -> torch.Tensor:
+    """Tiles with slide background for the tissue-mask tests: tile i of N gets a left stripe of glass, ``round(235 + 20 * rand)`` in every
+    element, ``round(i / (N - 1) * W)`` pixels wide -- no background in the first tile, nothing else in the last."""
+    n, _, height, width = tiles_u8.shape
+    gen = torch.Generator().manual_seed(int(seed))
+    out = tiles_u8.clone()
+    for i in range(n):
+        stripe = round(i / max(n - 1, 1) * width)
+        glass = (235 + 20 * torch.rand(3, height, stripe, generator=gen)).round().to(torch.uint8)
+        out[i, :, :, :stripe] = glass
+    return out
