@@ -2,7 +2,8 @@
 """The hot path in five lines each: the three normalisers, the nn.Module, uint8 HWC tiles as a decoder hands them over,
 the sampled `precision="fast"` mode, how a batch is split over GPUs (one process per GPU, no collective for
 `transform`), the slide-level use: one source estimate, applied to batch after batch, per-tile statistics for Reinhard and
-histogram matching on a batch of tiles from different slides, and their tissue masks for tiles with slide background.  Run on a ROCm GPU:  python examples/normalize_tiles.py
+histogram matching on a batch of tiles from different slides, their tissue masks for tiles with slide background, and slide-level
+histogram matching (histograms added up over batches, one table, one launch per batch).  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -14,7 +15,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from stainx_amd import HistogramMatching, Macenko, Reinhard, StainNormalizerTransform, synth, tissue_mask  # noqa: E402
+from stainx_amd import HistogramMatching, HistogramStatistics, Macenko, Reinhard, StainNormalizerTransform, synth, tissue_mask  # noqa: E402
 from stainx_amd import distributed as sxd  # noqa: E402
 from stainx_amd.backends.torch_hip_backend import MacenkoHIP  # noqa: E402
 
@@ -98,6 +99,18 @@ def main() -> None:
         assert torch.equal(out[glass], edge[glass])                  # background: the bits of the input
         assert torch.equal(cls(device=dev, statistics="tile").fit(reference.to(dev)).transform(edge, mask=mask), out)      # the rule == its own mask
         print(f"[rank {rank}] {cls.__name__ + ' tissue only':27s} {tuple(out.shape)} {out.dtype}  tissue share per tile {[round(c / (256 * 256), 2) for c in counts.tolist()]}")
+
+    # 9. slide-level histogram matching: a slide arrives in many batches.  Histograms are integer counts, so those of the batches ADD UP
+    #    EXACTLY: estimate each batch with the rule, pool, build the lookup table ONCE, then every batch is one launch
+    hm = HistogramMatching(device=dev, mask="luminosity").fit(reference.to(dev))
+    slide_tiles = torch.cat([edge, tiles, more])
+    batches = list(slide_tiles.split(8))
+    slide_hist = HistogramStatistics.pool(*[hm.estimate(b, pooled=True) for b in batches])      # counts (1, 3, 256), pixels (1,): int64 on the device
+    #    (under torchrun: torch.distributed.all_reduce(slide_hist.counts), all_reduce(slide_hist.pixels) pools them over the ranks as well)
+    table = hm.lookup_tables(slide_hist)                             # (1, 3, 256) float32
+    out = torch.cat([hm.apply(b, table) for b in batches])
+    assert torch.equal(out, HistogramMatching(device=dev, statistics="batch", mask="luminosity").fit(reference.to(dev)).transform(slide_tiles))      # the slide as ONE batch, bit for bit
+    print(f"[rank {rank}] HistogramMatching slide     {tuple(out.shape)} in {len(batches)} batches  tissue pixels {slide_hist.pixels.item()}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

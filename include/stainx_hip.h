@@ -489,6 +489,45 @@ int sx_hm_transform_masked(const void* images_dev, void* out_dev, int dtype, int
                            int per_tile, uint32_t* tile_counts_out_dev, float* tile_lut_out_dev,
                            unsigned long long* tissue_counts_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- Histogram matching, slide level ----
+ * An extension: ESTIMATE the integer histograms of a source once (a thumbnail, a sample of tissue tiles, many batches), build lookup
+ * tables from GIVEN counts, APPLY given tables to every tile of the slide.  Histograms are integer counts: those of different batches,
+ * slides or ranks add up exactly (add the uint64 tensors), and a table built from added counts is bit for bit the table of the
+ * concatenated pixels.
+ *
+ * sx_hm_estimate / sx_hm_estimate_masked: the histogram pass of the calls above as a call of its own.  per_tile != 0: one set per tile
+ *   (sets = n_tiles); per_tile == 0: one set pooled over the batch (sets = 1).  The masked form counts tissue pixels only (mask_dev /
+ *   luminosity_threshold as in the tissue-mask section).
+ *   counts_out_dev  sets x 3 x 256 uint64: bin b of channel c; unmasked, the bincount of the tile's (batch's) grey levels; masked, the
+ *                   tile_counts_out of sx_hm_transform_masked with the same arguments
+ *   pixels_out_dev  sets uint64: the pixels (tissue pixels) counted per channel; may be NULL
+ *   Workspace: sx_hm_tiles_workspace_bytes() / sx_hm_masked_workspace_bytes(); any contents are accepted and the workspace is left READY,
+ *   so the calls may alternate with sx_hm_transform_ready, sx_hm_transform_tiles and sx_hm_transform_masked on one workspace.
+ * sx_hm_tables: float lookup tables from GIVEN counts: one launch of 3 x n_sets workgroups, no workspace.
+ *   counts_dev   n_sets x 3 x 256 uint64;  pixels_dev  n_sets uint64, DEVICE memory, required: the divisor of set s
+ *   lut_out_dev  n_sets x 3 x 256 floats.  The arithmetic of the LUT launch of sx_hm_transform: count / float(pixels + 1e-8), running sums
+ *   in torch.cumsum's order.  A set with pixels == 0 gets the IDENTITY table (entry b = b): a source without tissue leaves grey levels
+ *   where they are.  (The reference never meets zero pixels; its arithmetic would give a table of zeros, i.e. black.)
+ * sx_hm_apply_tables / sx_hm_apply_tables_masked: the apply pass with GIVEN tables -- ONE launch on `stream`, nothing else enqueued, no
+ *   workspace.  lut_dev: n_sources x 3 x 256 floats (0..255, what sx_hm_tables writes), DEVICE memory read by the kernel: a captured
+ *   graph replayed after new tables (or mask bytes) were written into the same buffers uses the new values.  n_sources is 1 (one
+ *   table set for the batch) or n_tiles (set t serves tile t); anything else is SX_ERR_BAD_ARG.  Every workgroup converts its source's
+ *   tables to the output element on the way into LDS.  Masked: a tissue pixel gets exactly the bits of the unmasked call, a
+ *   background pixel the bits of its input (floats are not quantised). */
+int sx_hm_estimate(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last, int per_tile,
+                   unsigned long long* counts_out_dev, unsigned long long* pixels_out_dev, void* workspace_dev,
+                   size_t workspace_bytes, void* stream);
+int sx_hm_estimate_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                          int per_tile, const uint8_t* mask_dev, double luminosity_threshold, unsigned long long* counts_out_dev,
+                          unsigned long long* pixels_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int sx_hm_tables(const unsigned long long* counts_dev, const unsigned long long* pixels_dev, int64_t n_sets, const float* ref_hist_dev,
+                 float* lut_out_dev, void* stream);
+int sx_hm_apply_tables(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                       int channels_last, const float* lut_dev, int64_t n_sources, void* stream);
+int sx_hm_apply_tables_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                              int channels_last, const float* lut_dev, int64_t n_sources, const uint8_t* mask_dev,
+                              double luminosity_threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

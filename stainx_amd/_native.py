@@ -108,6 +108,12 @@ SIGNATURES = {
     "sx_hm_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "sx_hm_fit_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
     "sx_hm_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # slide-level histogram matching: estimate histograms, tables from given counts, apply given tables
+    "sx_hm_estimate": (_int, [_vp, _int, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "sx_hm_estimate_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _int, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "sx_hm_tables": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sx_hm_apply_tables": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
+    "sx_hm_apply_tables_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _c.c_double, _vp]),
 }
 
 _lib = None

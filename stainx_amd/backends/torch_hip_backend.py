@@ -1126,6 +1126,89 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
             self.last_workspace = ws
         return (out, tables) if return_tables else out
 
+    # ---- slide level: estimate histograms, tables from given counts, apply given tables (include/stainx_hip.h: sx_hm_estimate ...) ----
+    def estimate_histograms(self, images: torch.Tensor, *, per_tile: bool, masked: bool = False, mask: torch.Tensor | None = None,
+                            luminosity_threshold: float = 0.8) -> tuple[torch.Tensor, torch.Tensor]:
+        """The histogram pass alone: ``counts`` (sets, 3, 256) int64 and ``pixels`` (sets,) int64 on the device, sets = N per tile or 1
+        pooled over the batch.  ``masked``: tissue pixels only (``mask`` (N, H, W) uint8, or None: the luminosity rule)."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        sets = n if per_tile else 1
+        counts = torch.zeros((sets, 3, 256), dtype=torch.int64, device=self.device)
+        pixels = torch.zeros((sets,), dtype=torch.int64, device=self.device)
+        if images.numel() == 0:
+            return counts, pixels
+        mask = _mask_bytes(mask, self.device) if masked else None
+        with _native.on_device(self.device):
+            if masked:
+                ws = self._masked_workspace(n, h, w)
+                rc = self._lib.sx_hm_estimate_masked(images.data_ptr(), _dtype_code(images), n, h, w, int(last), int(per_tile), None if mask is None else mask.data_ptr(),
+                                                     float(luminosity_threshold), counts.data_ptr(), pixels.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            else:
+                scratch = self.__dict__.get("_tile_scratch")
+                if scratch is None:
+                    scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
+                ws = scratch.get(int(self._lib.sx_hm_tiles_workspace_bytes(n, h, w)), self.device)
+                rc = self._lib.sx_hm_estimate(images.data_ptr(), _dtype_code(images), n, h, w, int(last), int(per_tile), counts.data_ptr(), pixels.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_estimate_masked" if masked else "sx_hm_estimate")
+        self.last_workspace = ws
+        return counts, pixels
+
+    def lookup_tables(self, counts: torch.Tensor, pixels: torch.Tensor, reference_histogram) -> torch.Tensor:
+        """(S, 3, 256) float32 lookup tables from GIVEN counts (S, 3, 256) and pixel totals (S,): one launch.  A set without pixels gets
+        the identity table."""
+        if counts.dim() != 3 or tuple(counts.shape[1:]) != (3, 256) or counts.shape[0] < 1:
+            raise ValueError(f"counts must have shape (S, 3, 256) with S >= 1, got {tuple(counts.shape)}")
+        if tuple(pixels.shape) != (counts.shape[0],):
+            raise ValueError(f"pixels must have shape (S,) = ({counts.shape[0]},), got {tuple(pixels.shape)}")
+        counts = counts.to(self.device, torch.int64).contiguous()
+        pixels = pixels.to(self.device, torch.int64).contiguous()
+        ref = self._stack_reference(reference_histogram, 3)
+        lut = torch.empty(tuple(counts.shape), dtype=torch.float32, device=self.device)
+        with _native.on_device(self.device):
+            rc = self._lib.sx_hm_tables(counts.data_ptr(), pixels.data_ptr(), int(counts.shape[0]), ref.data_ptr(), lut.data_ptr(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_tables")
+        return lut
+
+    def _given_tables(self, tables: torch.Tensor, n: int) -> torch.Tensor:
+        if tables.dim() == 2:
+            tables = tables.unsqueeze(0)
+        if tables.dim() != 3 or tuple(tables.shape[1:]) != (3, 256) or tables.shape[0] not in (1, n):
+            raise ValueError(f"tables must be (3, 256), (1, 3, 256) or ({n}, 3, 256) for {n} tiles, got shape {tuple(tables.shape)}")
+        if tables.dtype != torch.float32:
+            raise ValueError(f"tables must be float32, got {tables.dtype}")
+        return tables.to(self.device).contiguous()
+
+    def apply_tables(self, images: torch.Tensor, tables: torch.Tensor) -> torch.Tensor:
+        """Normalise with GIVEN float lookup tables, (1, 3, 256) for the whole batch or (N, 3, 256) per tile: one launch, no workspace."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        tables = self._given_tables(tables, n)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        with _native.on_device(self.device):
+            rc = self._lib.sx_hm_apply_tables(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), tables.data_ptr(), int(tables.shape[0]),
+                                              _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_apply_tables")
+        return out
+
+    def apply_tables_masked(self, images: torch.Tensor, tables: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
+        """``apply_tables`` with a tissue mask: one launch; background pixels are copied with the bits of the input."""
+        images = images.to(self.device).contiguous()
+        n, h, w, last = self._dims(images)
+        tables = self._given_tables(tables, n)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        mask = _mask_bytes(mask, self.device)
+        with _native.on_device(self.device):
+            rc = self._lib.sx_hm_apply_tables_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), tables.data_ptr(), int(tables.shape[0]),
+                                                     None if mask is None else mask.data_ptr(), float(luminosity_threshold), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_hm_apply_tables_masked")
+        return out
+
     # ---- source histogram pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_counts(self, images: torch.Tensor) -> torch.Tensor:
         images = images.to(self.device).contiguous()

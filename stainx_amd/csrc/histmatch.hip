@@ -678,6 +678,125 @@ __global__ void normalise_masked_kernel(Tables* __restrict__ tab, uint32_t* __re
     hist_out[c * kBins + t] = raw[t] / total_s;
 }
 
+// ---- slide level: the histogram pass as a call of its own, tables from GIVEN counts, the apply pass with GIVEN tables ----
+// The export step of sx_hm_estimate(_masked), behind the histogram kernels above: workgroup b widens channel b % 3 of set b / 3 to 64
+// bits, consumes the live counters and runs the ready-state check of lut_body() -- the set's counters add up to `expected` pixels
+// (kMasked: to the tissue pixels the histogram pass counted for the set).  pixels_out: that total (may be null).
+template <bool kMasked>
+__global__ __launch_bounds__(kBins) void export_counts_kernel(Tables* __restrict__ tab, uint32_t* __restrict__ live, uint32_t* __restrict__ counted, unsigned long long* __restrict__ counts_out,
+                                                              unsigned long long* __restrict__ pixels_out, double expected, const uint32_t* __restrict__ tissue_counts) {
+    const int c = blockIdx.x % 3, t = threadIdx.x;
+    const uint32_t set = blockIdx.x / 3;
+    const size_t entry = (size_t)blockIdx.x * kBins + t;      // (set * 3 + c) * 256 + t
+    __shared__ double parts[kBins / kWave];
+    const uint32_t mine = live[entry];
+    live[entry] = 0;      // consumed
+    counted[entry] = mine;
+    counts_out[entry] = mine;
+    const double wave_total = wave_sum((double)mine);      // (integers below 2^53: exact)
+    if (lane_id() == 0) parts[t / kWave] = wave_total;
+    __syncthreads();
+    if (t == 0) {
+        double total = 0.0;
+        for (int w = 0; w < kBins / kWave; ++w) total += parts[w];
+        if (total != (kMasked ? (double)tissue_counts[set] : expected)) atomicOr(&tab->status, 1u);
+        if (c == 0 && pixels_out) pixels_out[set] = (unsigned long long)total;
+    }
+}
+
+// sx_hm_tables: lut_body()'s arithmetic on GIVEN 64-bit counts and pixel totals (device memory), workgroup b: channel b % 3 of set b / 3.
+// A set without pixels gets the identity table: the reference's arithmetic would give 0 / 1e-8 = 0 in every bin, a running sum of
+// zeros and so a table of zeros -- black; it never sees such a source, and a slide without tissue is better left as it is.
+__global__ __launch_bounds__(kBins) void tables_kernel(const unsigned long long* __restrict__ counts, const unsigned long long* __restrict__ pixels, const float* __restrict__ ref_hist, float* __restrict__ lut_out) {
+    const int c = blockIdx.x % 3, t = threadIdx.x;
+    const size_t entry = (size_t)blockIdx.x * kBins + t;
+    const unsigned long long n_pixels = pixels[blockIdx.x / 3];
+    if (n_pixels == 0) {      // (uniform in the workgroup)
+        lut_out[entry] = (float)t;
+        return;
+    }
+    __shared__ float src_cdf[kBins], ref_cdf[kBins];
+    __shared__ float src_term[kBins], ref_term[kBins];
+    __shared__ float ref_denom_s;
+    __shared__ float ref_raw[kBins];
+    ref_raw[t] = ref_hist[c * kBins + t];
+    __syncthreads();
+    if (t == 64) ref_denom_s = torch_sum_256([&](int b) { return ref_raw[b]; }) + 1e-8f;      // :222-223
+    src_term[t] = (float)counts[entry] / (float)((double)n_pixels + 1e-8);                      // :235
+    __syncthreads();
+    ref_term[t] = ref_raw[t] / ref_denom_s;
+    __syncthreads();
+    if (t == 0) running_sum(src_term, src_cdf);
+    else if (t == 64) running_sum(ref_term, ref_cdf);
+    __syncthreads();
+    lut_out[entry] = lut_value(src_cdf[t], ref_cdf);
+}
+
+// sx_hm_apply_tables: apply_tiles_kernel() with GIVEN float tables.  A workgroup converts its source's 768 floats to the output element
+// in its prologue (table `tile` of `lut`, or table 0 for every tile when there is one source); no typed table in a workspace.
+template <typename T, bool kVec, bool kLast>
+__global__ __launch_bounds__(kThreads) void apply_tables_kernel(const T* __restrict__ images, T* __restrict__ out, int64_t pixels, int chunks_per_tile, const float* __restrict__ tables, int per_tile) {
+    constexpr int V = kVec ? VecOf<T>::n : 1;
+    constexpr int64_t kChunk = (int64_t)kThreads * V * kTilePacks;
+    const int64_t work = (int64_t)gridDim.x - 1 - blockIdx.x;
+    const int64_t tile = work / chunks_per_tile, chunk = work % chunks_per_tile, per_tile_elems = 3 * pixels;
+    __shared__ T lut[3][kBins];
+    const float* mine = tables + (per_tile ? tile * 3 * kBins : 0);
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) (&lut[0][0])[i] = typed_value<T>(mine[i]);
+    __syncthreads();
+    const T* src = images + tile * per_tile_elems;
+    T* dst = out + tile * per_tile_elems;
+    const int64_t begin = chunk * kChunk, end = min(begin + kChunk, per_tile_elems);      // (vector path: per_tile_elems % V == 0, so is end - begin)
+    for (int64_t e0 = (int64_t)threadIdx.x * V; e0 < end - begin; e0 += (int64_t)kThreads * V) {
+        const int64_t e = end - V - e0;
+        int c = kLast ? (int)(e % 3) : (int)(e >= pixels) + (int)(e >= 2 * pixels);      // (planar: a pack never straddles planes)
+        if constexpr (kVec) {
+            const Pack<T, V> pk = *reinterpret_cast<const Pack<T, V>*>(src + e);
+            Pack<T, V> res;
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                res.v[i] = lut[c][grey_level<T>(pk.v[i])];
+                if constexpr (kLast) c = c == 2 ? 0 : c + 1;
+            }
+            store_pack_stream<T, V>(dst + e, res.v);
+        } else {
+            dst[e] = lut[c][grey_level<T>(src[e])];
+        }
+    }
+}
+
+// sx_hm_apply_tables_masked: apply_masked_kernel() with GIVEN float tables, converted in the prologue as above
+template <typename T, bool kVec, bool kLast>
+__global__ __launch_bounds__(kThreads) void apply_tables_masked_kernel(const T* __restrict__ images, T* __restrict__ out, Layout lay, int chunks_per_tile, int per_tile, tissue::Source tis, const float* __restrict__ tables) {
+    constexpr int VP = kVec ? VecOf<T>::n : 1;
+    __shared__ T lut[sizeof(T) == 1 ? 4 : 3][kBins];      // (uint8: the fourth row is the identity, see apply_masked_kernel)
+    __shared__ LinearTable table;
+    const int64_t tile = blockIdx.x / chunks_per_tile;
+    const float* mine = tables + (per_tile ? tile * 3 * kBins : 0);
+    for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) (&lut[0][0])[i] = typed_value<T>(mine[i]);
+    if constexpr (sizeof(T) == 1) {
+        for (int i = threadIdx.x; i < kBins; i += kThreads) lut[3][i] = (T)i;
+        table.fill();
+    }
+    __syncthreads();
+    const T* src = images + tile * 3 * lay.pixels;
+    T* dst = out + tile * 3 * lay.pixels;
+    const int64_t begin = (int64_t)(blockIdx.x % chunks_per_tile) * kThreads * VP * kMaskTrips, end = min(begin + (int64_t)kThreads * VP * kMaskTrips, lay.pixels);
+    for (int64_t p = begin + (int64_t)threadIdx.x * VP; p < end; p += (int64_t)kThreads * VP) {
+        T v[3][VP];
+        load_pixels<T, VP, kLast>(src, lay.pixels, p, v);
+        const uint32_t in = pixel_bits<T, VP>(tis, tile * lay.pixels + p, v, table);
+#pragma unroll
+        for (int i = 0; i < VP; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if constexpr (sizeof(T) == 1) v[c][i] = lut[3 - (int)((in >> i) & 1u) * (3 - c)][grey_level<T>(v[c][i])];
+                else v[c][i] = (in >> i) & 1u ? lut[c][grey_level<T>(v[c][i])] : v[c][i];
+            }
+        store_pixels<T, VP, kLast>(dst, lay.pixels, p, v);
+    }
+}
+
 #ifdef SX_DIAG
 }  // namespace histmatch
 }  // namespace sx
@@ -807,7 +926,7 @@ static size_t masked_tissue_bytes(int64_t n) { return (sizeof(uint32_t) * (size_
 static size_t masked_workspace_bytes(int64_t n) { return workspace_bytes() + masked_tissue_bytes(n) + tile_area_bytes(n); }
 
 template <typename T>
-static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, tissue::Source tis, bool per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, hipStream_t stream) {
+static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, tissue::Source tis, bool per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, hipStream_t stream, unsigned long long* counts64_out = nullptr) {
     Layout lay{n, h * w, channels_last};
     Tables* tab = static_cast<Tables*>(ws);
     const int64_t sets = per_tile ? n : 1;
@@ -831,13 +950,17 @@ static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64
         hipLaunchKernelGGL(normalise_masked_kernel, dim3(3), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, tissue_counts, hist_out, tissue_out);
         return check_launch("histogram fit (tissue mask)");
     }
+    if (counts64_out) {      // sx_hm_estimate_masked: the histogram pass alone
+        hipLaunchKernelGGL((export_counts_kernel<true>), dim3((unsigned)(3 * sets)), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, counts64_out, tissue_out, 0.0, tissue_counts);
+        return check_launch("histogram estimate (tissue mask)");
+    }
     hipLaunchKernelGGL((lut_masked_kernel<T>), dim3((unsigned)(3 * sets)), dim3(kBins), 0, stream, tab, ref_hist, areas, tissue_counts, tissue_out);
     SX_HM_MASKED_LAUNCH(apply_masked_kernel, in, static_cast<T*>(out), lay, chunks_per_tile, per_tile ? 1 : 0, tis, static_cast<const T*>(areas.typed))
 #undef SX_HM_MASKED_LAUNCH
     return check_launch("histogram transform (tissue mask)");
 }
 
-static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, const uint8_t* mask, double threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, size_t ws_bytes, void* stream_ptr) {
+static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, const uint8_t* mask, double threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, size_t ws_bytes, void* stream_ptr, unsigned long long* counts64_out = nullptr) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
     if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
@@ -850,11 +973,11 @@ static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, 
     const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(threshold)};
     const bool tiles = per_tile != 0;
     switch (dtype) {
-        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
-        case SX_F16: return run_masked<__half>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
-        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
-        case SX_F32: return run_masked<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
-        default: return run_masked<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream);
+        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
+        case SX_F16: return run_masked<__half>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
+        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
+        case SX_F32: return run_masked<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
+        default: return run_masked<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
     }
 }
 
@@ -870,6 +993,101 @@ static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t
         case SX_BF16: return run<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
         case SX_F32: return run<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
         case SX_F64: return run<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// sx_hm_estimate: one clear, the histogram pass of run_tiles() (per tile) or run() (pooled), the export launch.  The workspace has the
+// per-tile layout either way; a pooled call counts into the Tables' own live counters.
+template <typename T>
+static int run_estimate(const void* images, int64_t n, int64_t h, int64_t w, int channels_last, bool per_tile, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, hipStream_t stream) {
+    Layout lay{n, h * w, channels_last};
+    Tables* tab = static_cast<Tables*>(ws);
+    const TileAreas areas = tile_areas(ws, n, nullptr, nullptr);
+    const T* in = static_cast<const T*>(images);
+    constexpr int V = VecOf<T>::n;
+    const int64_t per_tile_elems = 3 * lay.pixels, total = lay.elements();
+    const bool aligned = reinterpret_cast<uintptr_t>(images) % 16 == 0;
+    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + (per_tile ? sizeof(uint32_t) * (size_t)n * 3 * kBins : 0), stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    if (per_tile) {
+        const bool vec = aligned && (channels_last ? (per_tile_elems % V == 0) : (lay.pixels % V == 0));
+        if (vec && !channels_last) {
+            const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
+            hipLaunchKernelGGL((histogram_planar_kernel<T, true>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, areas.counts);
+        } else if (vec) {
+            const int chunks_per_tile = (int)((per_tile_elems + kLastChunk - 1) / kLastChunk);
+            hipLaunchKernelGGL((histogram_last_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, per_tile_elems, areas.counts, chunks_per_tile);
+        } else {
+            const int blocks_per_tile = (int)std::min<int64_t>((per_tile_elems + kThreads * 4 - 1) / (kThreads * 4), 64);
+            hipLaunchKernelGGL((histogram_tile_kernel<T>), dim3((unsigned)(n * blocks_per_tile)), dim3(kThreads), 0, stream, in, lay, blocks_per_tile, areas.counts);
+        }
+        hipLaunchKernelGGL((export_counts_kernel<false>), dim3((unsigned)(3 * n)), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, counts_out, pixels_out, (double)lay.pixels, nullptr);
+    } else {
+        const bool vec = aligned && (channels_last ? (total % V == 0) : (lay.pixels % V == 0));
+        if (vec && !channels_last) {
+            const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
+            hipLaunchKernelGGL((histogram_planar_kernel<T>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, &tab->counts[0][0]);
+        } else if (vec) {
+            hipLaunchKernelGGL((histogram_last_kernel<T>), dim3((unsigned)((total + kLastChunk - 1) / kLastChunk)), dim3(kThreads), 0, stream, in, total, &tab->counts[0][0]);
+        } else {
+            const int64_t per_block = (int64_t)kThreads * 4;
+            const unsigned grid = (unsigned)std::min<int64_t>((total + per_block - 1) / per_block, 256 * 8);
+            hipLaunchKernelGGL((histogram_kernel<T, false>), dim3(grid), dim3(kThreads), 0, stream, in, lay, &tab->counts[0][0]);
+        }
+        hipLaunchKernelGGL((export_counts_kernel<false>), dim3(3), dim3(kBins), 0, stream, tab, &tab->counts[0][0], &tab->counted[0][0], counts_out, pixels_out, (double)(n * lay.pixels), nullptr);
+    }
+    return check_launch("histogram estimate");
+}
+
+// sx_hm_apply_tables(_masked): ONE launch, the float tables read by the kernel
+template <typename T>
+static int run_apply_tables(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* tables, int64_t n_sources, tissue::Source tis, bool masked, hipStream_t stream) {
+    Layout lay{n, h * w, channels_last};
+    const T* in = static_cast<const T*>(images);
+    T* dst = static_cast<T*>(out);
+    constexpr int V = VecOf<T>::n;
+    const int per_tile = n_sources > 1 ? 1 : 0;      // (n_sources == n_tiles == 1: table 0 either way)
+    const bool aligned = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    if (masked) {
+        // vector path: whole packs of pixels per tile, a pack's mask bytes aligned (run_masked)
+        const bool vec = aligned && (lay.pixels % V == 0) && (reinterpret_cast<uintptr_t>(tis.mask) % V == 0);
+        const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kMaskTrips;
+        const int64_t chunks_per_tile = (lay.pixels + chunk - 1) / chunk;
+        if (n * chunks_per_tile > 0x7fffffffll) return fail(SX_ERR_BAD_ARG, "batch too large for one launch: %lld tiles of %lld pixels", (long long)n, (long long)lay.pixels);
+        const dim3 grid((unsigned)(n * chunks_per_tile));
+        if (vec && channels_last) hipLaunchKernelGGL((apply_tables_masked_kernel<T, true, true>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
+        else if (vec) hipLaunchKernelGGL((apply_tables_masked_kernel<T, true, false>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
+        else if (channels_last) hipLaunchKernelGGL((apply_tables_masked_kernel<T, false, true>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
+        else hipLaunchKernelGGL((apply_tables_masked_kernel<T, false, false>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
+        return check_launch("histogram apply with given tables (tissue mask)");
+    }
+    // vector path: a pack crosses neither a channel plane nor a tile (run_tiles)
+    const int64_t per_tile_elems = 3 * lay.pixels;
+    const bool vec = aligned && (channels_last ? (per_tile_elems % V == 0) : (lay.pixels % V == 0));
+    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kTilePacks;
+    const int64_t chunks_per_tile = (per_tile_elems + chunk - 1) / chunk;
+    if (n * chunks_per_tile > 0x7fffffffll) return fail(SX_ERR_BAD_ARG, "batch too large for one launch: %lld tiles of %lld pixels", (long long)n, (long long)lay.pixels);
+    const dim3 grid((unsigned)(n * chunks_per_tile));
+    if (vec && channels_last) hipLaunchKernelGGL((apply_tables_kernel<T, true, true>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
+    else if (vec) hipLaunchKernelGGL((apply_tables_kernel<T, true, false>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
+    else if (channels_last) hipLaunchKernelGGL((apply_tables_kernel<T, false, true>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
+    else hipLaunchKernelGGL((apply_tables_kernel<T, false, false>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
+    return check_launch("histogram apply with given tables");
+}
+
+static int dispatch_apply_tables(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* tables, int64_t n_sources, bool masked, const uint8_t* mask, double threshold, void* stream_ptr) {
+    if (!images || !out || !tables) return fail(SX_ERR_BAD_ARG, "images / out / lut pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
+    if (masked && !mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const tissue::Source tis{mask, (masked && !mask) ? tissue::y_cut_of(threshold) : 0.0f};
+    switch (dtype) {
+        case SX_U8: return run_apply_tables<uint8_t>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
+        case SX_F16: return run_apply_tables<__half>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
+        case SX_BF16: return run_apply_tables<__hip_bfloat16>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
+        case SX_F32: return run_apply_tables<float>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
+        case SX_F64: return run_apply_tables<double>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }
@@ -976,4 +1194,49 @@ extern "C" int sx_hm_fit_masked(const void* images, int dtype, int64_t n, int64_
 extern "C" int sx_hm_transform_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, const uint8_t* mask, double luminosity_threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_counts_out, void* ws, size_t ws_bytes, void* stream) {
     if (!out || !ref_hist) return fail(SX_ERR_BAD_ARG, "out / ref_hist pointer is null");
     return histmatch::dispatch_masked(images, out, dtype, n, h, w, channels_last, ref_hist, nullptr, mask, luminosity_threshold, per_tile, counts_out, lut_out, tissue_counts_out, ws, ws_bytes, stream);
+}
+
+// ---- slide level: estimate histograms, build tables from given counts, apply given tables (an extension) --------------------
+static int estimate_checks(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned long long* counts_out) {
+    if (!images || !counts_out) return fail(SX_ERR_BAD_ARG, "images / counts_out pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
+    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    return SX_OK;
+}
+
+extern "C" int sx_hm_estimate(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, int per_tile, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, size_t ws_bytes, void* stream_ptr) {
+    if (const int rc = estimate_checks(images, dtype, n, h, w, counts_out)) return rc;
+    const size_t need = histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const bool tiles = per_tile != 0;
+    switch (dtype) {
+        case SX_U8: return histmatch::run_estimate<uint8_t>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
+        case SX_F16: return histmatch::run_estimate<__half>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
+        case SX_BF16: return histmatch::run_estimate<__hip_bfloat16>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
+        case SX_F32: return histmatch::run_estimate<float>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
+        default: return histmatch::run_estimate<double>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
+    }
+}
+
+extern "C" int sx_hm_estimate_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, int per_tile, const uint8_t* mask, double luminosity_threshold, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!counts_out) return fail(SX_ERR_BAD_ARG, "counts_out pointer is null");
+    return histmatch::dispatch_masked(images, nullptr, dtype, n, h, w, channels_last, nullptr, nullptr, mask, luminosity_threshold, per_tile, nullptr, nullptr, pixels_out, ws, ws_bytes, stream, counts_out);
+}
+
+extern "C" int sx_hm_tables(const unsigned long long* counts, const unsigned long long* pixels, int64_t n_sets, const float* ref_hist, float* lut_out, void* stream) {
+    if (!counts || !pixels || !ref_hist || !lut_out) return fail(SX_ERR_BAD_ARG, "counts / pixels / ref_hist / lut_out pointer is null");
+    if (n_sets <= 0 || n_sets * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "n_sets must be positive and at most %lld, got %lld", 0x7fffffffll / 64 / 3, (long long)n_sets);
+    hipLaunchKernelGGL(histmatch::tables_kernel, dim3((unsigned)(3 * n_sets)), dim3(histmatch::kBins), 0, static_cast<hipStream_t>(stream), counts, pixels, ref_hist, lut_out);
+    return check_launch("histogram tables");
+}
+
+extern "C" int sx_hm_apply_tables(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* lut, int64_t n_sources, void* stream) {
+    return histmatch::dispatch_apply_tables(images, out, dtype, n, h, w, channels_last, lut, n_sources, false, nullptr, 0.0, stream);
+}
+
+extern "C" int sx_hm_apply_tables_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* lut, int64_t n_sources, const uint8_t* mask, double luminosity_threshold, void* stream) {
+    return histmatch::dispatch_apply_tables(images, out, dtype, n, h, w, channels_last, lut, n_sources, true, mask, luminosity_threshold, stream);
 }
