@@ -68,6 +68,8 @@ def main() -> None:
     out = norm.apply(tiles, slide)
     more = synth.he_batch(8, 256, 256, seed0=4048).to(dev)           # more tiles of the same slide: no new estimate
     out_more = norm.apply(more, slide)
+    tissue = Macenko(device=dev, mask="luminosity").fit(reference.to(dev))      # the estimate over tissue pixels only (edge tiles, thumbnails): glass is copied
+    out_tissue = tissue.apply(tiles, tissue.estimate(tiles, pooled=True))       # ... also slide-level: one masked estimate, applied under the same rule
     per_tile = norm.estimate(tiles)                                  # every tile's own estimate fed back: the transform, bit for bit
     assert torch.equal(norm.apply(tiles, per_tile), norm.transform(tiles))
     print(f"[rank {rank}] slide-level apply   {tuple(out.shape)} + {tuple(out_more.shape)} {out.dtype}  maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")

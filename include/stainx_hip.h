@@ -200,6 +200,56 @@ int sx_macenko_apply(const void* images_dev, void* out_dev, int dtype, int64_t n
                      const float* stain_matrix_dev, const float* target_max_conc_dev,
                      unsigned flags, void* stream);
 
+/* Tissue masks: the three calls above with an explicit mask -- the Macenko estimate taken over the masked-in pixels only, the masked-out
+ * pixels copied.  An extension (the reference's only notion of tissue is the optical-density filter, which protects the stain vectors
+ * but not the concentration percentiles: on a tile that is mostly glass maxC comes out too small and the tissue is over-darkened).
+ *   mask_dev   (N, H, W), one byte per pixel, non-zero = in: what sx_tissue_mask writes.  Explicit masks only: a caller that wants the
+ *              luminosity rule runs sx_tissue_mask first.  NULL is SX_ERR_BAD_ARG.
+ * The contract: masked Macenko is the reference's algorithm run on the masked-in pixels of a group (a tile, or the pooled batch) --
+ * the optical-density filter, the "fewer than 3 kept -> every pixel" fallback (per tile only; "every pixel" = every masked-in pixel), the
+ * covariance, plane, angle percentiles, stain vectors and the concentration percentiles, with nearest ranks over the masked-in set, not
+ * over H*W.  A masked-in pixel of the output gets exactly the arithmetic of the unmasked reconstruct pass with its tile's estimate.  A
+ * masked-out pixel is COPIED: its input level on the 0-255 scale (uint8: the byte; floats: x * 255 formed in float32) goes through the
+ * output path of the tissue pixels -- clamp to [0, 255], cast to the output element, the optional / 255 -- so uint8 in, uint8 out is
+ * byte-identical there.  The values under masked-out pixels do not matter at all, NaN and Inf included (every use is a select).  The
+ * edge is hard.  A group WITHOUT an estimate -- per tile: fewer than 3 masked-in pixels; pooled, where the reference's fit has no
+ * fallback: fewer than 3 pixels both masked-in and kept by the filter -- has NaN HE and maxC rows and a kept count of 0;
+ * sx_macenko_transform_masked copies such a tile through (every pixel by the background rule), sx_macenko_apply_masked copies a tile
+ * whose source row holds a NaN (as sx_reinhard_apply_stats_masked does); the unmasked sx_macenko_apply is not changed.
+ * With every mask byte set the three calls give the BITS of sx_macenko_estimate / sx_macenko_fit, of sx_macenko_transform(...,
+ * SX_MACENKO_CLASSIC) and of sx_macenko_apply (same grids, same reduction order) wherever those have an estimate.
+ * They always run the four-pass form over planar (N,3,H,W) tiles, read the float pixels in every pass (no 8-bit codes), make no host
+ * synchronisation and are capturable.  The mask is read in packs as wide as the pixel packs (16 / 8 / 4 bytes for uint8 / 16-bit /
+ * float32 pixels) where the image pointers, the tile size AND the mask pointer allow it, one byte at a time otherwise; the mask
+ * pointer's alignment is independent of the images'.
+ * Flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 (uint8 input) -- transform and apply --, SX_MACENKO_CLASSIC
+ * (a no-op, all three).  SX_MACENKO_SAMPLED, SX_MACENKO_CHANNELS_LAST and any other bit are SX_ERR_BAD_ARG before anything is enqueued,
+ * as are the argument errors of the unmasked calls.  Workspace (estimate, transform): sx_macenko_workspace_bytes_for(dtype, n_tiles,
+ * height, width, SX_MACENKO_CLASSIC) bytes -- the masked forms keep their one extra datum, the work items' masked-in counts, in an area
+ * that is free during the moments pass.
+ *
+ * sx_macenko_estimate_masked: pooled == 0: n_tiles rows, the transform's per-tile estimate over the masked-in pixels; pooled != 0: ONE
+ * row over the masked-in pixels of the whole batch (sx_macenko_fit's path, without a fallback).
+ *   he_out_dev, max_c_out_dev   rows x 6 / rows x 2 floats
+ *   kept_out_dev                rows floats: the pixels of the selection set (masked-in and kept by the filter; the masked-in pixels of a
+ *                               tile that took them all; 0 without an estimate); may be NULL
+ *   mask_counts_out_dev         rows x uint64: the masked-in pixels of the group, exact; may be NULL */
+int sx_macenko_estimate_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, const unsigned char* mask_dev, int pooled,
+                               float* he_out_dev, float* max_c_out_dev, float* kept_out_dev, unsigned long long* mask_counts_out_dev,
+                               unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* sx_macenko_transform_masked: the masked per-tile estimate followed by a masked reconstruct pass (sx_macenko_transform's other arguments). */
+int sx_macenko_transform_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, const unsigned char* mask_dev,
+                                const float* stain_matrix_dev, const float* target_max_conc_dev, unsigned flags, void* workspace_dev, size_t workspace_bytes,
+                                void* stream);
+/* sx_macenko_apply_masked: sx_macenko_apply (all its modes: n_sources 1 or n_tiles, factors or none, normalise or own basis) under a mask --
+ * ONE kernel launch on `stream`, nothing else enqueued, no workspace; source, factors, reference and mask are device memory read by the
+ * kernel.  transform_masked(x, m) has the bits of apply_masked(x, estimate_masked(x, m), m). */
+int sx_macenko_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                            const float* source_he_dev, const float* source_max_c_dev, int64_t n_sources,
+                            const float* alpha_dev, const float* beta_dev,
+                            const float* stain_matrix_dev, const float* target_max_conc_dev,
+                            const unsigned char* mask_dev, unsigned flags, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

@@ -55,6 +55,10 @@ SIGNATURES = {
     "sx_macenko_estimate": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _uint, _vp]),
     "sx_macenko_fit": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    # tissue masks for Macenko: explicit masks only (the rule: sx_tissue_mask first)
+    "sx_macenko_estimate_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_macenko_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_macenko_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

@@ -323,7 +323,7 @@ class MacenkoHIP(TorchHIPBackendBase):
 
     def apply(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None = None,
               target_max_conc: torch.Tensor | None = None, *, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None,
-              normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False) -> torch.Tensor:
+              normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False, _masking: tuple | None = None) -> torch.Tensor:
         """Normalise (and optionally jitter) with a GIVEN source basis (include/stainx_hip.h: sx_macenko_apply): one kernel launch, no
         estimate, no workspace, no host synchronisation.  ``source_he`` is (3, 2) or (1, 3, 2) -- one basis for the batch -- or
         (N, 3, 2), ``source_max_c`` (2,), (1, 2) or (N, 2) to match.  With ``stain_matrix`` / ``target_max_conc`` the tiles are
@@ -393,10 +393,112 @@ class MacenkoHIP(TorchHIPBackendBase):
             return t.data_ptr() if t is not None else None
 
         with _native.on_device(self.device):
+            if _masking is not None:      # (apply_masked: the same arguments and one more; the rule's mask is a launch of its own in front)
+                mask = self._mask_for(images, *_masking)
+                rc = self._lib.sx_macenko_apply_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, he.data_ptr(), ptr(mc), n_sources, ptr(a), ptr(b),
+                                                       ptr(sm), ptr(tmc), mask.data_ptr(), flags, _native.stream_ptr(self.device))
+                _native.check(rc, "sx_macenko_apply_masked", self._lib)
+                return out
             rc = self._lib.sx_macenko_apply(images.data_ptr(), out.data_ptr(), code, n, h, w, he.data_ptr(), ptr(mc), n_sources, ptr(a), ptr(b),
                                             ptr(sm), ptr(tmc), flags, _native.stream_ptr(self.device))
             _native.check(rc, "sx_macenko_apply", self._lib)
         return out
+
+    # ---- tissue masks (include/stainx_hip.h: sx_macenko_*_masked): the estimate over the masked-in pixels, masked-out pixels copied ----
+    def _mask_for(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
+        """The dense (N, H, W) uint8 mask a masked call reads: the explicit one, or -- ``mask=None`` -- the luminosity rule's, made by an
+        ``sx_tissue_mask`` launch in front of the call on the same stream (one extra streaming pass over the images and its bytes: the
+        library's masked Macenko calls take explicit masks only).  ``images``: dense NCHW on the device."""
+        if mask is not None:
+            mask = _mask_bytes(mask, self.device)
+            if tuple(mask.shape) != (images.shape[0], images.shape[2], images.shape[3]) or mask.dtype != torch.uint8:
+                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(images.shape[0], images.shape[2], images.shape[3])}, got {mask.dtype} {tuple(mask.shape)}")
+            return mask
+        n, _, h, w = images.shape
+        made = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        rc = self._lib.sx_tissue_mask(images.data_ptr(), _dtype_code(images), n, h, w, 0, float(luminosity_threshold), made.data_ptr(), None, _native.stream_ptr(self.device))
+        _native.check(rc, "sx_tissue_mask", self._lib)
+        return made
+
+    def _check_masked(self, images: torch.Tensor, what: str) -> torch.Tensor:
+        if self._precision == "sampled":
+            raise ValueError(f"{what} with a mask runs the exact four-pass form; precision='sampled' has no masked form")
+        images = images.to(self.device)
+        self._check_images(images, what)
+        return images.contiguous()
+
+    def estimate_masked(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, pooled: bool = False) -> dict[str, torch.Tensor]:
+        """``estimate`` over the masked-in pixels only (``mask``: (N, H, W) uint8 / bool, or None: the luminosity rule): ``he`` (rows, 3, 2),
+        ``max_c`` (rows, 2), ``tissue`` (rows,) float32 -- the pixels of the selection set -- and ``mask_pixels`` (rows,) int64, the exact
+        masked-in counts; rows = N, or 1 with ``pooled`` (one estimate over the masked-in pixels of the batch, the pooled fit's path).  A
+        group without an estimate (per tile: fewer than 3 masked-in pixels; pooled: fewer than 3 that also pass the OD filter) has NaN
+        rows and ``tissue`` 0."""
+        images = self._check_masked(images, "estimate")
+        n, _, h, w = images.shape
+        rows = 1 if pooled else n
+        out = {
+            "he": torch.empty((rows, 3, 2), dtype=torch.float32, device=self.device),
+            "max_c": torch.empty((rows, 2), dtype=torch.float32, device=self.device),
+            "tissue": torch.empty((rows,), dtype=torch.float32, device=self.device),
+            "mask_pixels": torch.empty((rows,), dtype=torch.int64, device=self.device),
+        }
+        if n == 0 or h * w == 0:
+            return out
+        code = _dtype_code(images)
+        with _native.on_device(self.device):
+            mask = self._mask_for(images, mask, luminosity_threshold)
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_estimate_masked(images.data_ptr(), code, n, h, w, mask.data_ptr(), int(pooled), out["he"].data_ptr(), out["max_c"].data_ptr(),
+                                                      out["tissue"].data_ptr(), out["mask_pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_estimate_masked", self._lib)
+        self.last_workspace = ws
+        return out
+
+    def compute_reference_stain_matrix_masked(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float = 0.8) -> tuple[torch.Tensor, torch.Tensor]:
+        """The pooled fit over the masked-in pixels of the batch: ``(HE (3,2), maxC (2,))``; NaN when fewer than 3 of them pass the OD filter."""
+        out = self.estimate_masked(images, mask, luminosity_threshold, pooled=True)
+        return out["he"][0], out["max_c"][0]
+
+    def transform_masked(self, images: torch.Tensor, stain_matrix: torch.Tensor, target_max_conc: torch.Tensor, mask: torch.Tensor | None,
+                         luminosity_threshold: float = 0.8, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, _extra_flags: int = 0) -> torch.Tensor:
+        """``transform`` with a tissue mask: the per-tile estimate over the masked-in pixels, those pixels normalised with it, the others
+        (and tiles without an estimate) copied.  Always the four-pass form: no routing, no telemetry, no host synchronisation."""
+        images = self._check_masked(images, "transform")
+        flags = int(_extra_flags) | (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0)
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        if tuple(stain_matrix.shape) != (3, 2):
+            raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+        sm = self._f32(stain_matrix)
+        tmc = self._f32(target_max_conc).flatten()
+        if tmc.numel() != 2:
+            raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        n, _, h, w = images.shape
+        code = _dtype_code(images)
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            mask = self._mask_for(images, mask, luminosity_threshold)
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_transform_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, mask.data_ptr(), sm.data_ptr(), tmc.data_ptr(), flags,
+                                                       ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_transform_masked", self._lib)
+        self.last_workspace = ws
+        return out
+
+    def apply_masked(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None,
+                     target_max_conc: torch.Tensor | None, mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, alpha: torch.Tensor | None = None,
+                     beta: torch.Tensor | None = None, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None) -> torch.Tensor:
+        """``apply`` with a tissue mask (all its modes): still one launch for an explicit mask; masked-out pixels, and tiles whose source row
+        holds a NaN, are copied."""
+        images = self._check_masked(images, "apply")
+        return self.apply(images, source_he, source_max_c, stain_matrix, target_max_conc, alpha=alpha, beta=beta, normalize_to_0_1=normalize_to_0_1,
+                          out_dtype=out_dtype, _masking=(mask, luminosity_threshold))
 
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.

@@ -556,6 +556,71 @@ struct PixelPacks {
     }
 };
 
+// ---- tissue masks (sx_macenko_*_masked) ------------------------------------------------------------------------------------------
+// The masked forms are compile-time variants (kMask) of the four passes, their per-tile stages and the apply kernel: the reference's
+// algorithm run on the masked-in pixels only.  What they take besides the unmasked arguments travels in MaskArgs, which is empty for
+// the unmasked instantiations -- those stay the code they were.  A mask is one byte per pixel, (N, H*W), non-zero = in
+// (sx_tissue_mask's layout); it is read in packs as wide as the pixel packs (V bytes: 16 / 8 / 4 for u8 / 16-bit / f32), and the
+// values under masked-out pixels are never used: every use is a select, never a product with zero (NaN and Inf included).
+template <bool kMask> struct MaskArgs {};
+template <> struct MaskArgs<true> {
+    const uint8_t* mask;
+};
+template <bool kMask> __device__ __forceinline__ const uint8_t* tile_mask(const MaskArgs<kMask>& mk, int64_t tile, int64_t pixels) {
+    if constexpr (kMask) return mk.mask + tile * pixels; else return nullptr;
+}
+// The mask bytes of the V pixels of a pack, as they arrived.
+template <int V>
+struct MaskPack {
+    static constexpr int kWords = (V + 3) / 4;
+    uint32_t w[kWords];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < kWords; ++i) w[i] = 0u;
+    }
+    __device__ __forceinline__ void load(const uint8_t* __restrict__ src) {
+        if constexpr (V == 16) {
+            const uint4 q = *reinterpret_cast<const uint4*>(src);
+            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        } else if constexpr (V == 8) {
+            const uint2 q = *reinterpret_cast<const uint2*>(src);
+            w[0] = q.x; w[1] = q.y;
+        } else if constexpr (V == 4) {
+            w[0] = *reinterpret_cast<const uint32_t*>(src);
+        } else if constexpr (V == 2) {
+            w[0] = (uint32_t)*reinterpret_cast<const uint16_t*>(src);
+        } else {
+            static_assert(V == 1, "mask packs of 16, 8, 4, 2 bytes or single bytes");
+            w[0] = (uint32_t)src[0];
+        }
+    }
+    // bit i: pixel i of the pack is in.  The V bytes shrink to one register the moment the pack is worked on (a non-zero byte -> its
+    // top bit; the four top bits of a word are gathered by one multiplication whose partial products do not collide), so that the
+    // pixel loops hold the mask in one register, not V / 4 (the uint8 moments pass has none to spare).
+    __device__ __forceinline__ uint32_t bits() const {
+        uint32_t out = 0u;
+#pragma unroll
+        for (int k = 0; k < kWords; ++k) {
+            const uint32_t top = (w[k] | ((w[k] & 0x7F7F7F7Fu) + 0x7F7F7F7Fu)) & 0x80808080u;
+            out |= (((top >> 7) * 0x01020408u) >> 24) << (4 * k);
+        }
+        return out;
+    }
+};
+__device__ __forceinline__ bool in_mask(uint32_t mask_bits, int i) { return ((mask_bits >> i) & 1u) != 0u; }
+// Where the moments pass of a masked call leaves the exact number of masked-in pixels of a work item: one word per wave at the head of
+// the work item's histogram row (free until the first bracket pass; the plane stage adds them up -- integers, any order -- before then).
+__device__ __forceinline__ uint32_t* mask_count_words(const Workspace& ws, int64_t item) { return ws.block_hist + (size_t)item * 512; }
+// What a masked-out sample pixel leaves in the sample: no optical density (the per-tile stages of a masked call skip it).
+__device__ __forceinline__ float sample_out_of_mask() { return __uint_as_float(0x7FC00000u); }
+__device__ __forceinline__ bool sample_in_mask(const float od[3]) { return od[0] == od[0]; }
+
+// The level of an input element on the 0-255 scale, from the value the reconstruct / apply passes hold for it (uint8: the grey level's
+// integer bits, load_pixels<..., kBits>; floats: the element converted to float32): what a masked-out pixel is copied from.
+template <typename T> __device__ __forceinline__ float input_level(float held) {
+    if constexpr (sizeof(T) == 1) return (float)__float_as_uint(held); else return held * 255.0f;
+}
+
 template <int W>      // W 32-bit words of codes per plane: the V = 4 W pixels of a pack
 __device__ __forceinline__ void store_codes(const Geometry& g, const Workspace& ws, int64_t tile, int64_t p, const uint32_t (&word)[3][W]) {
     static_assert(W == 1 || W == 2, "four or eight codes per plane");
@@ -1398,8 +1463,10 @@ __device__ __forceinline__ int64_t next_lane_pixel(int64_t p, int64_t lane_px) {
 
 // Moments of ALL pixels of a work item (see the end of stats_item): the same fp32 runs / fp64 sums as the kept set.  Not
 // (ordinary tiles never run it).
-template <typename T, int V, int TPB, bool kInter>
-__device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img, int64_t pixels, int64_t p_begin, int64_t p_end, double* __restrict__ dst, StatsScratch<TPB>* sh) {
+// kMask: the moments of all MASKED-IN pixels (`msk`: the tile's mask bytes); a masked-out pixel adds exact zeros.
+template <typename T, int V, int TPB, bool kInter, bool kMask = false>
+__device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img, int64_t pixels, int64_t p_begin, int64_t p_end, double* __restrict__ dst, StatsScratch<TPB>* sh,
+                                                      const uint8_t* __restrict__ msk = nullptr) {
     constexpr int kShortRun = 32 / V > 0 ? 32 / V : 1;
     const int64_t lane_px = lane_pixels<T, V>(pixels);
     double acc[kPartial];
@@ -1413,12 +1480,25 @@ __device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img,
         for (int64_t p = run + (int64_t)threadIdx.x * lane_px; p < run_end; p = next_lane_pixel<V, TPB>(p, lane_px)) {
             float u[3][V];
             load_pixels<T, V, kInter>(img, pixels, p, u);
+            uint32_t in_bits = 0u;
+            if constexpr (kMask) {
+                MaskPack<V> mp;
+                mp.load(msk + p);
+                in_bits = mp.bits();
+            }
 #pragma unroll
             for (int i = 0; i < V; ++i) {
                 float od[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) od[c] = optical_density<T>(u[c][i]);
-                m[0] += 1.0f;
+                if constexpr (kMask) {
+                    const bool in = in_mask(in_bits, i);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) od[c] = in ? od[c] : 0.0f;
+                    m[0] += in ? 1.0f : 0.0f;
+                } else {
+                    m[0] += 1.0f;
+                }
                 m[1] += od[0];
                 m[2] += od[1];
                 m[3] += od[2];
@@ -1455,8 +1535,8 @@ __device__ __forceinline__ void stats_item_all_pixels(const T* __restrict__ img,
 // a batch of real tiles.  A witness settles it: every thread looks at ONE pixel of the tile (TPB pixels spread evenly over it);
 // three kept ones among them prove that the tile has three kept pixels -- the same predicate on the same optical density, so there
 // is no false proof; a tile whose tissue the witnesses miss just does the sweep as before.  Workgroup-uniform result.
-template <typename T, int TPB, bool kInter>
-__device__ __forceinline__ bool tile_has_three_kept_witnesses(const T* __restrict__ img, int64_t pixels) {
+template <typename T, int TPB, bool kInter, bool kMask = false>
+__device__ __forceinline__ bool tile_has_three_kept_witnesses(const T* __restrict__ img, int64_t pixels, const uint8_t* __restrict__ msk = nullptr) {
     const int64_t step = pixels / TPB > 0 ? pixels / TPB : 1;
     const int64_t p = (int64_t)threadIdx.x * step + (int64_t)(((uint32_t)threadIdx.x * 0x9E3779B1u) >> 16) % step;
     int kept = 0;
@@ -1465,6 +1545,7 @@ __device__ __forceinline__ bool tile_has_three_kept_witnesses(const T* __restric
         load_pixels<T, 1, kInter>(img, pixels, p, v);
         const float od[3] = {optical_density<T>(v[0][0]), optical_density<T>(v[1][0]), optical_density<T>(v[2][0])};
         kept = od_selected(od, false) ? 1 : 0;
+        if constexpr (kMask) kept = msk[p] != 0 ? kept : 0;      // (a masked call: a witness is a kept pixel under the mask)
     }
     return __syncthreads_count(kept) >= 3;
 }
@@ -1472,9 +1553,15 @@ __device__ __forceinline__ bool tile_has_three_kept_witnesses(const T* __restric
 // kEmit (Codable instantiations, g.code_epoch != 0): the pass also leaves the tile as 8-bit codes (see Coded<F>) -- a pack's elements
 // are looked up in the code table; where all of them are grey levels (the table entry has the element's bits) their optical density
 // comes from the table too, else (wave-uniform branch) from the expression as without kEmit and the tile is marked.
-template <typename T, int V, int TPB, bool kInter, bool kEmit = false>
+// kMask (sx_macenko_*_masked): the kept set is the masked-in pixels that pass the OD filter, the fallback's set the masked-in pixels;
+// a masked-out pixel enters every sum as an exact zero (selected, so that a NaN under it stays out), a masked-out sample pixel leaves
+// no optical density in the sample, and the work item's exact count of masked-in pixels goes to mask_count_words().
+template <typename T, int V, int TPB, bool kInter, bool kEmit = false, bool kMask = false>
 __device__ void stats_item(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id, int64_t item, StatsScratch<TPB>* sh, const LevelTables<T>& tb,
-                           const CodeTable<T, 4>* __restrict__ ct = nullptr) {
+                           const CodeTable<T, 4>* __restrict__ ct = nullptr, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
+    static_assert(!(kMask && kEmit), "the masked forms run without the codes");
+    const uint8_t* msk = tile_mask(mk, tile, g.pixels);
+    uint32_t n_in = 0;      // (kMask) masked-in pixels this thread has seen
     const int64_t p_begin = (int64_t)chunk_id * g.chunk;
     const int64_t p_end = min(p_begin + (int64_t)g.chunk, g.pixels);
     const T* img = images + tile * 3 * g.pixels;
@@ -1504,7 +1591,12 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
     constexpr bool kAhead = sizeof(T) == 2 && !kEmit && V > 1;
     PixelPacks<T, V, kInter> ahead;
     ahead.clear();
-    if (kAhead && p_begin + (int64_t)threadIdx.x * V < p_end) ahead.load(img, g.pixels, p_begin + (int64_t)threadIdx.x * V);
+    MaskPack<V> mask_ahead;
+    mask_ahead.clear();
+    if (kAhead && p_begin + (int64_t)threadIdx.x * V < p_end) {
+        ahead.load(img, g.pixels, p_begin + (int64_t)threadIdx.x * V);
+        if constexpr (kMask) mask_ahead.load(msk + p_begin + (int64_t)threadIdx.x * V);
+    }
     for (int64_t run = p_begin; run < p_end; run += (int64_t)TPB * V * kShortRun) {
         float m[kPartial];
 #pragma unroll
@@ -1512,25 +1604,42 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
         const int64_t run_end = min(run + (int64_t)TPB * V * kShortRun, p_end);
         for (int64_t p = run + (int64_t)threadIdx.x * lane_px; p < run_end; p = next_lane_pixel<V, TPB>(p, lane_px)) {
             PixelPacks<T, V, kInter> u;
+            MaskPack<V> mp;
             if constexpr (kAhead) {
                 u = ahead;
-                if (p + (int64_t)TPB * V < p_end) ahead.load(img, g.pixels, p + (int64_t)TPB * V);      // (the thread's next pack, in this run or the next)
+                if constexpr (kMask) mp = mask_ahead;
+                if (p + (int64_t)TPB * V < p_end) {      // (the thread's next pack, in this run or the next)
+                    ahead.load(img, g.pixels, p + (int64_t)TPB * V);
+                    if constexpr (kMask) mask_ahead.load(msk + p + (int64_t)TPB * V);
+                }
             } else {
                 u.load(img, g.pixels, p);
+                if constexpr (kMask) mp.load(msk + p);
+            }
+            uint32_t in_bits = 0u;
+            if constexpr (kMask) {
+                in_bits = mp.bits();
+                n_in += (uint32_t)__popc(in_bits);
             }
             // sample j sits in the cell [j*stride, (j+1)*stride) of its group at a hashed offset (a fixed offset would alias
             // with the image width: stride 1024 on a 2048-wide tile samples two columns only); tested once per pack
             const uint32_t gpos = group_offset + (uint32_t)p, j = gpos >> shift, off = sample_offset_in(j, shift, group_count);
             if (by_pack && (((gpos & mask) ^ off) >> kLog2V) == 0u && j < sample_count) {
                 float raw[3] = {u.value(0, 0), u.value(1, 0), u.value(2, 0)};
+                bool raw_in = true;
+                if constexpr (kMask) raw_in = in_mask(in_bits, 0);
 #pragma unroll
                 for (int i = 1; i < V; ++i)
                     if ((int)(off & (uint32_t)(V - 1)) == i) {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) raw[c] = u.value(c, i);
+                        if constexpr (kMask) raw_in = in_mask(in_bits, i);
                     }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) put(&sample_out[c * kSample + j], od_of<T>(raw[c], tb));
+                for (int c = 0; c < 3; ++c) {
+                    if constexpr (kMask) put(&sample_out[c * kSample + j], raw_in ? od_of<T>(raw[c], tb) : sample_out_of_mask());
+                    else put(&sample_out[c * kSample + j], od_of<T>(raw[c], tb));
+                }
             }
             float od_quad[4][3];
             if constexpr (kEmit) {
@@ -1550,8 +1659,16 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
                     const uint32_t pos = gpos + (uint32_t)i, jj = pos >> shift;
                     if ((pos & mask) == sample_offset_in(jj, shift, group_count) && jj < sample_count) {
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) put(&sample_out[c * kSample + jj], od[c]);
+                        for (int c = 0; c < 3; ++c) {
+                            if constexpr (kMask) put(&sample_out[c * kSample + jj], in_mask(in_bits, i) ? od[c] : sample_out_of_mask());
+                            else put(&sample_out[c * kSample + jj], od[c]);
+                        }
                     }
+                }
+                if constexpr (kMask) {      // (a masked-out pixel: zeros, which the filter drops and every sum takes as an exact +0)
+                    const bool in = in_mask(in_bits, i);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) od[c] = in ? od[c] : 0.0f;
                 }
                 const float keep = od_selected(od, false) ? 1.0f : 0.0f;
                 const float k0 = keep * od[0], k1 = keep * od[1], k2 = keep * od[2];
@@ -1584,6 +1701,10 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
         for (int w = 0; w < TPB / kWave; ++w) s += sh->red[w][threadIdx.x];
         put(&ws.partial[item * kPartial + threadIdx.x], s);
     }
+    if constexpr (kMask) {
+        const uint32_t wave_in = wave_total_u32(n_in);      // (every lane is here)
+        if (lane_id() == 0) put(&mask_count_words(ws, item)[wave], wave_in);
+    }
     // A work item none of whose pixels pass the OD filter also leaves the moments of ALL its pixels: a tile with fewer than 3
     // kept pixels takes every pixel (torch_backend.py:409-410), and then each of its work items is such a one -- the plane
     // stage adds the partial sums up instead of streaming the whole tile through one workgroup (0.1 ms per blank tile).
@@ -1592,7 +1713,7 @@ __device__ void stats_item(const T* __restrict__ images, const Geometry& g, cons
 #pragma unroll
     for (int w = 0; w < TPB / kWave; ++w) kept += sh->red[w][0];      // workgroup-uniform
     if (__builtin_expect(kept < 3.0, 0)) {
-        if (!tile_has_three_kept_witnesses<T, TPB, kInter>(img, g.pixels)) stats_item_all_pixels<T, V, TPB, kInter>(img, g.pixels, p_begin, p_end, ws.partial_all + item * kPartial, sh);
+        if (!tile_has_three_kept_witnesses<T, TPB, kInter, kMask>(img, g.pixels, msk)) stats_item_all_pixels<T, V, TPB, kInter, kMask>(img, g.pixels, p_begin, p_end, ws.partial_all + item * kPartial, sh, msk);
     }
 }
 
@@ -1641,8 +1762,11 @@ __device__ __forceinline__ void flush_queue(const uint32_t* queue, uint32_t n, u
     }
 }
 
-template <typename T, int V, bool kConc, int TPB, bool kInter>
-__device__ void bracket_item(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id, int64_t item, BracketScratch<TPB>* sh, const LevelTables<T>& tb) {
+// kMask: a masked-out pixel is in neither stage's set -- in the concentration stage, whose threshold is -inf, the mask is the only filter.
+template <typename T, int V, bool kConc, int TPB, bool kInter, bool kMask = false>
+__device__ void bracket_item(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id, int64_t item, BracketScratch<TPB>* sh, const LevelTables<T>& tb,
+                             const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
+    const uint8_t* msk = tile_mask(mk, tile, g.pixels);
     const int group = g.pooled ? 0 : (int)tile;
     GroupState& st = ws.state[group];
     constexpr int s0 = kConc ? 2 : 0;
@@ -1659,7 +1783,12 @@ __device__ void bracket_item(const T* __restrict__ images, const Geometry& g, co
     const int64_t mine = (int64_t)lane_id() * V;
     PixelPacks<T, V, kInter> next;
     next.clear();
-    if (base + mine < p_end) next.load(img, g.pixels, base + mine);
+    MaskPack<V> mask_next;
+    mask_next.clear();
+    if (base + mine < p_end) {
+        next.load(img, g.pixels, base + mine);
+        if constexpr (kMask) mask_next.load(msk + base + mine);
+    }
     StageRecord rec;
     load_record(&st.rec[kConc ? 1 : 0], rec);
     for (int i = threadIdx.x; i < 512; i += TPB) (&sh->hist[0][0])[i] = 0;
@@ -1681,8 +1810,13 @@ __device__ void bracket_item(const T* __restrict__ images, const Geometry& g, co
     for (; base < p_end; base += (int64_t)TPB * V) {
         const uint64_t live_mask = __builtin_amdgcn_ballot_w64(base + mine < p_end);
         const PixelPacks<T, V, kInter> u = next;
+        uint32_t in_bits = 0u;
+        if constexpr (kMask) in_bits = mask_next.bits();
         const int64_t p_next = base + (int64_t)TPB * V + mine;
-        if (p_next < p_end) next.load(img, g.pixels, p_next);
+        if (p_next < p_end) {
+            next.load(img, g.pixels, p_next);
+            if constexpr (kMask) mask_next.load(msk + p_next);
+        }
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             float od[3];
@@ -1700,7 +1834,8 @@ __device__ void bracket_item(const T* __restrict__ images, const Geometry& g, co
             // five comparisons per pixel; everything else happens on their lane masks with scalar instructions (the
             // ballot of a bare comparison is the comparison's own result register, inverse_ballot makes a mask the
             // branch condition again -- no 0/1 values in vector registers)
-            const uint64_t valid = __builtin_amdgcn_ballot_w64(fminf(od[0], fminf(od[1], od[2])) >= threshold) & live_mask;     // torch_backend.py:404-405
+            uint64_t valid = __builtin_amdgcn_ballot_w64(fminf(od[0], fminf(od[1], od[2])) >= threshold) & live_mask;     // torch_backend.py:404-405
+            if constexpr (kMask) valid &= __builtin_amdgcn_ballot_w64(in_mask(in_bits, i));
             const uint64_t lt_a = __builtin_amdgcn_ballot_w64(key_a < lo_a), le_a = __builtin_amdgcn_ballot_w64(key_a <= hi_a);
             const uint64_t lt_b = __builtin_amdgcn_ballot_w64(key_b < lo_b), le_b = __builtin_amdgcn_ballot_w64(key_b <= hi_b);
             below_a += (uint32_t)__popcll(valid & lt_a);
@@ -1780,9 +1915,28 @@ __device__ void bracket_item(const T* __restrict__ images, const Geometry& g, co
 // ------------------------------------------------------------------------------------------------
 // kAug (sx_macenko_augment): the tile's own factors C' = a C + b folded in as well, and -- g.own_basis -- the tile rebuilt with its own
 // HE_source; a separate instantiation, so that the transform's kernels are the same code as without it.
-template <typename T, typename O, int V, bool kUnit, int TPB, bool kInter, bool kAug = false>
+// kMask (sx_macenko_transform_masked): a masked-in pixel gets exactly the arithmetic below; a masked-out pixel -- and every pixel of a tile
+// without an estimate (a NaN in its HE_source or maxC) -- is COPIED: its input level on the 0-255 scale (uint8: the byte; floats: x * 255 in
+// float32) takes the place of the reconstructed value in front of the clamp, and so goes through the same clamp, cast and optional / 255.
+template <typename T, typename O, int V, bool kUnit, int TPB, bool kInter, bool kAug = false, bool kMask = false>
 __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O* __restrict__ out, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id,
-                                 const float* __restrict__ stain_matrix, const LevelTables<T>& tb, uint4* __restrict__ stage = nullptr, const float* __restrict__ given = nullptr) {
+                                 const float* __restrict__ stain_matrix, const LevelTables<T>& tb, uint4* __restrict__ stage = nullptr, const float* __restrict__ given = nullptr,
+                                 const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
+    const uint8_t* msk = tile_mask(mk, tile, g.pixels);
+    bool through = false;      // (kMask, uniform) the tile has no estimate: every pixel is copied
+    if constexpr (kMask) {
+        const GroupState& own = ws.state[tile];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const float v = get(&own.he[i]);
+            through = through || v != v;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float v = get(&own.max_c[i]);
+            through = through || v != v;
+        }
+    }
     const int64_t chunk = g.recon_chunk ? g.recon_chunk : (g.fine_chunk ? g.fine_chunk : g.chunk);
     const int64_t p_begin = (int64_t)chunk_id * chunk;
     const int64_t p_end = min(p_begin + chunk, g.pixels);
@@ -1871,6 +2025,12 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
         } else {
             load_pixels<T, V, kInter, sizeof(T) == 1>(img, g.pixels, p, u);
         }
+        uint32_t in_bits = 0u;
+        if constexpr (kMask) {
+            MaskPack<V> mp;
+            mp.load(msk + p);
+            in_bits = through ? 0u : mp.bits();
+        }
         O res[3][V];
 #pragma unroll
         for (int i = 0; i < V; ++i) {
@@ -1881,6 +2041,7 @@ __device__ __forceinline__ void reconstruct_item(const T* __restrict__ images, O
             for (int c = 0; c < 3; ++c) {
                 const float x = fmaf(m[c][2], l[2], fmaf(m[c][1], l[1], fmaf(m[c][0], l[0], k[c])));
                 float rgb = __builtin_amdgcn_exp2f(x);                                // bare v_exp_f32: a result below 2^-126 is 0 either way after the cast
+                if constexpr (kMask) rgb = in_mask(in_bits, i) ? rgb : input_level<T>(u[c][i]);
                 rgb = fminf(fmaxf(rgb, 0.0f), 255.0f);                                // :459, :128
                 using S = typename Sem<T>::type;      // (the output rules follow what the element means: a coded float tile is a float tile)
                 if constexpr (kUnit) {
@@ -2099,9 +2260,15 @@ __device__ void all_pixel_moments(const Geometry& g, const Workspace& ws, int gr
     __syncthreads();
 }
 
-template <typename T, bool kFast = false>
+// kMask: the all-pixel set is the group's masked-in pixels -- its size the sum of the work items' exact counts, not the group's pixels --
+// and masked-out sample pixels stay out of the bracket guess.  A group WITHOUT an estimate (per tile: fewer than 3 masked-in pixels;
+// pooled, where the reference has no fallback: fewer than 3 that also pass the OD filter) is marked kNoEstimate in its use_all words:
+// the streaming passes then collect nothing for it, the later stages leave NaN rows, its selection count is 0.
+constexpr int kNoEstimate = 2;      // bit of GroupState::use_all / StageRecord::use_all (masked calls only)
+template <typename T, bool kFast = false, bool kMask = false>
 __device__ void plane_stage(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int group, int allow_fallback, TileScratch* sh, const double* __restrict__ given_moments = nullptr,
                             const float* __restrict__ target_max_conc = nullptr) {
+    static_assert(!(kFast && kMask), "the masked forms take the exact percentiles");
     GroupState& st = ws.state[group];
     SX_STAMP(st, 0);
     reset_scratch(sh);
@@ -2128,8 +2295,19 @@ __device__ void plane_stage(const T* __restrict__ images, const Geometry& g, con
                 for (int b = 0; b < live; ++b) running += sh->stage[b][threadIdx.x];
         }
         if (threadIdx.x < kPartial) sh->mom[threadIdx.x] = running;
-        const GroupPixels gp = group_pixels(g, group);
-        if (threadIdx.x == kPartial) sh->mom[kPartial] = (double)gp.count;       // all-pixel set: the count is known,
+        if constexpr (kMask) {      // the masked-in pixels of the group, counted by the moments pass (one word per wave of a work item)
+            if (threadIdx.x == 0) sh->radix_rank = 0ull;
+            __syncthreads();
+            uint32_t part = 0;      // (a call holds fewer than 2^32 pixels)
+            for (int64_t i = threadIdx.x; i < nblk * (kStreamThreads / kWave); i += blockDim.x) part += get(&mask_count_words(ws, first + i / (kStreamThreads / kWave))[i % (kStreamThreads / kWave)]);
+            part = wave_total_u32(part);
+            if (lane_id() == 0 && part) atomicAdd(&sh->radix_rank, (unsigned long long)part);
+            __syncthreads();
+            if (threadIdx.x == kPartial) sh->mom[kPartial] = (double)sh->radix_rank;
+        } else {
+            const GroupPixels gp = group_pixels(g, group);
+            if (threadIdx.x == kPartial) sh->mom[kPartial] = (double)gp.count;       // all-pixel set: the count is known,
+        }
         if (threadIdx.x > kPartial && threadIdx.x < kMoments) sh->mom[threadIdx.x] = 0.0;   // the sums only matter in the fallback below
     }
     __syncthreads();
@@ -2149,6 +2327,12 @@ __device__ void plane_stage(const T* __restrict__ images, const Geometry& g, con
             put(&st.vecs[i], vecs[i]);
         }
         sh->flag = use_all ? 1 : 0;
+        if constexpr (kMask) {
+            if (allow_fallback ? sh->mom[kPartial] < 3.0 : sh->mom[0] < 3.0) {
+                sh->flag |= kNoEstimate;
+                n_sel = 0ull;
+            }
+        }
         sh->n_sel = n_sel;
 #pragma unroll
         for (int k = 0; k < kMoments; ++k) put(&st.mom[k], sh->mom[k]);
@@ -2179,18 +2363,37 @@ __device__ void plane_stage(const T* __restrict__ images, const Geometry& g, con
     }
     __syncthreads();
     SX_STAMP(st, 2);
-    const bool use_all = sh->flag != 0;
+    const bool use_all = kMask ? (sh->flag & 1) != 0 : sh->flag != 0;
     const unsigned long long n_sel = sh->n_sel;
     float v[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) v[i] = sh->coef[i];
+    if constexpr (kMask) {
+        if (sh->flag & kNoEstimate) {      // (uniform) an empty bracket: the angle pass collects nothing for this group
+            if (threadIdx.x == 0) {
+                StageRecord* rec = &st.rec[0];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) put(&rec->coef[i], 0.0f);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    put(&st.rank[s], 0ull);
+                    put(&rec->lo[s], 0xFFFFFFFFu);
+                    put(&rec->hi[s], 0u);
+                    put(&rec->bin_origin[s], 0.0);
+                    put(&rec->bin_scale[s], 0.0);
+                }
+                put(&rec->use_all, sh->flag);
+            }
+            return;
+        }
+    }
     // angle keys of the selected sample pixels
     uint32_t key[1][kKeys];
 #pragma unroll
     for (int i = 0; i < kKeys; ++i) {
         const int j = i * kGroupThreads + (int)threadIdx.x;
         uint32_t k = 0xFFFFFFFFu;
-        if (j < g.sample_count && od_selected(sod[i], use_all)) k = angle_key(sod[i], v);
+        if (j < g.sample_count && (!kMask || sample_in_mask(sod[i])) && od_selected(sod[i], use_all)) k = angle_key(sod[i], v);
         key[0][i] = k;
         sh->keys[0][j] = k;
     }
@@ -2276,14 +2479,17 @@ __device__ void plane_stage(const T* __restrict__ images, const Geometry& g, con
 // ------------------------------------------------------------------------------------------------
 // exact order statistics of the two slots of a stage from what the streaming stage left behind
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool kThrough = false, class Scratch>
+template <typename T, bool kThrough = false, bool kMask = false, class Scratch>
 __device__ uint32_t select_whole_group(const T* __restrict__ images, const Geometry& g, int group, int slot, unsigned long long rank, const float* coef, bool use_all,
-                                       Scratch* sh, uint32_t* __restrict__ keep = nullptr) {
+                                       Scratch* sh, uint32_t* __restrict__ keep = nullptr, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
     const GroupPixels gp = group_pixels(g, group);
     return radix_select_stream<kThrough>((unsigned long long)gp.count, rank,
                                [&](unsigned long long i, uint32_t& k) {
                                    int64_t tile, p;
                                    gp.locate((int64_t)i, tile, p);
+                                   if constexpr (kMask) {      // (the walk is over the group's pixels; the set is the masked-in ones)
+                                       if (tile_mask(mk, tile, g.pixels)[p] == 0) return false;
+                                   }
                                    float od[3];
                                    load_od_scalar<T>(images, g, tile, p, od);
                                    if (!od_selected(od, use_all)) return false;
@@ -2347,9 +2553,9 @@ __device__ __forceinline__ void prefetch_pair(PairPrefetch& pf, const Geometry& 
 // rank, the candidates of that bin (~n/256 keys) are listed and rank-counted.  Anything unusual -- bracket missed
 // or overflowed, a crowded bin -- goes to the radix paths (over the candidates, or recomputing every key of the
 // group from the pixels).  Needs reset_scratch() before it.
-template <typename T>
+template <typename T, bool kMask = false>
 __device__ void resolve_pair(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int group, int first_slot, const float* coef, bool use_all,
-                             const PairPrefetch& pf, uint32_t (&key_out)[2], TileScratch* sh) {
+                             const PairPrefetch& pf, uint32_t (&key_out)[2], TileScratch* sh, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
     GroupState& st = ws.state[group];
     bool ok[2], tie[2];
     uint32_t want_in[2];
@@ -2444,7 +2650,7 @@ __device__ void resolve_pair(const T* __restrict__ images, const Geometry& g, co
             key_out[j] = radix_select_stream((unsigned long long)pf.ncand[j], (unsigned long long)want_in[j], [cand](unsigned long long i, uint32_t& k) { k = get(&cand[i]); return true; }, sh);
         } else {                 // the bracket did not hold: recompute every key of the group
             if (threadIdx.x == 0) atomicOr(&st.fell_back, 1u << slot);
-            key_out[j] = select_whole_group<T>(images, g, group, slot, pf.rank[j], coef, use_all, sh);
+            key_out[j] = select_whole_group<T, false, kMask>(images, g, group, slot, pf.rank[j], coef, use_all, sh, nullptr, mk);
         }
     }
 }
@@ -2583,9 +2789,9 @@ __global__ __launch_bounds__(kGroupThreads) void pool_gather_kernel(Geometry g, 
 // (3) in the group stage: the compact list (the candidates of ONE value-linear bin over all tiles: hundreds to a few
 // thousand keys, with heavy ties when the tiles come from 8-bit data) goes to LDS and four byte-wise radix rounds over
 // it give the wanted element; a list that does not fit LDS is read from memory in every round.
-template <typename T>
+template <typename T, bool kMask = false>
 __device__ void resolve_pair_spread(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int first_slot, const float* coef, bool use_all,
-                                    uint32_t (&key_out)[2], TileScratch* sh) {
+                                    uint32_t (&key_out)[2], TileScratch* sh, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
     GroupState& st = ws.state[0];
     const PoolState* pool = ws.pool;
     __syncthreads();
@@ -2610,7 +2816,7 @@ __device__ void resolve_pair_spread(const T* __restrict__ images, const Geometry
             key_out[j] = 0u;
         } else {      // bracket missed or a buffer overflowed: recompute every key of the group (exact, slow)
             if (threadIdx.x == 0) atomicOr(&st.fell_back, 1u << slot);
-            key_out[j] = select_whole_group<T>(images, g, 0, slot, get(&st.rank[slot]), coef, use_all, sh);
+            key_out[j] = select_whole_group<T, false, kMask>(images, g, 0, slot, get(&st.rank[slot]), coef, use_all, sh, nullptr, mk);
         }
     }
     __syncthreads();
@@ -2619,8 +2825,9 @@ __device__ void resolve_pair_spread(const T* __restrict__ images, const Geometry
 // ------------------------------------------------------------------------------------------------
 // per-tile stage B ("stain"): angle percentiles -> HE_source -> pseudo-inverse; concentration brackets
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool kSpread = false>
-__device__ void stain_stage(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int group, TileScratch* sh) {
+// kMask: the concentration stage's set is the group's masked-in pixels (its size: the plane stage's count in mom[kPartial]).
+template <typename T, bool kSpread = false, bool kMask = false>
+__device__ void stain_stage(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int group, TileScratch* sh, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
     GroupState& st = ws.state[group];
     const GroupPixels gp = group_pixels(g, group);
     SX_STAMP(st, 6);
@@ -2632,14 +2839,48 @@ __device__ void stain_stage(const T* __restrict__ images, const Geometry& g, con
     float vecs[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) vecs[i] = get(&st.rec[0].coef[i]);
-    const bool use_all = get(&st.rec[0].use_all) != 0;
+    const int use_all_word = get(&st.rec[0].use_all);
+    const bool use_all = kMask ? (use_all_word & 1) != 0 : use_all_word != 0;
+    if constexpr (kMask) {
+        if (use_all_word & kNoEstimate) {      // (uniform) no estimate: NaN rows, and an empty bracket for the concentration pass
+            if (threadIdx.x == 0) {
+                const float nan = sample_out_of_mask();
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    put(&st.he[i], nan);
+                    put(&st.pinv[i], nan);
+                }
+                put(&st.phi_key[0], 0u);
+                put(&st.phi_key[1], 0u);
+                put(&st.ncand_seen[0], 0u);
+                put(&st.ncand_seen[1], 0u);
+                StageRecord* rec = &st.rec[1];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) put(&rec->coef[i], 0.0f);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    put(&st.rank[2 + s], 0ull);
+                    put(&rec->lo[s], 0xFFFFFFFFu);
+                    put(&rec->hi[s], 0u);
+                    put(&rec->bin_origin[s], 0.0);
+                    put(&rec->bin_scale[s], 0.0);
+                }
+                put(&rec->use_all, 1);
+            }
+            if (g.fine_chunk) {
+                uint32_t* row = ws.block_hist + (size_t)group * g.blocks_per_tile * 512;
+                for (int i = threadIdx.x; i < 512; i += blockDim.x) put(&row[i], 0u);
+            }
+            return;
+        }
+    }
     uint32_t phi_key[2];
     if constexpr (kSpread) {
         pf.ncand[0] = get(&ws.pool->ncand[0]);
         pf.ncand[1] = get(&ws.pool->ncand[1]);
-        resolve_pair_spread<T>(images, g, ws, 0, vecs, use_all, phi_key, sh);
+        resolve_pair_spread<T, kMask>(images, g, ws, 0, vecs, use_all, phi_key, sh, mk);
     } else {
-        resolve_pair<T>(images, g, ws, group, 0, vecs, use_all, pf, phi_key, sh);
+        resolve_pair<T, kMask>(images, g, ws, group, 0, vecs, use_all, pf, phi_key, sh, mk);
     }
     SX_STAMP(st, 7);
     if (threadIdx.x == 0) {
@@ -2662,14 +2903,14 @@ __device__ void stain_stage(const T* __restrict__ images, const Geometry& g, con
     float pinv[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) pinv[i] = sh->coef[i];
-    const unsigned long long n_all = g.distributed ? (unsigned long long)g.n_all : (unsigned long long)gp.count;
+    const unsigned long long n_all = kMask ? (unsigned long long)get(&st.mom[kPartial]) : g.distributed ? (unsigned long long)g.n_all : (unsigned long long)gp.count;
     const unsigned long long k99 = nearest_rank_index(99.0, n_all);          // torch_backend.py:447-448
     uint32_t key[2][kKeys];
 #pragma unroll
     for (int i = 0; i < kKeys; ++i) {
         const int j = i * kGroupThreads + (int)threadIdx.x;
         uint32_t ka = 0xFFFFFFFFu, kb = 0xFFFFFFFFu;
-        if (j < g.sample_count) {
+        if (j < g.sample_count && (!kMask || sample_in_mask(sod[i]))) {
             float c0, c1;
             concentration(sod[i], pinv, c0, c1);
             ka = float_key(c0);
@@ -2708,11 +2949,34 @@ __device__ void stain_stage(const T* __restrict__ images, const Geometry& g, con
 // ------------------------------------------------------------------------------------------------
 // per-tile stage C ("scale"): concentration percentiles -> scale factors (transform) / outputs (fit)
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool kSpread = false>
+template <typename T, bool kSpread = false, bool kMask = false>
 __device__ void scale_stage(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int group, const float* __restrict__ target_max_conc, float* __restrict__ he_out,
-                            float* __restrict__ max_c_out, TileScratch* sh) {
+                            float* __restrict__ max_c_out, TileScratch* sh, const MaskArgs<kMask>& mk = MaskArgs<kMask>{}) {
     GroupState& st = ws.state[group];
     SX_STAMP(st, 12);
+    if constexpr (kMask) {
+        if (get(&st.use_all) & kNoEstimate) {      // (uniform) no estimate: NaN maxC, and a NaN fold for a reconstruct pass that copies the tile anyway
+            if (threadIdx.x == 0) {
+                const float nan = sample_out_of_mask();
+                put(&st.max_c[0], nan);
+                put(&st.max_c[1], nan);
+                put(&st.ncand_seen[2], 0u);
+                put(&st.ncand_seen[3], 0u);
+                StageRecord* rec = &st.rec[2];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) put(&rec->coef[i], nan);
+                put(&rec->scale[0], nan);
+                put(&rec->scale[1], nan);
+                if (he_out) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) he_out[i] = nan;
+                    max_c_out[0] = nan;
+                    max_c_out[1] = nan;
+                }
+            }
+            return;
+        }
+    }
     reset_scratch(sh);
     PairPrefetch pf;
     if constexpr (!kSpread) prefetch_pair(pf, g, ws, group, 2);
@@ -2723,9 +2987,9 @@ __device__ void scale_stage(const T* __restrict__ images, const Geometry& g, con
     if constexpr (kSpread) {
         pf.ncand[0] = get(&ws.pool->ncand[2]);
         pf.ncand[1] = get(&ws.pool->ncand[3]);
-        resolve_pair_spread<T>(images, g, ws, 2, pinv, true, c_key, sh);
+        resolve_pair_spread<T, kMask>(images, g, ws, 2, pinv, true, c_key, sh, mk);
     } else {
-        resolve_pair<T>(images, g, ws, group, 2, pinv, true, pf, c_key, sh);
+        resolve_pair<T, kMask>(images, g, ws, group, 2, pinv, true, pf, c_key, sh, mk);
     }
     SX_STAMP(st, 13);
     if (threadIdx.x == 0) {
@@ -2755,12 +3019,18 @@ __device__ void scale_stage(const T* __restrict__ images, const Geometry& g, con
 // ------------------------------------------------------------------------------------------------
 // (two-byte pixels: five waves per SIMD -- a 224 x 224 tile is five work items (set_chunk), 1280 for the batch that matters, and at the
 // 106 registers the compiler would take, four workgroups per CU made that a second round)
-template <typename T, int V, bool kInter = false>
-__global__ __launch_bounds__(kStreamThreads, sizeof(T) <= 2 ? 5 : 1) void stats_kernel(const T* __restrict__ images, Geometry g, Workspace ws) {
+// (kMask, here and below: the masked forms -- sx_macenko_*_masked -- with the mask in `mk`, which is empty otherwise; they run without the codes)
+// (the masked uint8 pass: four waves per SIMD -- at five, the mask's two registers, its bits and the count, made it spill more than the unmasked pass does)
+template <typename T, int V, bool kInter = false, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads, sizeof(T) <= 2 ? (kMask && sizeof(T) == 1 ? 4 : 5) : 1) void stats_kernel(const T* __restrict__ images, Geometry g, Workspace ws, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     __shared__ StatsScratch<kStreamThreads> sh;
     __shared__ LevelTables<T> tb;
     tb.fill();
-    if constexpr (Codable<T, V, kInter>::value) {
+    if constexpr (kMask) {
+        stats_item<T, V, kStreamThreads, kInter, false, true>(images, g, ws, blockIdx.x / g.blocks_per_tile, blockIdx.x % g.blocks_per_tile, blockIdx.x, &sh, tb, nullptr, mk);
+        return;
+    }
+    if constexpr (!kMask && Codable<T, V, kInter>::value) {
         if (g.code_epoch != 0u) {      // (uniform over the launch)
             __shared__ CodeTable<T, 4> ct;
             ct.fill();
@@ -2771,13 +3041,17 @@ __global__ __launch_bounds__(kStreamThreads, sizeof(T) <= 2 ? 5 : 1) void stats_
     stats_item<T, V, kStreamThreads, kInter>(images, g, ws, blockIdx.x / g.blocks_per_tile, blockIdx.x % g.blocks_per_tile, blockIdx.x, &sh, tb);
 }
 
-template <typename T, int V, bool kConc, bool kInter = false>
-__global__ __launch_bounds__(kStreamThreads) void bracket_kernel(const T* __restrict__ images, Geometry g, Workspace ws) {
+template <typename T, int V, bool kConc, bool kInter = false, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void bracket_kernel(const T* __restrict__ images, Geometry g, Workspace ws, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     __shared__ BracketScratch<kStreamThreads> sh;
     const int per_tile = g.fine_chunk ? g.fine_blocks : g.blocks_per_tile;
     __shared__ LevelTables<T> tb;
     tb.fill();
-    if constexpr (Codable<T, V, kInter>::value) {
+    if constexpr (kMask) {
+        bracket_item<T, V, kConc, kStreamThreads, kInter, true>(images, g, ws, blockIdx.x / per_tile, blockIdx.x % per_tile, blockIdx.x, &sh, tb, mk);
+        return;
+    }
+    if constexpr (!kMask && Codable<T, V, kInter>::value) {
         if (g.code_epoch != 0u && get(&ws.code_bad[blockIdx.x / per_tile]) != g.code_epoch) {      // the tile is 8-bit levels: its codes (uniform over the workgroup)
             __shared__ LevelTables<Coded<T>> ctb;
             ctb.fill();
@@ -2788,13 +3062,19 @@ __global__ __launch_bounds__(kStreamThreads) void bracket_kernel(const T* __rest
     bracket_item<T, V, kConc, kStreamThreads, kInter>(images, g, ws, blockIdx.x / per_tile, blockIdx.x % per_tile, blockIdx.x, &sh, tb);
 }
 
-template <typename T, typename O, int V, bool kUnit, bool kInter = false, bool kAug = false>
-__global__ __launch_bounds__(kStreamThreads) void reconstruct_kernel(const T* __restrict__ images, O* __restrict__ out, Geometry g, Workspace ws, const float* __restrict__ stain_matrix) {
+template <typename T, typename O, int V, bool kUnit, bool kInter = false, bool kAug = false, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void reconstruct_kernel(const T* __restrict__ images, O* __restrict__ out, Geometry g, Workspace ws, const float* __restrict__ stain_matrix,
+                                                                     MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     const int per_tile = g.recon_chunk ? g.recon_blocks : (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile);
     __shared__ LevelTables<T> tb;
     tb.fill();
     const unsigned item = blockIdx.x;      // (measured: reversing the order, so that the work items pass A touched last come first, changes nothing)
-    if constexpr (Codable<T, V, kInter>::value && std::is_same<T, O>::value) {
+    if constexpr (kMask) {
+        static_assert(!kMask || (!kInter && !kAug), "masked Macenko: planar tiles, no augmentation");
+        reconstruct_item<T, O, V, kUnit, kStreamThreads, false, false, true>(images, out, g, ws, item / per_tile, item % per_tile, stain_matrix, tb, nullptr, nullptr, mk);
+        return;
+    }
+    if constexpr (!kMask && Codable<T, V, kInter>::value && std::is_same<T, O>::value) {
         if (g.code_epoch != 0u && get(&ws.code_bad[item / per_tile]) != g.code_epoch) {      // the tile is 8-bit levels: its codes in, the same float pixels out
             __shared__ LevelTables<Coded<T>> ctb;
             ctb.fill();
@@ -2859,11 +3139,14 @@ struct ApplyArgs {
 //   3. the pixels stream through reconstruct_item's arithmetic and store paths.
 // The result does not depend on how a tile is cut into work items (independent pixels), nor on n_sources (the same six + two floats
 // give the same fold).
-template <typename T, typename O, int V, bool kUnit, bool kInter>
-__global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restrict__ images, O* __restrict__ out, ApplyArgs a) {
+// kMask (sx_macenko_apply_masked): reconstruct_item's rule -- a masked-in pixel gets the arithmetic above, a masked-out pixel is copied
+// (its input level through the same clamp, cast and / 255), and so is every pixel of a tile whose source row holds a NaN.
+template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restrict__ images, O* __restrict__ out, ApplyArgs a, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     constexpr int TPB = kStreamThreads;
     __shared__ LevelTables<T> tb;
-    __shared__ float fold[12];
+    __shared__ float fold[kMask ? 13 : 12];      // (kMask: the last word says whether the tile is copied through)
+    const uint8_t* msk = tile_mask(mk, blockIdx.x / (unsigned)a.blocks, a.pixels);
     const int64_t tile = blockIdx.x / (unsigned)a.blocks;
     const int chunk_id = (int)(blockIdx.x % (unsigned)a.blocks);
     const int64_t p_begin = (int64_t)chunk_id * a.chunk;
@@ -2888,7 +3171,12 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
     };
     int64_t p = p_begin + (int64_t)threadIdx.x * V;
     float u[3][V];
-    if (p < p_end) load(p, u);
+    MaskPack<V> mp;
+    mp.clear();
+    if (p < p_end) {
+        load(p, u);
+        if constexpr (kMask) mp.load(msk + p);
+    }
 
     if (threadIdx.x == 0) {
         const bool own = a.sm == nullptr;
@@ -2897,13 +3185,20 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
 #pragma unroll
         for (int i = 0; i < 6; ++i) he[i] = he_src[i];
         pinv_of_he(he, rec8);
+        bool no_estimate = false;      // (kMask) a NaN in the tile's source row
+        if constexpr (kMask) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) no_estimate = no_estimate || he[i] != he[i];
+        }
         if (own) {
             rec8[6] = rec8[7] = 1.0f;
         } else {
             const float* mc = a.max_c + (a.per_tile ? tile * 2 : 0);
             rec8[6] = a.tmc[0] / mc[0];      // torch_backend.py:452
             rec8[7] = a.tmc[1] / mc[1];
+            if constexpr (kMask) no_estimate = no_estimate || mc[0] != mc[0] || mc[1] != mc[1];
         }
+        if constexpr (kMask) fold[12] = no_estimate ? 1.0f : 0.0f;
         const float* sm_src = own ? he_src : a.sm;
         // (reconstruct_item's fold, kAug form)
         double pinv[6], sm[6];
@@ -2942,10 +3237,14 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
         for (int j = 0; j < 3; ++j) m[c][j] = fold[c * 3 + j];
         k[c] = fold[9 + c];
     }
+    bool through = false;
+    if constexpr (kMask) through = fold[12] != 0.0f;
 
     __shared__ uint4 stage[(kInter && V > 1 && sizeof(O) * V == 16) ? kStreamThreads * 3 : 1];      // 3 KB per wave: store_pixels_staged()
     while (p < p_end) {
         O res[3][V];
+        uint32_t in_bits = 0u;
+        if constexpr (kMask) in_bits = through ? 0u : mp.bits();
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             float l[3];
@@ -2954,12 +3253,20 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float x = fmaf(m[c][2], l[2], fmaf(m[c][1], l[1], fmaf(m[c][0], l[0], k[c])));
-                res[c][i] = rgb_to_output<T, O, kUnit>(fminf(fmaxf(__builtin_amdgcn_exp2f(x), 0.0f), 255.0f));      // :459, :128
+                if constexpr (kMask) {
+                    const float rgb = in_mask(in_bits, i) ? __builtin_amdgcn_exp2f(x) : input_level<T>(u[c][i]);
+                    res[c][i] = rgb_to_output<T, O, kUnit>(fminf(fmaxf(rgb, 0.0f), 255.0f));
+                } else {
+                    res[c][i] = rgb_to_output<T, O, kUnit>(fminf(fmaxf(__builtin_amdgcn_exp2f(x), 0.0f), 255.0f));      // :459, :128
+                }
             }
         }
         const int64_t q = p;
         p += (int64_t)TPB * V;
-        if (p < p_end) load(p, u);      // (a work item of several pack sets: the next one is on its way while this one is stored)
+        if (p < p_end) {      // (a work item of several pack sets: the next one is on its way while this one is stored)
+            load(p, u);
+            if constexpr (kMask) mp.load(msk + p);
+        }
         if constexpr (kInter && V > 1 && sizeof(O) * V == 16) {
             if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {      // wave-uniform: every lane has a pack (all but a tile's last sweep)
                 store_pixels_staged<O, V>(dst, q, res, stage + (threadIdx.x / kWave) * (3 * kWave));
@@ -2988,22 +3295,37 @@ __global__ __launch_bounds__(kGroupThreads) void fast_kernel(const T* __restrict
     plane_stage<T, true>(images, g, ws, blockIdx.x, 1, &sh, nullptr, target_max_conc);
 }
 
-template <typename T>
+template <typename T, bool kMask = false>
 __global__ __launch_bounds__(kGroupThreads) void plane_kernel(const T* __restrict__ images, Geometry g, Workspace ws, int allow_fallback) {
     __shared__ TileScratch sh;
-    plane_stage<T>(images, g, ws, blockIdx.x, allow_fallback, &sh);
+    plane_stage<T, false, kMask>(images, g, ws, blockIdx.x, allow_fallback, &sh);
 }
 
-template <typename T, bool kSpread = false>
-__global__ __launch_bounds__(kGroupThreads) void stain_kernel(const T* __restrict__ images, Geometry g, Workspace ws) {
+template <typename T, bool kSpread = false, bool kMask = false>
+__global__ __launch_bounds__(kGroupThreads) void stain_kernel(const T* __restrict__ images, Geometry g, Workspace ws, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     __shared__ TileScratch sh;
-    stain_stage<T, kSpread>(images, g, ws, blockIdx.x, &sh);
+    stain_stage<T, kSpread, kMask>(images, g, ws, blockIdx.x, &sh, mk);
 }
 
-template <typename T, bool kSpread = false>
-__global__ __launch_bounds__(kGroupThreads) void scale_kernel(const T* __restrict__ images, Geometry g, Workspace ws, const float* __restrict__ target_max_conc, float* __restrict__ he_out, float* __restrict__ max_c_out) {
+template <typename T, bool kSpread = false, bool kMask = false>
+__global__ __launch_bounds__(kGroupThreads) void scale_kernel(const T* __restrict__ images, Geometry g, Workspace ws, const float* __restrict__ target_max_conc, float* __restrict__ he_out, float* __restrict__ max_c_out,
+                                                              MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     __shared__ TileScratch sh;
-    scale_stage<T, kSpread>(images, g, ws, blockIdx.x, target_max_conc, he_out, max_c_out, &sh);
+    scale_stage<T, kSpread, kMask>(images, g, ws, blockIdx.x, target_max_conc, he_out, max_c_out, &sh, mk);
+}
+
+// sx_macenko_estimate_masked: the estimate of every group out of the workspace -- HE_source and maxC (NaN rows: no estimate), the selection
+// count (the kept pixels, or the masked-in ones where the tile took them all; 0 without an estimate) and the exact count of masked-in pixels
+__global__ void export_estimate_masked_kernel(const GroupState* __restrict__ state, int64_t n_groups, float* __restrict__ he_out, float* __restrict__ max_c_out, float* __restrict__ kept_out,
+                                              unsigned long long* __restrict__ mask_counts_out) {
+    const int64_t gidx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (gidx >= n_groups) return;
+    const GroupState& st = state[gidx];
+    for (int i = 0; i < 6; ++i) he_out[gidx * 6 + i] = st.he[i];
+    max_c_out[gidx * 2] = st.max_c[0];
+    max_c_out[gidx * 2 + 1] = st.max_c[1];
+    if (kept_out) kept_out[gidx] = (float)st.n_sel;
+    if (mask_counts_out) mask_counts_out[gidx] = (unsigned long long)st.mom[kPartial];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3238,28 +3560,30 @@ static void set_sampling(Geometry& g, bool may_add_item = false) {
     g.cap = cap_for(g.spread ? g.pixels : count);
 }
 
-template <typename T, int V, bool kInter = false>
-static int run_estimate(const T* images, const Geometry& g, const Workspace& ws, int n_groups, int allow_fallback, const float* tmc, float* he_out, float* max_c_out, hipStream_t stream) {
+// (kMask: the masked forms of the same launches -- the same grids, so that a mask of all ones gives the unmasked call's bits)
+template <typename T, int V, bool kInter = false, bool kMask = false>
+static int run_estimate(const T* images, const Geometry& g, const Workspace& ws, int n_groups, int allow_fallback, const float* tmc, float* he_out, float* max_c_out, hipStream_t stream,
+                        MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     const unsigned grid = (unsigned)(g.n_tiles * g.blocks_per_tile);
     const unsigned grid_b = (unsigned)(g.n_tiles * (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile));      // bracket stages
-    hipLaunchKernelGGL((stats_kernel<T, V, kInter>), dim3(grid), dim3(kStreamThreads), 0, stream, images, g, ws);
-    hipLaunchKernelGGL((plane_kernel<T>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws, allow_fallback);
-    hipLaunchKernelGGL((bracket_kernel<T, V, false, kInter>), dim3(grid_b), dim3(kStreamThreads), 0, stream, images, g, ws);
+    hipLaunchKernelGGL((stats_kernel<T, V, kInter, kMask>), dim3(grid), dim3(kStreamThreads), 0, stream, images, g, ws, mk);
+    hipLaunchKernelGGL((plane_kernel<T, kMask>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws, allow_fallback);
+    hipLaunchKernelGGL((bracket_kernel<T, V, false, kInter, kMask>), dim3(grid_b), dim3(kStreamThreads), 0, stream, images, g, ws, mk);
     if (g.spread) {
         hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)g.n_tiles), dim3(512), 0, stream, g, ws, 0);
         hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)g.n_tiles), dim3(kGroupThreads), 0, stream, g, ws, 0);
-        hipLaunchKernelGGL((stain_kernel<T, true>), dim3(1), dim3(kGroupThreads), 0, stream, images, g, ws);
+        hipLaunchKernelGGL((stain_kernel<T, true, kMask>), dim3(1), dim3(kGroupThreads), 0, stream, images, g, ws, mk);
     } else {
-        hipLaunchKernelGGL((stain_kernel<T>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws);
+        hipLaunchKernelGGL((stain_kernel<T, false, kMask>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws, mk);
     }
     if (g.own_basis) return check_launch("macenko estimate");      // (sx_macenko_augment without a reference: HE_source and its pinv are all it needs)
-    hipLaunchKernelGGL((bracket_kernel<T, V, true, kInter>), dim3(grid_b), dim3(kStreamThreads), 0, stream, images, g, ws);
+    hipLaunchKernelGGL((bracket_kernel<T, V, true, kInter, kMask>), dim3(grid_b), dim3(kStreamThreads), 0, stream, images, g, ws, mk);
     if (g.spread) {
         hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)g.n_tiles), dim3(512), 0, stream, g, ws, 1);
         hipLaunchKernelGGL(pool_gather_kernel, dim3((unsigned)g.n_tiles), dim3(kGroupThreads), 0, stream, g, ws, 1);
-        hipLaunchKernelGGL((scale_kernel<T, true>), dim3(1), dim3(kGroupThreads), 0, stream, images, g, ws, tmc, he_out, max_c_out);
+        hipLaunchKernelGGL((scale_kernel<T, true, kMask>), dim3(1), dim3(kGroupThreads), 0, stream, images, g, ws, tmc, he_out, max_c_out, mk);
     } else {
-        hipLaunchKernelGGL((scale_kernel<T>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws, tmc, he_out, max_c_out);
+        hipLaunchKernelGGL((scale_kernel<T, false, kMask>), dim3(n_groups), dim3(kGroupThreads), 0, stream, images, g, ws, tmc, he_out, max_c_out, mk);
     }
     return check_launch("macenko estimate");
 }
@@ -3615,8 +3939,8 @@ static int separate_typed(const void* images, const Geometry& g0, const Workspac
 // 68.8 with 4, 73.5 with 16; 256 x 224 x 224 bfloat16: 28.8 / 29.9 / 29.6 / 35.8.  One-byte output (uint8 in, uint8 out: 16 pixels per lane
 // and set) takes 4 sets: 22.9 us with 1, 21.8 with 4, 29.3 with 16.  The scalar path: sixteen sweeps.
 template <typename O> constexpr int apply_sets() { return sizeof(O) == 1 ? 4 : 1; }
-template <typename T, typename O, int V, bool kUnit, bool kInter>
-static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipStream_t stream) {
+template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
+static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
     int sets = V == 1 ? 16 : apply_sets<O>();
 #ifdef SX_STAMPS      // diagnostic builds: pack sets per work item from the environment (tools/bench_apply.py --sets: A/B of the grid)
@@ -3627,20 +3951,25 @@ static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipS
 #endif
     a.chunk = kStreamThreads * VR * sets;
     a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
-    hipLaunchKernelGGL((apply_kernel<T, O, VR, kUnit, kInter>), dim3((unsigned)(n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, out, a);
+    hipLaunchKernelGGL((apply_kernel<T, O, VR, kUnit, kInter, kMask>), dim3((unsigned)(n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, out, a, mk);
     return check_launch("macenko apply");
 }
 
-template <typename T>
-static int apply_typed(const void* images, void* out, int64_t n_tiles, const ApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream) {
+// (kMask: sx_macenko_apply_masked -- planar tiles only; the mask's packs are as wide as the pixels', so its pointer has a say in `vec`)
+template <typename T, bool kMask = false>
+static int apply_typed(const void* images, void* out, int64_t n_tiles, const ApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     const bool u8_half = sizeof(T) == 1 && out_code != 0;
     const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
     const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
     constexpr int W = PackOf<T>::n;
     // (16-byte packs where both pointers allow them, as transform_typed decides; the scalar path otherwise)
-    const bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
     const T* in = static_cast<const T*>(images);
 #define SX_RUN_APPLY(O, U)                                                                                                                                     \
+    if constexpr (kMask)                                                                                                                                       \
+        return vec ? run_apply<T, O, W, U, false, true>(in, static_cast<O*>(out), n_tiles, a, stream, mk) : run_apply<T, O, 1, U, false, true>(in, static_cast<O*>(out), n_tiles, a, stream, mk); \
+    else                                                                                                                                                       \
     return interleaved ? (vec ? run_apply<T, O, W, U, true>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, true>(in, static_cast<O*>(out), n_tiles, a, stream)) \
                        : (vec ? run_apply<T, O, W, U, false>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, false>(in, static_cast<O*>(out), n_tiles, a, stream));
     if constexpr (sizeof(T) == 1) {
@@ -3694,6 +4023,77 @@ static int fit_typed(const void* images, const Geometry& g0, const Workspace& ws
     const T* in = static_cast<const T*>(images);
     return vec ? run_estimate<T, W>(in, g, ws, 1, 0, nullptr, he_out, max_c_out, stream)
                : run_estimate<T, 1>(in, g, ws, 1, 0, nullptr, he_out, max_c_out, stream);
+}
+
+// ---- the masked calls (sx_macenko_*_masked): always the four passes, planar tiles, no codes ------------------------------------
+// The geometry is the unmasked four-pass call's (transform_typed / estimate_typed / fit_typed), so that a mask of all ones has its bits;
+// 16-byte pixel packs need a mask pointer aligned to the pack's pixels as well (the scalar path serves everything else).
+template <typename T>
+static void masked_geometry(Geometry& g, const void* images, const void* out, size_t out_elem, const uint8_t* mask, bool per_tile) {
+    constexpr int W = PackOf<T>::n;
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (out == nullptr || aligned_for(out, out_elem * W)) && aligned_for(mask, W);
+    g.vec = vec ? 1 : 0;
+    g.vec_width = W;
+    set_sampling(g, per_tile);
+    g.code_epoch = 0u;
+    if (per_tile) set_fine_chunk(g, vec ? W : 1);
+}
+
+template <typename T>
+static int estimate_masked_typed(const void* images, const Geometry& g0, const Workspace& ws, const uint8_t* mask, float* he_out, float* max_c_out, float* kept_out, unsigned long long* mask_counts_out,
+                                 hipStream_t stream) {
+    Geometry g = g0;
+    constexpr int W = PackOf<T>::n;
+    masked_geometry<T>(g, images, nullptr, 0, mask, !g.pooled);
+    const T* in = static_cast<const T*>(images);
+    const MaskArgs<true> mk{mask};
+    const int n_groups = g.pooled ? 1 : (int)g.n_tiles, allow_fallback = g.pooled ? 0 : 1;      // (the reference's pooled fit has no fallback)
+    const int rc = g.vec ? run_estimate<T, W, false, true>(in, g, ws, n_groups, allow_fallback, nullptr, nullptr, nullptr, stream, mk)
+                         : run_estimate<T, 1, false, true>(in, g, ws, n_groups, allow_fallback, nullptr, nullptr, nullptr, stream, mk);
+    if (rc != SX_OK) return rc;
+    hipLaunchKernelGGL(export_estimate_masked_kernel, dim3((unsigned)((n_groups + 63) / 64)), dim3(64), 0, stream, ws.state, (int64_t)n_groups, he_out, max_c_out, kept_out, mask_counts_out);
+    return check_launch("macenko export_estimate_masked");
+}
+
+template <typename T, typename O, int V>
+static int run_transform_masked(const T* images, O* out, const Geometry& g, const Workspace& ws, const float* sm, const float* tmc, bool unit, MaskArgs<true> mk, hipStream_t stream) {
+    const int rc = run_estimate<T, V, false, true>(images, g, ws, (int)g.n_tiles, 1, tmc, nullptr, nullptr, stream, mk);
+    if (rc != SX_OK) return rc;
+    // (run_transform's reconstruct grid: 16 bytes of output per lane and plane, one pack set per work item for big batches)
+    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    Geometry gr = g;
+    unsigned items_r = (unsigned)(g.n_tiles * (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile));
+    if (!g.fine_chunk && V > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {
+        gr.recon_chunk = kStreamThreads * VR;
+        gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
+        items_r = (unsigned)(g.n_tiles * gr.recon_blocks);
+    }
+    if (unit)
+        hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, true, false, false, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm, mk);
+    else
+        hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, false, false, false, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm, mk);
+    return check_launch("macenko masked reconstruct");
+}
+
+template <typename T>
+static int transform_masked_typed(const void* images, void* out, const Geometry& g0, const Workspace& ws, const uint8_t* mask, const float* sm, const float* tmc, bool unit, hipStream_t stream) {
+    Geometry g = g0;
+    const bool u8_half = sizeof(T) == 1 && g.out_code != 0;
+    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
+    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
+    constexpr int W = PackOf<T>::n;
+    masked_geometry<T>(g, images, out, out_elem, mask, true);
+    const T* in = static_cast<const T*>(images);
+    const MaskArgs<true> mk{mask};
+#define SX_RUN_MASKED(O) \
+    return g.vec ? run_transform_masked<T, O, W>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, mk, stream) : run_transform_masked<T, O, 1>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, mk, stream);
+    if constexpr (sizeof(T) == 1) {
+        if (u8_half && g.out_code == SX_BF16) { SX_RUN_MASKED(__hip_bfloat16) }
+        if (u8_half) { SX_RUN_MASKED(__half) }
+        if (u8_unit) { SX_RUN_MASKED(float) }
+    }
+    SX_RUN_MASKED(T)
+#undef SX_RUN_MASKED
 }
 
 // ---- distributed pooled fit on the bracket machinery (sx_macenko_pfit_*) ---------------------------------
@@ -4281,6 +4681,105 @@ extern "C" int sx_macenko_fit(const void* images, int dtype, int64_t n, int64_t 
         case SX_BF16: return fit_typed<__hip_bfloat16>(images, g, ws, he_out, max_c_out, stream);
         case SX_F32: return fit_typed<float>(images, g, ws, he_out, max_c_out, stream);
         case SX_F64: return fit_typed<double>(images, g, ws, he_out, max_c_out, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// ---- tissue masks: the reference's algorithm on the masked-in pixels only, masked-out pixels copied (include/stainx_hip.h) ----
+// The flags the masked calls take; everything else -- SX_MACENKO_SAMPLED and SX_MACENKO_CHANNELS_LAST among it -- is refused before anything is enqueued.
+static int masked_flags_ok(unsigned flags, unsigned allowed, int dtype, const char* who, bool selects = true) {
+#ifdef SX_DIAG
+    if (selects) allowed |= SX_MACENKO_NO_TIE_SHORTCUT;      // (the diagnostic build: the calls that select may be sent down their slow exact paths)
+#endif
+    if (flags & ~allowed) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s runs the four passes over planar tiles (no SX_MACENKO_SAMPLED, no SX_MACENKO_CHANNELS_LAST) and takes the flags 0x%x only", flags, who, allowed);
+    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
+        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    return SX_OK;
+}
+
+extern "C" int sx_macenko_estimate_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, int pooled, float* he_out, float* max_c_out, float* kept_out,
+                                          unsigned long long* mask_counts_out, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = masked_flags_ok(flags, SX_MACENKO_CLASSIC, dtype, "sx_macenko_estimate_masked");
+    if (rc != SX_OK) return rc;
+    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (!he_out || !max_c_out) return fail(SX_ERR_BAD_ARG, "he_out / max_c_out pointer is null");
+    Geometry g = make_geometry(n, h * w, pooled ? 1 : 0);
+#ifdef SX_DIAG
+    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
+#endif
+    const Workspace ws = carve(ws_ptr, n, g.pixels);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {
+        case SX_U8: return estimate_masked_typed<uint8_t>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
+        case SX_F16: return estimate_masked_typed<__half>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
+        case SX_BF16: return estimate_masked_typed<__hip_bfloat16>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
+        case SX_F32: return estimate_masked_typed<float>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
+        case SX_F64: return estimate_masked_typed<double>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+extern "C" int sx_macenko_transform_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* sm, const float* tmc, unsigned flags,
+                                           void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_transform_masked");
+    if (rc != SX_OK) return rc;
+    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (!out || !sm || !tmc) return fail(SX_ERR_BAD_ARG, "out / stain_matrix / target_max_conc pointer is null");
+    Geometry g = make_geometry(n, h * w, 0);
+#ifdef SX_DIAG
+    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
+#endif
+    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const Workspace ws = carve(ws_ptr, n, g.pixels);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    switch (dtype) {
+        case SX_U8: return transform_masked_typed<uint8_t>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
+        case SX_F16: return transform_masked_typed<__half>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
+        case SX_BF16: return transform_masked_typed<__hip_bfloat16>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
+        case SX_F32: return transform_masked_typed<float>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
+        case SX_F64: return transform_masked_typed<double>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+extern "C" int sx_macenko_apply_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources,
+                                       const float* alpha, const float* beta, const float* sm, const float* tmc, const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
+    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise) or both null (own basis)");
+    if ((alpha == nullptr) != (beta == nullptr)) return fail(SX_ERR_BAD_ARG, "alpha and beta: both given or both null");
+    if (!sm && !alpha) return fail(SX_ERR_BAD_ARG, "own basis (no stain_matrix / target_max_conc) needs the factors alpha and beta: without them the call would rebuild its input");
+    if (sm && !source_max_c) return fail(SX_ERR_BAD_ARG, "source_max_c pointer is null (it may be null in own-basis mode only)");
+    const int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_apply_masked", false);
+    if (rc != SX_OK) return rc;
+    ApplyArgs a{};
+    a.he = source_he;
+    a.max_c = source_max_c;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.sm = sm;
+    a.tmc = tmc;
+    a.pixels = h * w;
+    a.per_tile = n_sources == n && n != 1 ? 1 : 0;
+    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const MaskArgs<true> mk{mask_dev};
+    switch (dtype) {
+        case SX_U8: return apply_typed<uint8_t, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_F16: return apply_typed<__half, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_BF16: return apply_typed<__hip_bfloat16, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_F32: return apply_typed<float, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_F64: return apply_typed<double, true>(images, out, n, a, out_code, false, unit, stream, mk);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }
