@@ -72,6 +72,10 @@ def main() -> None:
     out_tissue = tissue.apply(tiles, tissue.estimate(tiles, pooled=True))       # ... also slide-level: one masked estimate, applied under the same rule
     per_tile = norm.estimate(tiles)                                  # every tile's own estimate fed back: the transform, bit for bit
     assert torch.equal(norm.apply(tiles, per_tile), norm.transform(tiles))
+    sep = norm.separate(more, source=slide, concentrations=True)     # the slide's basis for separation too: one launch, H / E maps that line up across tiles
+    sep_tissue = tissue.separate(tiles, concentrations=True)         # under the rule, glass holds no stain: concentrations 0, both images at the 240 level
+    assert torch.equal(norm.separate(tiles, source=per_tile).hematoxylin, norm.separate(tiles).hematoxylin)
+    assert sep.concentrations.shape == (8, 2, 256, 256) and sep_tissue.eosin.shape == tiles.shape
     print(f"[rank {rank}] slide-level apply   {tuple(out.shape)} + {tuple(out_more.shape)} {out.dtype}  maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")
 
     # 7. a batch of tiles from DIFFERENT slides (a DataLoader batch): Reinhard and histogram matching with every tile's own statistics --

@@ -250,6 +250,41 @@ int sx_macenko_apply_masked(const void* images_dev, void* out_dev, int dtype, in
                             const float* stain_matrix_dev, const float* target_max_conc_dev,
                             const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- separation and augmentation: given source basis, tissue masks ----
+ * sx_macenko_separate_apply: sx_macenko_separate's streaming pass with a GIVEN source basis -- ONE kernel launch on `stream`, nothing else
+ * enqueued, no workspace, no estimate; a pixel is read once.  Outputs and flags are sx_macenko_separate's (either output may be NULL, not
+ * both), the source arguments sx_macenko_apply's: n_sources is 1 (one basis for the batch) or n_tiles; source_max_c_dev may be NULL in own
+ * basis (stain_matrix_dev and target_max_conc_dev both NULL: images built with the given HE, concentrations unscaled); source, reference
+ * and mask are device memory read by the kernel (a captured call replayed after new values were copied in uses them).
+ * separate_apply(x, estimate(x)) with n_tiles rows has the bits of sx_macenko_separate(x) wherever the tile's maxC is finite and
+ * non-zero; with one row the result does not depend on n_sources.  NaN source rows are not special-cased (as in sx_macenko_apply). */
+int sx_macenko_separate_apply(const void* images_dev, void* stains_out_dev, float* conc_out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                              const float* source_he_dev, const float* source_max_c_dev, int64_t n_sources,
+                              const float* stain_matrix_dev, const float* target_max_conc_dev, unsigned flags, void* stream);
+/* sx_macenko_separate_apply_masked: the same under a mask (N, H, W), one byte per pixel, planar tiles only (SX_MACENKO_CHANNELS_LAST is
+ * refused, a NULL mask is an error).  A masked-out pixel holds no stain: both concentrations are +0.0f, both stain images the level of
+ * zero concentration, 240, cast (and / 255) as a tissue pixel's level is.  Values under masked-out pixels are never used (NaN and Inf
+ * included).  A tile whose source row holds a NaN -- in normalised mode its maxC row counts too -- is masked-out entirely.  With a mask of
+ * all ones: the bits of sx_macenko_separate_apply. */
+int sx_macenko_separate_apply_masked(const void* images_dev, void* stains_out_dev, float* conc_out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                                     const float* source_he_dev, const float* source_max_c_dev, int64_t n_sources,
+                                     const float* stain_matrix_dev, const float* target_max_conc_dev,
+                                     const unsigned char* mask_dev, unsigned flags, void* stream);
+/* sx_macenko_separate_masked: sx_macenko_separate's arguments plus the mask: the masked per-tile estimate (sx_macenko_estimate_masked's
+ * launches; own basis without tile_max_c_out_dev stops after the stain stage), then the masked separation pass over its rows -- the bits
+ * of sx_macenko_estimate_masked followed by sx_macenko_separate_apply_masked.  A tile without an estimate (fewer than 3 masked-in pixels)
+ * has NaN tile_he / tile_max_c rows and comes out entirely as background.  Workspace: sx_macenko_workspace_bytes_for(..., SX_MACENKO_CLASSIC). */
+int sx_macenko_separate_masked(const void* images_dev, void* stains_out_dev, float* conc_out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                               const unsigned char* mask_dev, const float* stain_matrix_dev, const float* target_max_conc_dev,
+                               float* tile_he_out_dev, float* tile_max_c_out_dev, unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* sx_macenko_augment_masked: sx_macenko_augment's arguments plus the mask: the masked per-tile estimate (own basis: without the
+ * concentration bracket pass and the scale stage), then the jitter on masked-in pixels -- the bits of sx_macenko_estimate_masked followed
+ * by sx_macenko_apply_masked with the factors.  Masked-out pixels, and tiles without an estimate, are copied by
+ * sx_macenko_transform_masked's background rule. */
+int sx_macenko_augment_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, const unsigned char* mask_dev,
+                              const float* alpha_dev, const float* beta_dev, const float* stain_matrix_dev, const float* target_max_conc_dev,
+                              unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

@@ -59,6 +59,11 @@ SIGNATURES = {
     "sx_macenko_estimate_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp]),
+    # separation / augmentation with a given source basis and under tissue masks
+    "sx_macenko_separate_apply": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _uint, _vp]),
+    "sx_macenko_separate_apply_masked": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _uint, _vp]),
+    "sx_macenko_separate_masked": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_macenko_augment_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

@@ -500,6 +500,171 @@ class MacenkoHIP(TorchHIPBackendBase):
         return self.apply(images, source_he, source_max_c, stain_matrix, target_max_conc, alpha=alpha, beta=beta, normalize_to_0_1=normalize_to_0_1,
                           out_dtype=out_dtype, _masking=(mask, luminosity_threshold))
 
+    # ---- separation / augmentation with a given source basis and under tissue masks (include/stainx_hip.h) ----
+    def _check_sources(self, source_he: torch.Tensor, source_max_c: torch.Tensor | None, n: int, need_max_c: bool) -> tuple[torch.Tensor, torch.Tensor | None, int]:
+        """The shape checks of a given source basis (``apply``'s): float32 device tensors and the number of rows, 1 or N."""
+        he_shape = tuple(source_he.shape)
+        if he_shape == (3, 2):
+            n_sources = 1
+        elif len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n):
+            n_sources = he_shape[0]
+        else:
+            raise ValueError(f"source_he must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
+        mc = None
+        if source_max_c is not None:
+            if source_max_c.numel() != 2 * n_sources or (source_max_c.dim() == 2 and tuple(source_max_c.shape) != (n_sources, 2)) or source_max_c.dim() > 2:
+                raise ValueError(f"source_max_c must hold 2 values per source basis, ({n_sources}, 2), got shape {tuple(source_max_c.shape)}")
+            mc = self._f32(source_max_c)
+        elif need_max_c:
+            raise ValueError("source_max_c is required to normalise to a reference (it may be None in own-basis mode only)")
+        return self._f32(source_he), mc, n_sources
+
+    def _separate_call(self, images: torch.Tensor, stain_matrix, target_max_conc, *, source, masking, stains: bool, concentrations: bool, max_conc: bool,
+                       normalize_to_0_1: bool, channels_last: bool, out_dtype) -> dict[str, torch.Tensor | None]:
+        """separate_apply / separate_apply_masked / separate_masked: ``source`` is None (the call's own masked estimate) or
+        ``(source_he, source_max_c)``; ``masking`` is None or ``(mask, luminosity_threshold)``."""
+        what = "separate"
+        if masking is not None:
+            if channels_last:
+                raise ValueError("the masked Macenko calls take planar (NCHW) tiles: channels_last has no masked form")
+            images = self._check_masked(images, what)
+        else:
+            images = images.to(self.device)
+        if not (stains or concentrations):
+            raise ValueError("separate: ask for stains, concentrations or both")
+        flags = 0
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = None
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError("stain_matrix and target_max_conc go together: both (normalised) or neither (the source basis itself)")
+        if channels_last:
+            if images.dim() != 4 or images.shape[3] != 3:
+                raise ValueError(f"Macenko separate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
+        else:
+            self._check_images(images, what)
+        n = images.shape[0]
+        he = mc = None
+        n_sources = n
+        if source is not None:
+            he, mc, n_sources = self._check_sources(source[0], source[1], n, stain_matrix is not None)
+        sm = tmc = None
+        if stain_matrix is not None:
+            if tuple(stain_matrix.shape) != (3, 2):
+                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+            sm = self._f32(stain_matrix)
+            tmc = self._f32(target_max_conc).flatten()
+            if tmc.numel() != 2:
+                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        images = images.contiguous()
+        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
+        code = _dtype_code(images)
+        if out_dtype is None:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        out = {
+            "stains": torch.empty((2, *images.shape), dtype=out_dtype, device=self.device) if stains else None,
+            "concentrations": torch.empty((n, h, w, 2) if channels_last else (n, 2, h, w), dtype=torch.float32, device=self.device) if concentrations else None,
+        }
+        if source is not None:      # (the given rows, broadcast to N)
+            out["he"] = he.reshape(n_sources, 3, 2).expand(n, 3, 2)
+            out["max_c"] = mc.reshape(n_sources, 2).expand(n, 2) if mc is not None else None
+        else:
+            out["he"] = torch.empty((n, 3, 2), dtype=torch.float32, device=self.device)
+            out["max_c"] = torch.empty((n, 2), dtype=torch.float32, device=self.device) if (max_conc or sm is not None) else None
+        if n == 0 or h * w == 0:
+            return out
+        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        with _native.on_device(self.device):
+            stream = _native.stream_ptr(self.device)
+            mask = self._mask_for(images, *masking) if masking is not None else None
+            if source is None:
+                ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+                rc = self._lib.sx_macenko_separate_masked(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, mask.data_ptr(), ptr(sm), ptr(tmc),
+                                                          ptr(out["he"]), ptr(out["max_c"]), flags, ws.data_ptr(), ws.numel(), stream)
+                _native.check(rc, "sx_macenko_separate_masked", self._lib)
+                self.last_workspace = ws
+            elif mask is not None:
+                rc = self._lib.sx_macenko_separate_apply_masked(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, he.data_ptr(), ptr(mc), n_sources,
+                                                                ptr(sm), ptr(tmc), mask.data_ptr(), flags, stream)
+                _native.check(rc, "sx_macenko_separate_apply_masked", self._lib)
+            else:
+                rc = self._lib.sx_macenko_separate_apply(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, he.data_ptr(), ptr(mc), n_sources,
+                                                         ptr(sm), ptr(tmc), flags, stream)
+                _native.check(rc, "sx_macenko_separate_apply", self._lib)
+        return out
+
+    def separate_apply(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None = None,
+                       target_max_conc: torch.Tensor | None = None, *, stains: bool = True, concentrations: bool = False, normalize_to_0_1: bool = False,
+                       channels_last: bool = False, out_dtype: torch.dtype | None = None) -> dict[str, torch.Tensor | None]:
+        """``separate`` with a GIVEN source basis (include/stainx_hip.h: sx_macenko_separate_apply): one kernel launch, no estimate, no
+        workspace, no host synchronisation.  ``source_he`` / ``source_max_c`` as ``apply`` takes them (one row or N; ``source_max_c`` may
+        be None in own basis).  Returns ``separate``'s dictionary; ``he`` / ``max_c`` are the given rows broadcast to N."""
+        return self._separate_call(images, stain_matrix, target_max_conc, source=(source_he, source_max_c), masking=None, stains=stains, concentrations=concentrations,
+                                   max_conc=False, normalize_to_0_1=normalize_to_0_1, channels_last=channels_last, out_dtype=out_dtype)
+
+    def separate_apply_masked(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None,
+                              target_max_conc: torch.Tensor | None, mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, stains: bool = True,
+                              concentrations: bool = False, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None) -> dict[str, torch.Tensor | None]:
+        """``separate_apply`` with a tissue mask (``mask=None``: the luminosity rule, one launch in front): masked-out pixels, and tiles
+        whose source row holds a NaN, hold no stain -- concentrations +0, stain images the 240 level."""
+        return self._separate_call(images, stain_matrix, target_max_conc, source=(source_he, source_max_c), masking=(mask, luminosity_threshold), stains=stains,
+                                   concentrations=concentrations, max_conc=False, normalize_to_0_1=normalize_to_0_1, channels_last=False, out_dtype=out_dtype)
+
+    def separate_masked(self, images: torch.Tensor, stain_matrix: torch.Tensor | None, target_max_conc: torch.Tensor | None, mask: torch.Tensor | None,
+                        luminosity_threshold: float = 0.8, *, stains: bool = True, concentrations: bool = False, max_conc: bool = False, normalize_to_0_1: bool = False,
+                        out_dtype: torch.dtype | None = None) -> dict[str, torch.Tensor | None]:
+        """``separate`` with a tissue mask: the per-tile estimate over the masked-in pixels, then the masked separation pass.  A tile
+        without an estimate (fewer than 3 masked-in pixels) has NaN ``he`` / ``max_c`` rows and comes out entirely as background."""
+        return self._separate_call(images, stain_matrix, target_max_conc, source=None, masking=(mask, luminosity_threshold), stains=stains, concentrations=concentrations,
+                                   max_conc=max_conc, normalize_to_0_1=normalize_to_0_1, channels_last=False, out_dtype=out_dtype)
+
+    def augment_masked(self, images: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, stain_matrix: torch.Tensor | None, target_max_conc: torch.Tensor | None,
+                       mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None) -> torch.Tensor:
+        """``augment`` with a tissue mask: the per-tile estimate over the masked-in pixels, the jitter on those pixels; masked-out pixels,
+        and tiles without an estimate, are copied by ``transform_masked``'s background rule."""
+        images = self._check_masked(images, "augment")
+        flags = _native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
+        else:
+            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError("stain_matrix and target_max_conc go together: both (normalise and jitter) or neither (each tile's own stain basis)")
+        n, _, h, w = images.shape
+        if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
+            raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+        sm = tmc = None
+        if stain_matrix is not None:
+            if tuple(stain_matrix.shape) != (3, 2):
+                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+            sm = self._f32(stain_matrix)
+            tmc = self._f32(target_max_conc).flatten()
+            if tmc.numel() != 2:
+                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
+        a, b = self._f32(alpha), self._f32(beta)
+        code = _dtype_code(images)
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            mask = self._mask_for(images, mask, luminosity_threshold)
+            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
+            rc = self._lib.sx_macenko_augment_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, mask.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                                     sm.data_ptr() if sm is not None else None, tmc.data_ptr() if tmc is not None else None, flags,
+                                                     ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_macenko_augment_masked", self._lib)
+        self.last_workspace = ws
+        return out
+
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.
         Never synchronises the host with the device except to wait for an answer that is five calls old (see below)."""

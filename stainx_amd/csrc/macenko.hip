@@ -3277,6 +3277,237 @@ __global__ __launch_bounds__(kStreamThreads) void apply_kernel(const T* __restri
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// sx_macenko_separate_apply: the separation pass with a GIVEN source basis -- one launch, no workspace, no estimate
+// ------------------------------------------------------------------------------------------------
+// apply_kernel's prologue joined to separate_item's fold and pixel loop.  As in ApplyArgs, everything besides the pixels is device memory
+// read by the kernel itself.
+struct SeparateApplyArgs {
+    const float* he;          // n_sources x 6: HE_source (3,2) row-major
+    const float* max_c;       // n_sources x 2: maxC; not read in own-basis mode
+    const float* sm;          // the reference's stain matrix; null: own basis (the stain images are built with the given HE, scale 1)
+    const float* tmc;         // the reference's maximal concentrations
+    void* stains;             // (2, N, 3, H, W) or (2, N, H, W, 3) of the output element, or null
+    float* conc;              // (N, 2, H, W) or (N, H, W, 2) float32, or null
+    int64_t pixels, n_tiles;  // P = H*W, N
+    int chunk, blocks;        // pixels per work item, work items per tile
+    int per_tile;             // 1: source row `tile`, 0: one row for the batch
+};
+
+// Per work item: every thread requests its first pack set; under that latency ONE thread builds the tile's fold -- pinv_of_he() of the
+// given HE, scale = target_max_conc / maxC in float32 as the scale stage forms it (1 in own basis), then mh, kh, me, ke, a, b with
+// separate_item's very expressions and roundings -- and hands the 32 floats over through LDS; the pixels then stream through
+// separate_item's arithmetic and store paths.  So separate_apply(x, estimate(x)) has separate(x)'s bits, however a tile is cut into
+// work items (independent pixels) and whatever n_sources is (the same six + two floats give the same fold).
+// kMask (sx_macenko_separate_apply_masked, planar only): a masked-out pixel holds no stain -- both concentrations +0.0f, both stain images
+// the level of zero concentration, 240, through the tissue pixels' output path -- and so does every pixel of a tile whose source row
+// holds a NaN.  Every use of a masked-out pixel's value is a select.
+template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void separate_apply_kernel(const T* __restrict__ images, SeparateApplyArgs a, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    static_assert(!(kInter && kMask), "the masked forms are planar");
+    constexpr int TPB = kStreamThreads;
+    __shared__ LevelTables<T> tb;
+    __shared__ float fold[kMask ? 33 : 32];      // mh 9, kh 3, me 9, ke 3, a 6, b 2 (kMask: the last word says whether the tile is all background)
+    const int64_t tile = blockIdx.x / (unsigned)a.blocks;
+    const int chunk_id = (int)(blockIdx.x % (unsigned)a.blocks);
+    const uint8_t* msk = tile_mask(mk, tile, a.pixels);
+    const int64_t p_begin = (int64_t)chunk_id * a.chunk;
+    const int64_t p_end = min(p_begin + (int64_t)a.chunk, a.pixels);
+    const T* img = images + tile * 3 * a.pixels;
+
+    // (the input is read once: planar 16-byte packs non-temporally, as in separate_item)
+    auto load = [&](int64_t p, float (&u)[3][V]) {
+        if constexpr (!kInter && sizeof(T) * V == 16) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const Pack<T, V> pk = load_pack_stream<T, V>(img + c * a.pixels + p);
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    if constexpr (sizeof(T) == 1) u[c][i] = __uint_as_float((uint32_t)pk.v[i]); else u[c][i] = raw_value<T>(pk.v[i]);
+                }
+            }
+        } else {
+            load_pixels<T, V, kInter, sizeof(T) == 1>(img, a.pixels, p, u);
+        }
+    };
+    int64_t p = p_begin + (int64_t)threadIdx.x * V;
+    float u[3][V];
+    MaskPack<V> mp;
+    mp.clear();
+    if (p < p_end) {
+        load(p, u);
+        if constexpr (kMask) mp.load(msk + p);
+    }
+
+    if (threadIdx.x == 0) {
+        const bool own = a.sm == nullptr;
+        const float* he_src = a.he + (a.per_tile ? tile * 6 : 0);
+        float he[6], rec8[8];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) he[i] = he_src[i];
+        pinv_of_he(he, rec8);
+        bool no_estimate = false;      // (kMask) a NaN in the tile's source row
+        if constexpr (kMask) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) no_estimate = no_estimate || he[i] != he[i];
+        }
+        if (own) {
+            rec8[6] = rec8[7] = 1.0f;
+        } else {
+            const float* mc = a.max_c + (a.per_tile ? tile * 2 : 0);
+            rec8[6] = a.tmc[0] / mc[0];      // torch_backend.py:452
+            rec8[7] = a.tmc[1] / mc[1];
+            if constexpr (kMask) no_estimate = no_estimate || mc[0] != mc[0] || mc[1] != mc[1];
+        }
+        if constexpr (kMask) fold[32] = no_estimate ? 1.0f : 0.0f;
+        const float* basis = own ? he_src : a.sm;
+        // (separate_item's fold)
+        double pinv[6], sm[6], s[2];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            pinv[i] = (double)rec8[i];
+            sm[i] = (double)basis[i];
+        }
+        s[0] = own ? 1.0 : (double)rec8[6];
+        s[1] = own ? 1.0 : (double)rec8[7];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double row_h = 0.0, row_e = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float h = (float)(sm[c * 2] * s[0] * pinv[j]);
+                const float e = (float)(sm[c * 2 + 1] * s[1] * pinv[3 + j]);
+                fold[c * 3 + j] = h;
+                fold[12 + c * 3 + j] = e;
+                row_h += (double)h;
+                row_e += (double)e;
+            }
+            fold[9 + c] = (float)(7.90689059560851852932 * (1.0 - row_h));      // log2(240)
+            fold[21 + c] = (float)(7.90689059560851852932 * (1.0 - row_e));
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) fold[24 + 3 * i + j] = (float)(-0.69314718055994530942 * s[i] * pinv[3 * i + j]);      // ln 2
+            fold[30 + i] = (float)(5.48063892334199 * s[i] * (pinv[3 * i] + pinv[3 * i + 1] + pinv[3 * i + 2]));      // ln 240
+        }
+    }
+    tb.fill();
+    __syncthreads();
+    // (the fold is the same for every lane: held in scalar registers, as separate_item's is)
+    auto uniform = [&](int i) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fold[i]))); };
+    float mh[3][3], kh[3], me[3][3], ke[3], ca[2][3], cb[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            mh[c][j] = uniform(c * 3 + j);
+            me[c][j] = uniform(12 + c * 3 + j);
+        }
+        kh[c] = uniform(9 + c);
+        ke[c] = uniform(21 + c);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ca[i][j] = uniform(24 + 3 * i + j);
+        cb[i] = uniform(30 + i);
+    }
+    bool background = false;
+    if constexpr (kMask) background = fold[32] != 0.0f;
+
+    O* hem = a.stains ? static_cast<O*>(a.stains) + tile * 3 * a.pixels : nullptr;
+    O* eos = a.stains ? static_cast<O*>(a.stains) + (a.n_tiles + tile) * 3 * a.pixels : nullptr;
+    float* conc = a.conc ? a.conc + tile * 2 * a.pixels : nullptr;
+
+    __shared__ uint4 stage[(kInter && V > 1 && sizeof(O) * V == 16) ? kStreamThreads * 3 : 1];      // 3 KB per wave: store_pixels_staged()
+    while (p < p_end) {
+        float l[3][V];
+#pragma unroll
+        for (int i = 0; i < V; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) l[c][i] = l2_of<T>(u[c][i], tb);
+        uint32_t in_bits = 0u;
+        if constexpr (kMask) in_bits = background ? 0u : mp.bits();
+        const int64_t q = p;
+        if (hem) {      // (uniform over the launch) the H image's packs, then the E image's
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float (&m)[3][3] = s == 0 ? mh : me;
+                const float (&k)[3] = s == 0 ? kh : ke;
+                O res[3][V];
+#pragma unroll
+                for (int i = 0; i < V; ++i)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float x = fmaf(m[c][2], l[2][i], fmaf(m[c][1], l[1][i], fmaf(m[c][0], l[0][i], k[c])));
+                        const float rgb = fminf(fmaxf(__builtin_amdgcn_exp2f(x), 0.0f), 255.0f);      // :459, :128
+                        if constexpr (kMask) res[c][i] = rgb_to_output<T, O, kUnit>(in_mask(in_bits, i) ? rgb : 240.0f);
+                        else res[c][i] = rgb_to_output<T, O, kUnit>(rgb);
+                    }
+                O* dst = s == 0 ? hem : eos;
+                if constexpr (kInter && V > 1 && sizeof(O) * V == 16) {
+                    if (__builtin_amdgcn_ballot_w64(true) == ~0ull) {      // wave-uniform: every lane has a pack (store_pixels_staged)
+                        store_pixels_staged<O, V>(dst, q, res, stage + (threadIdx.x / kWave) * (3 * kWave));
+                        continue;
+                    }
+                }
+                store_pixels<O, V, kInter>(dst, a.pixels, q, res);
+            }
+        }
+        if (conc) {
+            float cc[2][V];
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const float v = fmaf(ca[s][2], l[2][i], fmaf(ca[s][1], l[1][i], fmaf(ca[s][0], l[0][i], cb[s])));
+                    if constexpr (kMask) cc[s][i] = in_mask(in_bits, i) ? v : 0.0f; else cc[s][i] = v;
+                }
+            if constexpr (kInter) {      // (H, W, 2): the lane's 2 V values side by side
+                if constexpr (V == 1) {
+                    conc[2 * q] = cc[0][0];
+                    conc[2 * q + 1] = cc[1][0];
+                } else {
+                    float flat[2 * V];
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        flat[2 * i] = cc[0][i];
+                        flat[2 * i + 1] = cc[1][i];
+                    }
+                    store_pack_stream<float, 2 * V>(conc + 2 * q, flat);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) store_pack_stream<float, V>(conc + s * a.pixels + q, cc[s]);
+            }
+        }
+        p += (int64_t)TPB * V;
+        if (p < p_end) {      // (the scalar path's work items are sixteen sweeps; the vector paths' a single pack set)
+            load(p, u);
+            if constexpr (kMask) mp.load(msk + p);
+        }
+    }
+}
+
+// sx_macenko_separate_masked / sx_macenko_augment_masked: the tiles' estimates out of the workspace as source rows for
+// separate_apply_kernel / apply_kernel (a null destination is skipped; own basis without maxC: `max_c` null)
+__global__ void export_rows_kernel(const GroupState* __restrict__ state, int64_t n_groups, float* __restrict__ he_a, float* __restrict__ max_c_a, float* __restrict__ he_b,
+                                   float* __restrict__ max_c_b) {
+    const int64_t gidx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (gidx >= n_groups) return;
+    const GroupState& st = state[gidx];
+    for (int i = 0; i < 6; ++i) {
+        const float v = st.he[i];
+        if (he_a) he_a[gidx * 6 + i] = v;
+        if (he_b) he_b[gidx * 6 + i] = v;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (max_c_a) max_c_a[gidx * 2 + i] = st.max_c[i];
+        if (max_c_b) max_c_b[gidx * 2 + i] = st.max_c[i];
+    }
+}
+
 // sx_macenko_estimate: the tile's estimate out of the workspace, as sx_macenko_tile_params reports it
 __global__ void export_estimate_kernel(const GroupState* __restrict__ state, int64_t n_groups, float* __restrict__ he_out, float* __restrict__ max_c_out, float* __restrict__ tissue_out) {
     const int64_t gidx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -3989,6 +4220,62 @@ static int apply_typed(const void* images, void* out, int64_t n_tiles, const App
 #undef SX_RUN_APPLY
 }
 
+// sx_macenko_separate_apply: ONE launch.  The pack is run_separate's (16 bytes of output per lane and plane, sized by the images' element
+// O -- float for a call without images); a work item is ONE pack set per thread on the vector paths, as in run_separate's big batches and
+// run_apply, sixteen sweeps on the scalar path.
+static int64_t separate_apply_chunk(int vr) { return (int64_t)kStreamThreads * vr * (vr == 1 ? 16 : 1); }
+template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
+static int run_separate_apply(const T* images, SeparateApplyArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    a.chunk = (int)separate_apply_chunk(VR);
+    a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
+    hipLaunchKernelGGL((separate_apply_kernel<T, O, VR, kUnit, kInter, kMask>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, a, mk);
+    return check_launch("macenko separate_apply");
+}
+
+// (kMask: sx_macenko_separate_apply_masked -- planar tiles only; the mask's packs are as wide as the pixels', so its pointer has a say in `vec`)
+template <typename T, bool kMask = false>
+static int separate_apply_typed(const void* images, const SeparateApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    const bool stains = a.stains != nullptr;
+    const bool u8_half = stains && sizeof(T) == 1 && out_code != 0;
+    const bool u8_unit = stains && unit && sizeof(T) == 1 && !u8_half;
+    const size_t out_elem = !stains ? sizeof(float) : (u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T)));
+    constexpr int W = PackOf<T>::n;
+    // (16-byte packs where every pointer allows them, as separate_typed decides; the scalar path otherwise)
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(a.stains, out_elem * W)) && (!a.conc || aligned_for(a.conc, 16));
+    if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
+    const T* in = static_cast<const T*>(images);
+#define SX_RUN_SEPA(O, U)                                                                                                                \
+    if constexpr (kMask)                                                                                                                 \
+        return vec ? run_separate_apply<T, O, W, U, false, true>(in, a, stream, mk) : run_separate_apply<T, O, 1, U, false, true>(in, a, stream, mk); \
+    else                                                                                                                                 \
+    return interleaved ? (vec ? run_separate_apply<T, O, W, U, true>(in, a, stream) : run_separate_apply<T, O, 1, U, true>(in, a, stream)) \
+                       : (vec ? run_separate_apply<T, O, W, U, false>(in, a, stream) : run_separate_apply<T, O, 1, U, false>(in, a, stream));
+    if (!stains) {
+        SX_RUN_SEPA(float, false)
+    }
+    if constexpr (sizeof(T) == 1) {
+        if (u8_half && out_code == SX_BF16) {
+            if (unit) { SX_RUN_SEPA(__hip_bfloat16, true) } else { SX_RUN_SEPA(__hip_bfloat16, false) }
+        }
+        if (u8_half) {
+            if (unit) { SX_RUN_SEPA(__half, true) } else { SX_RUN_SEPA(__half, false) }
+        }
+        if (u8_unit) {
+            SX_RUN_SEPA(float, true)
+        }
+        SX_RUN_SEPA(T, false)
+    } else {
+        if (unit) { SX_RUN_SEPA(T, true) } else { SX_RUN_SEPA(T, false) }
+    }
+#undef SX_RUN_SEPA
+}
+
+// Where the masked separation and augmentation keep the source rows between their estimate and their one streaming launch: the head of
+// the all-pixel partial moments (10 doubles per work item, at least one work item per tile: 80 bytes a tile, the rows take 32), which
+// the estimate's plane stage has read by then.
+static float* workspace_rows(const Workspace& ws) { return reinterpret_cast<float*>(ws.partial_all); }
+
 // sx_macenko_estimate: the transform's four-pass estimate with its geometry (transform_typed's, four-pass form), then the export.
 template <typename T>
 static int estimate_typed(const void* images, const Geometry& g0, const Workspace& ws, float* he_out, float* max_c_out, float* tissue_out, hipStream_t stream) {
@@ -4029,9 +4316,9 @@ static int fit_typed(const void* images, const Geometry& g0, const Workspace& ws
 // The geometry is the unmasked four-pass call's (transform_typed / estimate_typed / fit_typed), so that a mask of all ones has its bits;
 // 16-byte pixel packs need a mask pointer aligned to the pack's pixels as well (the scalar path serves everything else).
 template <typename T>
-static void masked_geometry(Geometry& g, const void* images, const void* out, size_t out_elem, const uint8_t* mask, bool per_tile) {
+static void masked_geometry(Geometry& g, const void* images, const void* out, size_t out_elem, const uint8_t* mask, bool per_tile, bool outputs_aligned = true) {
     constexpr int W = PackOf<T>::n;
-    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (out == nullptr || aligned_for(out, out_elem * W)) && aligned_for(mask, W);
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (out == nullptr || aligned_for(out, out_elem * W)) && aligned_for(mask, W) && outputs_aligned;
     g.vec = vec ? 1 : 0;
     g.vec_width = W;
     set_sampling(g, per_tile);
@@ -4094,6 +4381,24 @@ static int transform_masked_typed(const void* images, void* out, const Geometry&
     }
     SX_RUN_MASKED(T)
 #undef SX_RUN_MASKED
+}
+
+// sx_macenko_separate_masked / sx_macenko_augment_masked: the masked per-tile estimate (sx_macenko_estimate_masked's launches, with the
+// geometry of the unmasked sibling so that a mask of all ones has its bits), the rows exported, then the given-basis kernel over them.
+template <typename T>
+static int estimate_rows_masked(const void* images, const Geometry& g0, const Workspace& ws, const uint8_t* mask, bool outputs_aligned, float* he_b, float* max_c_b, hipStream_t stream) {
+    Geometry g = g0;
+    constexpr int W = PackOf<T>::n;
+    masked_geometry<T>(g, images, nullptr, 0, mask, true, outputs_aligned);
+    const T* in = static_cast<const T*>(images);
+    const MaskArgs<true> mk{mask};
+    const int rc = g.vec ? run_estimate<T, W, false, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream, mk)
+                         : run_estimate<T, 1, false, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream, mk);
+    if (rc != SX_OK) return rc;
+    float* rows = workspace_rows(ws);
+    hipLaunchKernelGGL(export_rows_kernel, dim3((unsigned)((g.n_tiles + 63) / 64)), dim3(64), 0, stream, ws.state, g.n_tiles, rows, g.own_basis ? nullptr : rows + 6 * g.n_tiles, he_b,
+                       g.own_basis ? nullptr : max_c_b);
+    return check_launch("macenko export_rows");
 }
 
 // ---- distributed pooled fit on the bracket machinery (sx_macenko_pfit_*) ---------------------------------
@@ -4781,6 +5086,165 @@ extern "C" int sx_macenko_apply_masked(const void* images, void* out, int dtype,
         case SX_F32: return apply_typed<float, true>(images, out, n, a, out_code, false, unit, stream, mk);
         case SX_F64: return apply_typed<double, true>(images, out, n, a, out_code, false, unit, stream, mk);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+// ---- separation and augmentation: given source basis, tissue masks ----
+// The argument checks sx_macenko_separate_apply and its masked form share (everything but the flags and the mask).
+static int separate_apply_args_ok(const void* images, const void* stains_out, const float* conc_out, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c,
+                                  int64_t n_sources, const float* sm, const float* tmc) {
+    if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    if (!stains_out && !conc_out) return fail(SX_ERR_BAD_ARG, "stains_out and conc_out are both null: nothing to separate into");
+    if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalised) or both null (own basis)");
+    if (sm && !source_max_c) return fail(SX_ERR_BAD_ARG, "source_max_c pointer is null (it may be null in own-basis mode only)");
+    return SX_OK;
+}
+
+template <bool kMask>
+static int separate_apply_dispatch(const void* images, int dtype, const SeparateApplyArgs& a, unsigned flags, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    switch (dtype) {
+        case SX_U8: return separate_apply_typed<uint8_t, kMask>(images, a, out_code, inter, unit, stream, mk);
+        case SX_F16: return separate_apply_typed<__half, kMask>(images, a, out_code, inter, unit, stream, mk);
+        case SX_BF16: return separate_apply_typed<__hip_bfloat16, kMask>(images, a, out_code, inter, unit, stream, mk);
+        case SX_F32: return separate_apply_typed<float, kMask>(images, a, out_code, inter, unit, stream, mk);
+        case SX_F64: return separate_apply_typed<double, kMask>(images, a, out_code, inter, unit, stream, mk);
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+}
+
+static SeparateApplyArgs separate_apply_args(void* stains_out, float* conc_out, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources,
+                                             const float* sm, const float* tmc) {
+    SeparateApplyArgs a{};
+    a.he = source_he;
+    a.max_c = source_max_c;
+    a.sm = sm;
+    a.tmc = tmc;
+    a.stains = stains_out;
+    a.conc = conc_out;
+    a.pixels = h * w;
+    a.n_tiles = n;
+    a.per_tile = n_sources == n && n != 1 ? 1 : 0;
+    return a;
+}
+
+// Separate with a GIVEN source basis: separate_apply_kernel, one launch on `stream`, nothing else enqueued, no workspace.
+extern "C" int sx_macenko_separate_apply(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he,
+                                         const float* source_max_c, int64_t n_sources, const float* sm, const float* tmc, unsigned flags, void* stream_ptr) {
+    const int rc = separate_apply_args_ok(images, stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc);
+    if (rc != SX_OK) return rc;
+    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_separate_apply takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
+    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
+        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    return separate_apply_dispatch<false>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr));
+}
+
+extern "C" int sx_macenko_separate_apply_masked(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he,
+                                                const float* source_max_c, int64_t n_sources, const float* sm, const float* tmc, const unsigned char* mask_dev, unsigned flags,
+                                                void* stream_ptr) {
+    int rc = separate_apply_args_ok(images, stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc);
+    if (rc != SX_OK) return rc;
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_separate_apply_masked", false);
+    if (rc != SX_OK) return rc;
+    return separate_apply_dispatch<true>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr),
+                                         MaskArgs<true>{mask_dev});
+}
+
+// sx_macenko_separate with a tissue mask: the masked per-tile estimate, its rows exported (to the caller's tile_he_out / tile_max_c_out as
+// well), then separate_apply_kernel<kMask> over them: what sx_macenko_estimate_masked followed by sx_macenko_separate_apply_masked runs.
+extern "C" int sx_macenko_separate_masked(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* sm,
+                                          const float* tmc, float* tile_he_out, float* tile_max_c_out, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_separate_masked");
+    if (rc != SX_OK) return rc;
+    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (!stains_out && !conc_out) return fail(SX_ERR_BAD_ARG, "stains_out and conc_out are both null: nothing to separate into");
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalised) or both null (own basis)");
+    Geometry g = make_geometry(n, h * w, 0);
+#ifdef SX_DIAG
+    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
+#endif
+    g.own_basis = (sm == nullptr && tile_max_c_out == nullptr) ? 1 : 0;      // (as sx_macenko_separate: maxC asked for in own basis runs the whole estimate)
+    const Workspace ws = carve(ws_ptr, n, g.pixels);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    // (the estimate's packs as the separation's: 16-byte packs where every pointer of the call allows them)
+    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    const int in_elem = dtype == SX_U8 ? 1 : (dtype == SX_F16 || dtype == SX_BF16) ? 2 : dtype == SX_F32 ? 4 : 8;
+    const size_t out_elem = (dtype == SX_U8 && out_code != 0) ? 2 : ((dtype == SX_U8 && unit) ? sizeof(float) : (size_t)in_elem);
+    const bool outs_ok = (!stains_out || aligned_for(stains_out, out_elem * (16 / in_elem))) && (!conc_out || aligned_for(conc_out, 16));
+    switch (dtype) {
+        case SX_U8: rc = estimate_rows_masked<uint8_t>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
+        case SX_F16: rc = estimate_rows_masked<__half>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
+        case SX_BF16: rc = estimate_rows_masked<__hip_bfloat16>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
+        case SX_F32: rc = estimate_rows_masked<float>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
+        case SX_F64: rc = estimate_rows_masked<double>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+    if (rc != SX_OK) return rc;
+    const float* rows = workspace_rows(ws);
+    return separate_apply_dispatch<true>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, rows, rows + 6 * n, n, sm, tmc), flags & ~SX_MACENKO_CLASSIC, stream, MaskArgs<true>{mask_dev});
+}
+
+// sx_macenko_augment with a tissue mask: the masked per-tile estimate (own basis: without the concentration bracket pass and the scale
+// stage), its rows exported, then apply_kernel<kMask> over them with the factors: masked-out pixels, and tiles without an estimate, are
+// copied by sx_macenko_transform_masked's background rule.
+extern "C" int sx_macenko_augment_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* alpha, const float* beta,
+                                         const float* sm, const float* tmc, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_augment_masked");
+    if (rc != SX_OK) return rc;
+    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (!out || !alpha || !beta) return fail(SX_ERR_BAD_ARG, "out / alpha / beta pointer is null");
+    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise and jitter) or both null (own basis)");
+    Geometry g = make_geometry(n, h * w, 0);
+#ifdef SX_DIAG
+    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
+#endif
+    g.own_basis = sm == nullptr ? 1 : 0;
+    const Workspace ws = carve(ws_ptr, n, g.pixels);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
+    const int in_elem = dtype == SX_U8 ? 1 : (dtype == SX_F16 || dtype == SX_BF16) ? 2 : dtype == SX_F32 ? 4 : 8;
+    const size_t out_elem = (dtype == SX_U8 && out_code != 0) ? 2 : ((dtype == SX_U8 && unit) ? sizeof(float) : (size_t)in_elem);
+    const bool outs_ok = aligned_for(out, out_elem * (16 / in_elem));      // (the estimate's packs as sx_macenko_transform_masked decides them)
+    switch (dtype) {
+        case SX_U8: rc = estimate_rows_masked<uint8_t>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
+        case SX_F16: rc = estimate_rows_masked<__half>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
+        case SX_BF16: rc = estimate_rows_masked<__hip_bfloat16>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
+        case SX_F32: rc = estimate_rows_masked<float>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
+        case SX_F64: rc = estimate_rows_masked<double>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+    if (rc != SX_OK) return rc;
+    const float* rows = workspace_rows(ws);
+    ApplyArgs a{};
+    a.he = rows;
+    a.max_c = rows + 6 * n;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.sm = sm;
+    a.tmc = tmc;
+    a.pixels = h * w;
+    a.per_tile = n != 1 ? 1 : 0;
+    const MaskArgs<true> mk{mask_dev};
+    switch (dtype) {
+        case SX_U8: return apply_typed<uint8_t, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_F16: return apply_typed<__half, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_BF16: return apply_typed<__hip_bfloat16, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        case SX_F32: return apply_typed<float, true>(images, out, n, a, out_code, false, unit, stream, mk);
+        default: return apply_typed<double, true>(images, out, n, a, out_code, false, unit, stream, mk);
     }
 }
 

@@ -52,8 +52,8 @@ class Macenko(NormalizerTemplate):
     the rule (pen marks, folds, an annotated region).  For Macenko the rule is a ``tissue_mask()`` launch in front of the masked call
     -- one extra streaming pass over the images and its bytes; an explicit mask costs only its own bytes.  A tile with fewer than 3
     masked-in pixels has no estimate (NaN rows) and is copied through; the edge is hard.  A masked call always runs the exact four-pass
-    form (``precision="sampled"`` with a mask is a ``ValueError``).  ``separate`` and ``MacenkoAugment`` take no masks.  ``mask=None``
-    runs exactly the unmasked code."""
+    form (``precision="sampled"`` with a mask is a ``ValueError``).  ``separate`` goes through the same rule (a masked-out pixel holds no
+    stain) and ``MacenkoAugment`` has ``mask=`` of its own.  ``mask=None`` runs exactly the unmasked code."""
 
     engine = "MacenkoHIP"
     fitted_slots = ("_stain_matrix", "_target_max_conc", "_concentration_matrix")      # (3,2), (2,), unused
@@ -123,13 +123,20 @@ class Macenko(NormalizerTemplate):
             raise ValueError("Must call fit() before transform()")
         return self._get_backend_impl().transform_masked(images, *self.arguments(), explicit, self.luminosity_threshold, **self.call_options())
 
-    def separate(self, images: Any, *, stains: bool = True, concentrations: bool = False, own_basis: bool | None = None) -> StainSeparation:
+    def separate(self, images: Any, *, stains: bool = True, concentrations: bool = False, own_basis: bool | None = None, source: Any = None, mask: Any = None) -> StainSeparation:
         """Split every tile of ``images`` (NCHW) into its hematoxylin and eosin parts, with the transform's per-tile estimate.
 
         ``own_basis=None``: each tile's own stain basis while the normaliser is unfitted, the fitted reference once it is fitted --
         then ``C' = C * target_max_conc / maxC`` and the images are built with the reference's stain matrix (torchstain's ``H`` and
         ``E``).  ``own_basis=True`` forces the tile's own basis; ``False`` requires a fit.  The images follow ``normalize_to_0_1`` and
-        ``output_dtype`` as ``transform`` does.  One library call (include/stainx_hip.h: sx_macenko_separate)."""
+        ``output_dtype`` as ``transform`` does.  One library call (include/stainx_hip.h: sx_macenko_separate).
+
+        ``source`` (what ``apply`` takes: a ``StainEstimate``, a ``StainSeparation`` or a ``(stain_matrices, max_concentrations)``
+        pair, one row or N): separate with that GIVEN basis instead of each tile's own estimate -- one kernel launch, no estimate
+        (sx_macenko_separate_apply); the returned ``stain_matrices`` / ``max_concentrations`` are the given ones, broadcast to N.
+        With a mask (the normaliser's rule, or ``mask=`` for this call: a tensor or ``"luminosity"``) the estimate is taken over the
+        masked-in pixels only, and a masked-out pixel -- and every pixel of a tile without an estimate -- holds no stain:
+        concentrations 0, both images the level of zero concentration (240, typed and scaled as the tissue's levels)."""
         if not (stains or concentrations):
             raise ValueError("separate: ask for stains, concentrations or both")
         if self._precision == "sampled":
@@ -141,8 +148,18 @@ class Macenko(NormalizerTemplate):
         shape = tuple(getattr(images, "shape", ()))
         if len(shape) != 4 or shape[1] != 3:
             raise ValueError(f"Macenko separate expects NCHW images with C=3, got shape {shape}")
-        reference = () if own_basis else (self._stain_matrix, self._target_max_conc)
-        out = self._get_backend_impl().separate(images, *reference, stains=stains, concentrations=concentrations, **self.call_options())
+        given = None if source is None else self._check_source(source, shape[0], need_max_c=not own_basis)
+        masked, explicit = self._masking(images, mask, "separate")
+        reference = (None, None) if own_basis else (self._stain_matrix, self._target_max_conc)
+        engine = self._get_backend_impl()
+        if given is not None and masked:
+            out = engine.separate_apply_masked(images, *given, *reference, explicit, self.luminosity_threshold, stains=stains, concentrations=concentrations, **self.call_options())
+        elif given is not None:
+            out = engine.separate_apply(images, *given, *reference, stains=stains, concentrations=concentrations, **self.call_options())
+        elif masked:
+            out = engine.separate_masked(images, *reference, explicit, self.luminosity_threshold, stains=stains, concentrations=concentrations, **self.call_options())
+        else:
+            out = engine.separate(images, *reference, stains=stains, concentrations=concentrations, **self.call_options())
         images_out = out["stains"]
         return StainSeparation(images_out[0] if images_out is not None else None, images_out[1] if images_out is not None else None,
                                out["concentrations"], out["he"], out["max_c"])
@@ -170,6 +187,29 @@ class Macenko(NormalizerTemplate):
         out = engine.estimate(images)
         return StainEstimate(out["he"], out["max_c"], out["tissue"])
 
+    @staticmethod
+    def _check_source(source: Any, n: int, need_max_c: bool) -> tuple[Any, Any]:
+        """``(stain_matrices, max_concentrations)`` of a given source basis for ``n`` tiles (``apply`` and ``separate`` take the same),
+        with its shape checks -- before any GPU work."""
+        if isinstance(source, (StainEstimate, StainSeparation)):
+            he, max_c = source.stain_matrices, source.max_concentrations
+        elif isinstance(source, (tuple, list)) and len(source) == 2:
+            he, max_c = source
+        else:
+            raise ValueError("source must be a StainEstimate, a StainSeparation or a (stain_matrices, max_concentrations) pair")
+        he_shape = tuple(getattr(he, "shape", ()))
+        if not (he_shape == (3, 2) or (len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n))):
+            raise ValueError(f"source stain_matrices must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
+        n_sources = 1 if len(he_shape) == 2 else he_shape[0]
+        if max_c is None:
+            if need_max_c:
+                raise ValueError("source carries no max_concentrations (a separation in its own basis?): they are needed to normalise to the reference")
+        else:
+            mc_shape = tuple(getattr(max_c, "shape", ()))
+            if mc_shape != (n_sources, 2) and not (len(he_shape) == 2 and mc_shape == (2,)):
+                raise ValueError(f"source max_concentrations must have shape ({n_sources}, 2) to match stain_matrices {he_shape}, got {mc_shape}")
+        return he, max_c
+
     def apply(self, images: Any, source: Any, *, alpha: Any | None = None, beta: Any | None = None, own_basis: bool = False, mask: Any = None) -> Any:
         """Normalise ``images`` (NCHW) to the fitted reference with a GIVEN source basis instead of each tile's own estimate: one
         kernel launch, a pixel read and a pixel written (include/stainx_hip.h: sx_macenko_apply).
@@ -190,24 +230,8 @@ class Macenko(NormalizerTemplate):
         shape = tuple(getattr(images, "shape", ()))
         if len(shape) != 4 or shape[1] != 3:
             raise ValueError(f"Macenko apply expects NCHW images with C=3, got shape {shape}")
-        if isinstance(source, (StainEstimate, StainSeparation)):
-            he, max_c = source.stain_matrices, source.max_concentrations
-        elif isinstance(source, (tuple, list)) and len(source) == 2:
-            he, max_c = source
-        else:
-            raise ValueError("source must be a StainEstimate, a StainSeparation or a (stain_matrices, max_concentrations) pair")
         n = shape[0]
-        he_shape = tuple(getattr(he, "shape", ()))
-        if not (he_shape == (3, 2) or (len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n))):
-            raise ValueError(f"source stain_matrices must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
-        n_sources = 1 if len(he_shape) == 2 else he_shape[0]
-        if max_c is None:
-            if not own_basis:
-                raise ValueError("source carries no max_concentrations (a separation in its own basis?): they are needed to normalise to the reference")
-        else:
-            mc_shape = tuple(getattr(max_c, "shape", ()))
-            if mc_shape != (n_sources, 2) and not (len(he_shape) == 2 and mc_shape == (2,)):
-                raise ValueError(f"source max_concentrations must have shape ({n_sources}, 2) to match stain_matrices {he_shape}, got {mc_shape}")
+        he, max_c = self._check_source(source, n, need_max_c=not own_basis)
         for name, factor in (("alpha", alpha), ("beta", beta)):
             if factor is not None and tuple(getattr(factor, "shape", ())) != (n, 2):
                 raise ValueError(f"{name} must have shape (N, 2) = ({n}, 2), got {tuple(getattr(factor, 'shape', ()))}")
