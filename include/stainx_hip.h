@@ -285,6 +285,51 @@ int sx_macenko_augment_masked(const void* images_dev, void* out_dev, int dtype, 
                               const float* alpha_dev, const float* beta_dev, const float* stain_matrix_dev, const float* target_max_conc_dev,
                               unsigned flags, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- three-stain colour deconvolution with a GIVEN basis (Ruifrok & Johnston: HED, H-DAB, a complemented H&E estimate) ----
+ * An extension (HistomicsTK color_deconvolution, scikit-image rgb2hed / hed2rgb): no estimate at all.  The conventions are the Macenko
+ * calls': optical density OD_c = -ln((255 x_c + 1) / 240) of the unit value x (uint8: x = u / 255), reconstruction
+ * level_c = clamp(240 exp(-OD'_c), 0, 255) cast to the output element by sx_macenko_transform's rules.
+ *   basis_dev   n_bases x 9 floats: a basis is (3, 3) row-major as [channel][stain] -- columns are stain vectors, as HE's (3, 2);
+ *               n_bases is 1 (one basis for the batch) or n_tiles (row t serves tile t)
+ *   C = inverse(basis) OD            three concentrations per pixel; a 3 x 3 basis is invertible, so nothing of OD is dropped
+ * Every call is ONE kernel launch on `stream`: nothing else enqueued, no workspace, no host synchronisation, capturable.  Bases, factors
+ * and masks are DEVICE memory read by the kernel (a captured graph replayed after new values were written into the same buffers uses
+ * the new values).  The inverse is the closed form in fp64 on the device; a SINGULAR basis is NOT detected: its coefficients are Inf /
+ * NaN and so are the levels, which the clamp and the casts treat as the Macenko kernels treat them (undefined pixel values, no error).
+ * Flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_CHANNELS_LAST, SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 (uint8 input, one of the two) with
+ * their meaning in sx_macenko_apply, SX_MACENKO_CLASSIC (a no-op); any other bit is SX_ERR_BAD_ARG.  All argument errors -- a NULL
+ * required pointer, n_bases / n_targets not 1 or n_tiles, one factor pointer without the other, bad flags, SX_MACENKO_CHANNELS_LAST on the
+ * masked call -- are SX_ERR_BAD_ARG with a message, before anything is enqueued.
+ *
+ * sx_deconv_apply:  C' = alpha * C + beta,  OD' = B_out C'  -- one streaming pass, a pixel read, a pixel written.
+ *   target_basis_dev     n_targets x 9 floats (n_targets 1 or n_tiles): B_out; NULL: the source basis (n_targets is then ignored)
+ *   alpha_dev, beta_dev  n_tiles x 3 floats each, per tile and stain; both or neither (neither: alpha = 1, beta = 0 -- with
+ *                        no target the call then rebuilds its input up to rounding) */
+int sx_deconv_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                    const float* basis_dev, int64_t n_bases, const float* target_basis_dev, int64_t n_targets,
+                    const float* alpha_dev, const float* beta_dev, unsigned flags, void* stream);
+/* sx_deconv_apply_masked: the same under an explicit mask (N, H, W), one byte per pixel, non-zero = in (what sx_tissue_mask writes);
+ * planar tiles only.  A masked-out pixel is COPIED by sx_macenko_transform_masked's background rule (its input level through the tissue
+ * pixels' clamp, cast and / 255: uint8 in, uint8 out is byte-identical there); a tile whose basis row -- or target row, if given --
+ * holds a NaN is copied entirely.  Values under masked-out pixels never matter (every use is a select).  The mask is read in packs as
+ * wide as the pixel packs where the image pointers, the tile size AND the mask pointer allow it.  All ones: sx_deconv_apply's bits. */
+int sx_deconv_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                           const float* basis_dev, int64_t n_bases, const float* target_basis_dev, int64_t n_targets,
+                           const float* alpha_dev, const float* beta_dev, const unsigned char* mask_dev, unsigned flags, void* stream);
+/* sx_deconv_separate: a pixel is read once; either output may be NULL, not both.
+ *   stains_out_dev  (3, N, 3, H, W) of the output element ((3, N, H, W, 3) with SX_MACENKO_CHANNELS_LAST): image i is the tile rebuilt
+ *                   from stain i alone, clamp(240 exp(-basis[:, i] C_i)) -- the BITS of sx_deconv_apply with alpha = e_i, beta = 0
+ *   conc_out_dev    (N, 3, H, W) float32 ((N, H, W, 3)): C */
+int sx_deconv_separate(const void* images_dev, void* stains_out_dev, float* conc_out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                       const float* basis_dev, int64_t n_bases, unsigned flags, void* stream);
+/* sx_deconv_combine: sx_deconv_separate's inverse -- a tile rebuilt from (N, 3, H, W) float32 concentrations ((N, H, W, 3) with
+ * SX_MACENKO_CHANNELS_LAST, then the output too): out = clamp(240 exp(-basis C), 0, 255) cast to out_dtype (any sx_dtype; uint8
+ * truncates as the transform does).  Flags: SX_MACENKO_NORMALIZE_0_1 (fuses / 255; float outputs only -- with uint8 output it is
+ * SX_ERR_BAD_ARG), SX_MACENKO_CHANNELS_LAST, SX_MACENKO_CLASSIC (a no-op).  Editing the concentrations in between -- a stain dropped
+ * or rescaled -- is what the pair is for. */
+int sx_deconv_combine(const float* conc_dev, void* out_dev, int out_dtype, int64_t n_tiles, int64_t height, int64_t width,
+                      const float* basis_dev, int64_t n_bases, unsigned flags, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

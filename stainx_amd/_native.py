@@ -64,6 +64,11 @@ SIGNATURES = {
     "sx_macenko_separate_apply_masked": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _uint, _vp]),
     "sx_macenko_separate_masked": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_macenko_augment_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    # three-stain colour deconvolution with a given (3, 3) basis: one launch each, no workspace
+    "sx_deconv_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _uint, _vp]),
+    "sx_deconv_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _uint, _vp]),
+    "sx_deconv_separate": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
+    "sx_deconv_combine": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

@@ -948,6 +948,129 @@ class MacenkoHIP(TorchHIPBackendBase):
                 "n_candidates": raw[:, 19:23].long(), "cov": raw[:, 23:32].reshape(-1, 3, 3), "stamps_us": raw[:, 32:48]}
 
 
+class DeconvHIP(TorchHIPBackendBase):
+    """Three-stain colour deconvolution with a GIVEN (3, 3) basis (include/stainx_hip.h: sx_deconv_*): one kernel launch per call, no
+    estimate, no workspace, no host synchronisation.  Bases, factors and masks are read on the device: a captured call replayed after
+    new values are copied into the same tensors uses the new values."""
+
+    def _bases(self, basis: torch.Tensor, n: int, what: str) -> tuple[torch.Tensor, int]:
+        shape = tuple(basis.shape)
+        if shape == (3, 3):
+            rows = 1
+        elif len(shape) == 3 and shape[1:] == (3, 3) and shape[0] in (1, n):
+            rows = shape[0]
+        else:
+            raise ValueError(f"{what} must have shape (3, 3), (1, 3, 3) or (N, 3, 3) = ({n}, 3, 3), got {shape}")
+        return self._f32(basis), rows
+
+    @staticmethod
+    def _dims(images: torch.Tensor, channels_last: bool, what: str) -> tuple[int, int, int]:
+        if images.dim() != 4 or images.shape[3 if channels_last else 1] != 3:
+            raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {tuple(images.shape)}")
+        return (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
+
+    @staticmethod
+    def _out_flags(images: torch.Tensor, out_dtype: torch.dtype | None, normalize_to_0_1: bool, channels_last: bool) -> tuple[int, torch.dtype]:
+        flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+        if out_dtype is not None and out_dtype != images.dtype:
+            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+            return flags | (_native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16), out_dtype
+        return flags, torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+
+    def apply(self, images: torch.Tensor, basis: torch.Tensor, target: torch.Tensor | None = None, *, alpha: torch.Tensor | None = None,
+              beta: torch.Tensor | None = None, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False,
+              masking: tuple | None = None) -> torch.Tensor:
+        """``C' = alpha * inverse(basis) OD + beta`` rebuilt with ``target`` (None: ``basis``).  ``basis`` / ``target``: (3, 3), (1, 3, 3)
+        or (N, 3, 3); ``alpha`` / ``beta``: (N, 3), both or neither.  ``masking``: None, or ``(explicit mask or None, luminosity
+        threshold)`` -- the masked call (planar tiles only); the rule's mask is an ``sx_tissue_mask`` launch in front."""
+        images = images.to(self.device)
+        n, h, w = self._dims(images, channels_last, "apply")
+        _dtype_code(images)
+        flags, out_dtype = self._out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together: both or neither")
+        if masking is not None and channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
+        b, n_bases = self._bases(basis, n, "basis")
+        t, n_targets = (None, 0) if target is None else self._bases(target, n, "target")
+        fa = fb = None
+        if alpha is not None:
+            if tuple(alpha.shape) != (n, 3) or tuple(beta.shape) != (n, 3):
+                raise ValueError(f"alpha and beta must have shape (N, 3) = ({n}, 3), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+            fa, fb = self._f32(alpha), self._f32(beta)
+        mask = None
+        if masking is not None and masking[0] is not None:
+            mask = _mask_bytes(masking[0], self.device)
+            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
+                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+        images = images.contiguous()
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+
+        def ptr(x):
+            return x.data_ptr() if x is not None else None
+
+        code, stream = _dtype_code(images), _native.stream_ptr(self.device)
+        with _native.on_device(self.device):
+            if masking is not None:
+                if mask is None:
+                    mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+                    rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
+                    _native.check(rc, "sx_tissue_mask", self._lib)
+                rc = self._lib.sx_deconv_apply_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, ptr(t), n_targets, ptr(fa), ptr(fb),
+                                                      mask.data_ptr(), flags, stream)
+                _native.check(rc, "sx_deconv_apply_masked", self._lib)
+            else:
+                rc = self._lib.sx_deconv_apply(images.data_ptr(), out.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, ptr(t), n_targets, ptr(fa), ptr(fb), flags, stream)
+                _native.check(rc, "sx_deconv_apply", self._lib)
+        return out
+
+    def separate(self, images: torch.Tensor, basis: torch.Tensor, *, stains: bool = True, concentrations: bool = False, normalize_to_0_1: bool = False,
+                 out_dtype: torch.dtype | None = None, channels_last: bool = False) -> tuple[torch.Tensor | None, torch.Tensor | None]:
+        """``(images (3, N, ...) or None, concentrations (N, 3, H, W) / (N, H, W, 3) float32 or None)``: image i is the tile rebuilt from
+        stain i alone -- the bits of ``apply`` with ``alpha = e_i``."""
+        images = images.to(self.device)
+        n, h, w = self._dims(images, channels_last, "separate")
+        if not stains and not concentrations:
+            raise ValueError("separate: ask for the stain images, the concentrations, or both")
+        _dtype_code(images)
+        flags, out_dtype = self._out_flags(images, out_dtype if stains else None, normalize_to_0_1 and stains, channels_last)
+        b, n_bases = self._bases(basis, n, "basis")
+        images = images.contiguous()
+        imgs = torch.empty((3,) + tuple(images.shape), dtype=out_dtype, device=self.device) if stains else None
+        conc = torch.empty((n, h, w, 3) if channels_last else (n, 3, h, w), dtype=torch.float32, device=self.device) if concentrations else None
+        if n == 0 or h * w == 0:
+            return imgs, conc
+        with _native.on_device(self.device):
+            rc = self._lib.sx_deconv_separate(images.data_ptr(), imgs.data_ptr() if stains else None, conc.data_ptr() if concentrations else None, _dtype_code(images),
+                                              n, h, w, b.data_ptr(), n_bases, flags, _native.stream_ptr(self.device))
+            _native.check(rc, "sx_deconv_separate", self._lib)
+        return imgs, conc
+
+    def combine(self, concentrations: torch.Tensor, basis: torch.Tensor, *, out_dtype: torch.dtype = torch.uint8, normalize_to_0_1: bool = False,
+                channels_last: bool = False) -> torch.Tensor:
+        """``separate``'s inverse: (N, 3, H, W) float32 concentrations (NHWC with ``channels_last``) -> the tile, cast to ``out_dtype``."""
+        n, h, w = self._dims(concentrations, channels_last, "combine")
+        if concentrations.dtype != torch.float32:
+            raise ValueError(f"concentrations must be float32, got {concentrations.dtype}")
+        if out_dtype not in _native.DTYPE_CODES:
+            raise TypeError(f"unsupported out_dtype {out_dtype}; supported: {sorted(str(d) for d in _native.DTYPE_CODES)}")
+        if normalize_to_0_1 and out_dtype == torch.uint8:
+            raise ValueError("normalize_to_0_1 needs a float out_dtype (uint8 output stays on 0-255)")
+        b, n_bases = self._bases(basis, n, "basis")
+        conc = concentrations.to(self.device).contiguous()
+        out = torch.empty(tuple(conc.shape), dtype=out_dtype, device=self.device)
+        if n == 0 or h * w == 0:
+            return out
+        flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+        with _native.on_device(self.device):
+            rc = self._lib.sx_deconv_combine(conc.data_ptr(), out.data_ptr(), _native.DTYPE_CODES[out_dtype], n, h, w, b.data_ptr(), n_bases, flags, _native.stream_ptr(self.device))
+            _native.check(rc, "sx_deconv_combine", self._lib)
+        return out
+
+
 class ReinhardHIP(TorchHIPBackendBase):
     """Reinhard LAB statistics matching on the GPU (numerics of ReinhardTorch, torch_backend.py:304-355)."""
 

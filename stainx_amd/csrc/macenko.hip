@@ -5492,3 +5492,6 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
     }
     return check_launch("macenko pfit finish");
 }
+
+// Three-stain colour deconvolution with a given basis (sx_deconv_*): kernels, launchers and entry points, on the helpers above.
+#include "deconv.hpp"

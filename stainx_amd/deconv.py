@@ -1,0 +1,291 @@
+"""Three-stain colour deconvolution with a GIVEN basis (an extension: the reference has none).
+
+Ruifrok & Johnston's colour deconvolution as HistomicsTK's ``color_deconvolution``, scikit-image's ``rgb2hed`` / ``hed2rgb`` and the
+fixed-matrix augmentors of tiatoolbox / torchstain offer it: the optical density of a pixel is split into THREE stain concentrations
+by the inverse of a fixed (3, 3) basis -- no estimate, so it serves IHC slides (haematoxylin + DAB) that Macenko's H&E estimate does
+not, and it is lossless: the concentrations can be edited and the tile rebuilt.  ``ColorDeconvolution`` separates, applies
+(``C' = alpha * C + beta``, optionally rebuilt with another basis) and combines; ``HEDAugment`` is the "HED-light" jitter of Tellez et
+al. as an ``nn.Module``.  The conventions are the Macenko calls' (``OD = -ln((255 x + 1) / 240)``, ``level = clamp(240 exp(-OD'))``), so
+an estimated H&E basis, complemented (``StainEstimate.complement()``), feeds the same path with the residual as a channel of its own.
+One kernel launch per call (include/stainx_hip.h: sx_deconv_*).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Any
+
+import torch
+import torch.nn as nn
+
+from stainx_amd import masks
+
+# (H, E or DAB, third) as Ruifrok & Johnston tabulate them; a missing third vector is the complement of the first two
+_NAMED = {
+    "hed": ((0.65, 0.70, 0.29), (0.07, 0.99, 0.11), (0.27, 0.57, 0.78)),
+    "he": ((0.644211, 0.716556, 0.266844), (0.092789, 0.954111, 0.283111), None),
+    "hdab": ((0.650, 0.704, 0.286), (0.268, 0.570, 0.776), None),
+}
+BASIS_NAMES = tuple(_NAMED)
+
+
+def complement_basis(he: torch.Tensor) -> torch.Tensor:
+    """``(..., 3, 2)`` stain vectors (columns, as ``HE_source``) -> ``(..., 3, 3)``: the two columns as they are, the third their
+    normalised cross product (HistomicsTK's ``complement_stain_matrix``) -- orthogonal to both, unit length, right-handed.  So the
+    first two rows of the inverse are the pseudo-inverse of ``he``, and the third concentration is the residual the rank-2 path drops.
+    Plain tensor arithmetic on the tensor's device (no synchronisation)."""
+    if not isinstance(he, torch.Tensor) or he.dim() < 2 or tuple(he.shape[-2:]) != (3, 2):
+        raise ValueError(f"complement_basis expects (..., 3, 2) stain vectors, got {tuple(getattr(he, 'shape', ()))}")
+    he = he.to(torch.float32)
+    third = torch.linalg.cross(he[..., 0], he[..., 1], dim=-1)
+    third = third / torch.linalg.vector_norm(third, dim=-1, keepdim=True)
+    return torch.cat([he, third.unsqueeze(-1)], dim=-1)
+
+
+def stain_basis(name_or_matrix: Any) -> torch.Tensor:
+    """A (3, 3) float32 basis, ``[channel][stain]``, with unit-length columns: one of the built-in names -- ``"hed"`` (Ruifrok &
+    Johnston's haematoxylin, eosin, DAB), ``"he"`` and ``"hdab"`` (two stains and their complement) -- or a given matrix.  A CPU
+    matrix is checked here (shape (3, 3) or (N, 3, 3), finite, non-zero determinant) and its columns normalised; a device tensor is
+    taken as it is, with no synchronisation (a singular basis is not detected on the device: the result is then undefined)."""
+    if isinstance(name_or_matrix, str):
+        if name_or_matrix not in _NAMED:
+            raise ValueError(f"unknown stain basis {name_or_matrix!r}; built in: {list(BASIS_NAMES)} (or pass a (3, 3) matrix)")
+        first, second, third = _NAMED[name_or_matrix]
+        cols = torch.tensor([first, second], dtype=torch.float64).T      # (3, 2)
+        cols = cols / torch.linalg.vector_norm(cols, dim=0, keepdim=True)
+        if third is None:
+            c = torch.linalg.cross(cols[:, 0], cols[:, 1])
+        else:
+            c = torch.tensor(third, dtype=torch.float64)
+        c = c / torch.linalg.vector_norm(c)
+        return torch.cat([cols, c.unsqueeze(1)], dim=1).to(torch.float32)
+    m = name_or_matrix
+    if not isinstance(m, torch.Tensor):
+        try:
+            m = torch.as_tensor(m, dtype=torch.float32)
+        except Exception:
+            raise ValueError(f"a stain basis is a name ({list(BASIS_NAMES)}) or a (3, 3) matrix, got {type(name_or_matrix).__name__}") from None
+    if not (tuple(m.shape) == (3, 3) or (m.dim() == 3 and tuple(m.shape[1:]) == (3, 3) and m.shape[0] >= 1)):
+        raise ValueError(f"a stain basis must have shape (3, 3) or (N, 3, 3), [channel][stain], got {tuple(m.shape)}")
+    if not m.dtype.is_floating_point:
+        m = m.to(torch.float32)
+    if m.device.type != "cpu":
+        return m.to(torch.float32)
+    m64 = m.to(torch.float64)
+    if not bool(torch.isfinite(m64).all()):
+        raise ValueError("a stain basis must be finite")
+    if bool((torch.linalg.det(m64).abs() < 1e-12).any()):
+        raise ValueError("a stain basis must be invertible (its determinant is zero: two stain vectors are parallel, or one is zero)")
+    return (m64 / torch.linalg.vector_norm(m64, dim=-2, keepdim=True)).to(torch.float32)
+
+
+@dataclass
+class DeconvSeparation:
+    """What ``ColorDeconvolution.separate`` returns; a field that was not asked for is None.
+    ``images``: (3, N, 3, H, W) -- (3, N, H, W, 3) with ``channel_axis=-1`` --, image i the tile rebuilt from stain i alone.
+    ``concentrations``: (N, 3, H, W) float32 ((N, H, W, 3)).  ``basis``: the (3, 3) or (N, 3, 3) basis used."""
+
+    images: torch.Tensor | None
+    concentrations: torch.Tensor | None
+    basis: torch.Tensor
+
+
+def _cuda_device(device: Any, fallback: torch.device, who: str) -> torch.device:
+    device = torch.device(device) if device is not None else fallback
+    if device.type != "cuda":
+        raise ValueError(f"{who} runs on a CUDA (ROCm) device; got {device} (pass device='cuda' or move the tensor there)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _check_factor(name: str, factor: Any, n: int) -> None:
+    if factor is not None and (not isinstance(factor, torch.Tensor) or tuple(factor.shape) != (n, 3)):
+        raise ValueError(f"{name} must be a tensor of shape (N, 3) = ({n}, 3), got {tuple(getattr(factor, 'shape', ()))}")
+
+
+class ColorDeconvolution:
+    """Separate, apply and combine with a given three-stain basis on an MI355X.
+
+    ``basis`` / ``target``: what ``stain_basis`` takes -- a name, a (3, 3) matrix, or per-tile (N, 3, 3) bases (a
+    ``StainEstimate.complement()``); with ``target`` ``apply`` rebuilds the tile with that basis (stain transfer between two fixed
+    bases).  ``channel_axis=-1``: NHWC tiles in and out (unmasked calls only).  ``normalize_to_0_1``: uint8 tiles come out as float32
+    in [0, 1], float tiles are divided by 255.  ``mask="luminosity"`` (or ``apply(..., mask=tensor)``): only tissue pixels are
+    changed, the others are copied by the masked transforms' background rule.  ``device=None`` follows the input tensor.  All argument
+    errors are raised before any GPU work."""
+
+    def __init__(self, basis: Any = "hed", *, target: Any = None, device: str | torch.device | None = None, channel_axis: int = 1, normalize_to_0_1: bool = False,
+                 mask: str | None = None, luminosity_threshold: float = masks.DEFAULT_LUMINOSITY_THRESHOLD):
+        self.basis = stain_basis(basis)
+        self.target = None if target is None else stain_basis(target)
+        self.mask = masks.check_mask_mode(mask)
+        self.luminosity_threshold = masks.check_threshold(luminosity_threshold)
+        if channel_axis in (-1, 3):
+            self.channels_last = True
+        elif channel_axis in (1, -3):
+            self.channels_last = False
+        else:
+            raise ValueError(f"Unsupported channel_axis={channel_axis}")
+        if self.channels_last and self.mask is not None:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        self.channel_axis = channel_axis
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"ColorDeconvolution runs on a CUDA (ROCm) device, got {self.device}")
+        self.normalize_to_0_1 = bool(normalize_to_0_1)
+        self._engines: dict[torch.device, Any] = {}
+        self._device_bases: dict[torch.device, tuple[torch.Tensor, torch.Tensor | None]] = {}
+
+    def _bases_on(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """The basis and the target as float32 tensors on ``device``, uploaded ONCE per device (a host basis copied in front of every
+        call would put a pageable copy before the one launch, and keep a call from being captured)."""
+        held = self._device_bases.get(device)
+        if held is None:
+            def put(b):
+                return None if b is None else b.to(device=device, dtype=torch.float32).contiguous()
+
+            held = self._device_bases[device] = (put(self.basis), put(self.target))
+        return held
+
+    def _engine(self, device: torch.device):
+        engine = self._engines.get(device)
+        if engine is None:
+            from stainx_amd.backends.torch_hip_backend import DeconvHIP
+
+            engine = self._engines[device] = DeconvHIP(device)
+        return engine
+
+    def _batch(self, x: Any, what: str) -> tuple[torch.Tensor, bool]:
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{what} expects a tensor, got {type(x).__name__}")
+        single = x.dim() == 3
+        if single:
+            x = x.unsqueeze(0)
+        axis = 3 if self.channels_last else 1
+        if x.dim() != 4 or x.shape[axis] != 3:
+            layout = "HWC / NHWC" if self.channels_last else "CHW / NCHW"
+            raise ValueError(f"{what} expects {layout} tensors with C=3, got shape {tuple(x.shape)}")
+        return x, single
+
+    def _rows_ok(self, n: int) -> None:
+        for name, b in (("basis", self.basis), ("target", self.target)):
+            if b is not None and b.dim() == 3 and b.shape[0] not in (1, n):
+                raise ValueError(f"{name} holds {b.shape[0]} bases for a batch of {n} tiles (one basis, or one per tile)")
+
+    def _dims(self, x: torch.Tensor) -> tuple[int, int, int]:
+        return (x.shape[0], x.shape[1], x.shape[2]) if self.channels_last else (x.shape[0], x.shape[2], x.shape[3])
+
+    def separate(self, x: torch.Tensor, stains: bool = True, concentrations: bool = False) -> DeconvSeparation:
+        batch, single = self._batch(x, "separate")
+        if not stains and not concentrations:
+            raise ValueError("separate: ask for the stain images (stains=True), the concentrations, or both")
+        self._rows_ok(batch.shape[0])
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        imgs, conc = self._engine(device).separate(batch, self._bases_on(device)[0], stains=stains, concentrations=concentrations, normalize_to_0_1=self.normalize_to_0_1,
+                                                   channels_last=self.channels_last)
+        if single:
+            imgs = None if imgs is None else imgs.squeeze(1)
+            conc = None if conc is None else conc.squeeze(0)
+        return DeconvSeparation(imgs, conc, self.basis)
+
+    def apply(self, x: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
+        """``alpha`` / ``beta``: (N, 3) per-tile factors of the three concentrations, both or neither.  ``mask``: an explicit uint8 /
+        bool tensor (N, H, W) or (N, 1, H, W) on the device, or ``"luminosity"``, for this call."""
+        batch, single = self._batch(x, "apply")
+        n, h, w = self._dims(batch)
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together: both or neither")
+        _check_factor("alpha", alpha, n)
+        _check_factor("beta", beta, n)
+        self._rows_ok(n)
+        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
+        if masked and self.channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        out = self._engine(device).apply(batch, *self._bases_on(device), alpha=alpha, beta=beta, normalize_to_0_1=self.normalize_to_0_1, channels_last=self.channels_last,
+                                         masking=(explicit, self.luminosity_threshold) if masked else None)
+        return out.squeeze(0) if single else out
+
+    def combine(self, concentrations: torch.Tensor, out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+        """``separate``'s inverse: (N, 3, H, W) float32 concentrations -> tiles of ``out_dtype``, rebuilt with ``basis``."""
+        batch, single = self._batch(concentrations, "combine")
+        if batch.dtype != torch.float32:
+            raise ValueError(f"concentrations must be float32, got {batch.dtype}")
+        if out_dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+            raise ValueError(f"out_dtype must be uint8, float16, bfloat16, float32 or float64, got {out_dtype}")
+        if self.normalize_to_0_1 and out_dtype == torch.uint8:
+            raise ValueError("normalize_to_0_1 needs a float out_dtype in combine (uint8 output stays on 0-255)")
+        self._rows_ok(batch.shape[0])
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        out = self._engine(device).combine(batch, self._bases_on(device)[0], out_dtype=out_dtype, normalize_to_0_1=self.normalize_to_0_1, channels_last=self.channels_last)
+        return out.squeeze(0) if single else out
+
+    def __repr__(self) -> str:
+        return (f"ColorDeconvolution(basis={tuple(self.basis.shape)}, target={None if self.target is None else tuple(self.target.shape)}, channel_axis={self.channel_axis}, "
+                f"normalize_to_0_1={self.normalize_to_0_1}, mask={self.mask!r})")
+
+
+def _sigma3(name: str, sigma: Any, upper: float | None) -> tuple[float, float, float]:
+    try:
+        values = tuple(float(s) for s in sigma) if isinstance(sigma, (tuple, list)) else (float(sigma),) * 3
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number or a per-stain triple, got {sigma!r}") from None
+    if len(values) != 3:
+        raise ValueError(f"{name} must be a number or a per-stain triple, got {len(values)} values")
+    for v in values:
+        if not math.isfinite(v) or v < 0.0 or (upper is not None and v >= upper):
+            bound = f"lie in [0, {upper})" if upper is not None else "be >= 0"
+            raise ValueError(f"{name} must be finite and {bound}, got {sigma!r}")
+    return values
+
+
+class HEDAugment(nn.Module):
+    """Random per-tile jitter of the three concentrations of a FIXED basis ("HED-light", Tellez et al.): ``C' = alpha * C + beta`` with
+    ``alpha ~ U[1 - sigma1, 1 + sigma1]``, ``beta ~ U[-sigma2, sigma2]`` per tile and stain.  No estimate: one streaming launch per
+    batch, on any stain (IHC included) and on tiles Macenko cannot estimate.  ``sigma1`` / ``sigma2``: a number or a per-stain triple.
+    CHW / NCHW tensors; ``normalize_to_0_1`` (default True, as ``MacenkoAugment``); ``generator`` drives ``sample_factors``;
+    ``mask="luminosity"`` (or ``forward(..., mask=tensor)``): only tissue pixels are jittered.  The basis and the sigmas are uploaded once per
+    device; with a generator ON the device the factors are drawn there and a call enqueues no host copy at all (the default CPU generator
+    draws on the host and copies 6 N floats per call, as ``MacenkoAugment`` does).  The factors never leave the device."""
+
+    def __init__(self, sigma1: Any = 0.05, sigma2: Any = 0.05, *, basis: Any = "hed", device: str | torch.device | None = None, normalize_to_0_1: bool = True,
+                 generator: torch.Generator | None = None, mask: str | None = None, luminosity_threshold: float = masks.DEFAULT_LUMINOSITY_THRESHOLD):
+        super().__init__()
+        self.sigma1 = _sigma3("sigma1", sigma1, 1.0)
+        self.sigma2 = _sigma3("sigma2", sigma2, None)
+        self.generator = generator
+        self.deconv = ColorDeconvolution(basis, device=device, normalize_to_0_1=normalize_to_0_1, mask=mask, luminosity_threshold=luminosity_threshold)
+        self.device = self.deconv.device
+        self._sigmas: dict[torch.device, tuple[torch.Tensor, torch.Tensor]] = {}      # (the per-stain sigmas on a device: uploaded once)
+
+    def sample_factors(self, n: int, device: str | torch.device | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(alpha, beta)``, each (n, 3) float32 on ``device`` (exactly 1 and 0 for sigma = 0), drawn with the module's generator (on
+        the generator's device, then moved), as ``MacenkoAugment.sample_factors`` draws them."""
+        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
+        draw_on = self.generator.device if self.generator is not None else device
+        u = torch.rand((2, n, 3), generator=self.generator, device=draw_on, dtype=torch.float32).to(device)
+        held = self._sigmas.get(device)
+        if held is None:
+            held = self._sigmas[device] = (torch.tensor(self.sigma1, dtype=torch.float32, device=device), torch.tensor(self.sigma2, dtype=torch.float32, device=device))
+        s1, s2 = held
+        return 1.0 + s1 * (2.0 * u[0] - 1.0), s2 * (2.0 * u[1] - 1.0)
+
+    def forward(self, img: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
+        batch, single = self.deconv._batch(img, "HEDAugment")
+        n = batch.shape[0]
+        _check_factor("alpha", alpha, n)
+        _check_factor("beta", beta, n)
+        if alpha is None or beta is None:
+            device = _cuda_device(self.device, batch.device, "HEDAugment")
+            drawn = self.sample_factors(n, device)
+            alpha = drawn[0] if alpha is None else alpha
+            beta = drawn[1] if beta is None else beta
+        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        out = self.deconv.apply(batch, alpha, beta, mask=mask)
+        return out.squeeze(0) if single else out
+
+    def extra_repr(self) -> str:
+        return f"sigma1={self.sigma1}, sigma2={self.sigma2}, normalize_to_0_1={self.deconv.normalize_to_0_1}, mask={self.deconv.mask!r}"

@@ -35,6 +35,15 @@ class StainEstimate(NamedTuple):
     max_concentrations: torch.Tensor
     tissue_pixels: torch.Tensor | None
 
+    def complement(self) -> torch.Tensor:
+        """The estimate as (N, 3, 3) -- pooled: (1, 3, 3) -- three-stain bases for ``ColorDeconvolution``: H, E and their normalised
+        cross product (``stainx_amd.complement_basis``), so the part of the optical density outside the H&E plane becomes a third
+        channel instead of being dropped.  On the estimate's device, no synchronisation."""
+        from stainx_amd.deconv import complement_basis
+
+        he = self.stain_matrices
+        return complement_basis(he if he.dim() == 3 else he.unsqueeze(0))
+
 
 class Macenko(NormalizerTemplate):
     """``normalize_to_0_1`` defaults to False here (output ~[0,255]); ``StainNormalizerTransform`` defaults it to True.
