@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Three-stain colour deconvolution with a given basis: separate a batch into its stains, edit one and rebuild the tiles, jitter the
-concentrations for training ("HED-light"), and feed a slide's ESTIMATED H&E basis, complemented, through the same lossless path.
+concentrations for training ("HED-light"), feed a slide's ESTIMATED H&E basis, complemented, through the same lossless path, and
+measure a slide (positive-pixel fraction, H-score, percentiles) from integer histograms without writing a concentration map.
 Run on a ROCm GPU:  python examples/deconvolve_stains.py"""
 from __future__ import annotations
 
@@ -10,7 +11,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from stainx_amd import ColorDeconvolution, HEDAugment, Macenko, stain_basis, synth  # noqa: E402
+from stainx_amd import ColorDeconvolution, HEDAugment, Macenko, StainHistograms, stain_basis, synth  # noqa: E402
 
 
 def main() -> None:
@@ -42,6 +43,15 @@ def main() -> None:
     own = ColorDeconvolution(est.complement(), device=dev)
     residual = own.separate(tiles, stains=False, concentrations=True).concentrations[:, 2]
     print(f"residual concentration outside the estimated H&E plane: mean |C_3| = {residual.abs().mean().item():.4f}")
+
+    # 5. measure instead of map: one streaming launch per batch gives 256-bin integer histograms of the three concentrations (bins of 1/32
+    # over [-2, 6) by default), their exact sums and the counted pixels -- no (N, 3, H, W) map is written.  Integer counts add up exactly:
+    # pool the batches of a slide, then read the figures off the pooled set.  Thresholds are bin edges, so the figures are exact.
+    ihc = ColorDeconvolution("hdab", device=dev, mask="luminosity")  # stain 1 is DAB; only tissue pixels count
+    slide = StainHistograms.pool(*[ihc.quantify(batch, pooled=True) for batch in tiles.split(4)])
+    print(f"tissue pixels {int(slide.pixels[0])}, mean DAB concentration {slide.mean()[0, 1].item():.4f}, "
+          f"DAB-positive fraction (C >= 0.25) {slide.positive_fraction(1, 0.25)[0].item():.4f}, "
+          f"H-score {slide.h_score(1, (0.25, 0.5, 1.0))[0].item():.1f}, 95th percentile bin {slide.quantile(1, 0.95)[0].item():.5f}")
 
 
 if __name__ == "__main__":

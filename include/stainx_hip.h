@@ -329,6 +329,30 @@ int sx_deconv_separate(const void* images_dev, void* stains_out_dev, float* conc
  * or rescaled -- is what the pair is for. */
 int sx_deconv_combine(const float* conc_dev, void* out_dev, int out_dtype, int64_t n_tiles, int64_t height, int64_t width,
                       const float* basis_dev, int64_t n_bases, unsigned flags, void* stream);
+/* sx_deconv_quantify: what a deconvolved slide is measured by -- 256-bin INTEGER histograms of the three concentrations, their exact
+ * fixed-point sums and the number of counted pixels -- in one streaming pass that reads a pixel once and writes no map.  The
+ * concentrations are, bit for bit, the float32 values sx_deconv_separate writes; binning is an exact function of them:
+ *   bin_s  = clamp((int)floor(C_s * 2^bin_log2) + zero_bin, 0, 255)   bin b covers [(b - zero_bin) 2^-bin_log2, (b + 1 - zero_bin) 2^-bin_log2);
+ *                                                                     bins 0 and 255 also take everything below / above the range
+ *   term_s = C_s * 2^16 converted to int32 (round to nearest even, saturating), summed as int64
+ *   bin_log2 in [0, 8], zero_bin in [0, 255]  (5 and 64: bins of 1/32 over [-2, 6))
+ * A pixel counts iff its three concentrations are finite (a NaN / Inf input element, or 255 x + 1 <= 0, is in no count, no sum and not
+ * in `pixels`); a tile whose basis row holds a NaN counts nothing.
+ *   out_dev   S x 772 int64, S = n_tiles (per_tile != 0) or 1 (one set pooled over the batch); row s is
+ *             [counts: 3 x 256][sums: 3][pixels: 1].  Caller-owned; the call zeroes it in-stream (one hipMemsetAsync) and enqueues ONE
+ *             kernel: every word is written.  No workspace.
+ * Integers throughout: the result does not depend on the order of the adds -- identical run to run, and rows of different calls add up
+ * exactly.  Flags: SX_MACENKO_CHANNELS_LAST (unmasked call only), SX_MACENKO_CLASSIC (a no-op); every other bit is SX_ERR_BAD_ARG
+ * (there is no output image). */
+int sx_deconv_quantify(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                       const float* basis_dev, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
+                       long long* out_dev, unsigned flags, void* stream);
+/* sx_deconv_quantify_masked: the same over the masked-in pixels of an explicit mask (N, H, W), one byte per pixel, non-zero = in; planar
+ * tiles only.  Values under masked-out pixels never matter.  The mask is read in packs as wide as the pixel packs where the image pointer,
+ * the tile size AND the mask pointer allow it. */
+int sx_deconv_quantify_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                              const float* basis_dev, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
+                              long long* out_dev, const unsigned char* mask_dev, unsigned flags, void* stream);
 
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:

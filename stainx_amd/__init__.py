@@ -6,7 +6,7 @@ the GPU; the native library is loaded when a backend is first instantiated and i
 """
 from stainx_amd.augment import MacenkoAugment
 from stainx_amd.base import StainNormalizerBase
-from stainx_amd.deconv import ColorDeconvolution, DeconvSeparation, HEDAugment, complement_basis, stain_basis
+from stainx_amd.deconv import ColorDeconvolution, DeconvSeparation, HEDAugment, StainHistograms, complement_basis, stain_basis
 from stainx_amd.masks import tissue_mask
 from stainx_amd.normalizers import HistogramMatching, Macenko, Reinhard
 from stainx_amd.normalizers.histogram_matching import HistogramStatistics
@@ -15,4 +15,4 @@ from stainx_amd.normalizers.reinhard import ColorStatistics
 from stainx_amd.transforms import StainNormalizerTransform
 
 __version__ = "0.1.0"
-__all__ = ["ColorDeconvolution", "ColorStatistics", "DeconvSeparation", "HEDAugment", "HistogramMatching", "HistogramStatistics", "Macenko", "MacenkoAugment", "Reinhard", "StainNormalizerBase", "StainEstimate", "StainNormalizerTransform", "StainSeparation", "complement_basis", "stain_basis", "tissue_mask", "__version__"]
+__all__ = ["ColorDeconvolution", "ColorStatistics", "DeconvSeparation", "HEDAugment", "HistogramMatching", "HistogramStatistics", "Macenko", "MacenkoAugment", "Reinhard", "StainNormalizerBase", "StainEstimate", "StainHistograms", "StainNormalizerTransform", "StainSeparation", "complement_basis", "stain_basis", "tissue_mask", "__version__"]

@@ -69,6 +69,9 @@ SIGNATURES = {
     "sx_deconv_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _uint, _vp]),
     "sx_deconv_separate": (_int, [_vp, _vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_deconv_combine": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
+    # stain quantification: integer histograms of the three concentrations, fixed-point sums, counted pixels -- a memset and one launch
+    "sx_deconv_quantify": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _int, _int, _vp, _uint, _vp]),
+    "sx_deconv_quantify_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

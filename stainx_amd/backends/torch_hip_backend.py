@@ -1070,6 +1070,50 @@ class DeconvHIP(TorchHIPBackendBase):
             _native.check(rc, "sx_deconv_combine", self._lib)
         return out
 
+    QUANT_WORDS = 3 * 256 + 3 + 1      # a row of sx_deconv_quantify's output: [counts 3 x 256][sums 3][pixels 1]
+
+    def quantify(self, images: torch.Tensor, basis: torch.Tensor, *, bin_log2: int = 5, zero_bin: int = 64, per_tile: bool = True, channels_last: bool = False,
+                 masking: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(counts (S, 3, 256), sums (S, 3), pixels (S,))``, int64 views of ONE (S, 772) tensor; S = N (``per_tile``) or 1.  The
+        histograms of the three concentrations ``separate`` would write, their fixed-point (2^-16) sums and the counted pixels: a memset
+        and one launch, no map.  ``masking`` as in ``apply``."""
+        images = images.to(self.device)
+        n, h, w = self._dims(images, channels_last, "quantify")
+        code = _dtype_code(images)
+        if not (isinstance(bin_log2, int) and 0 <= bin_log2 <= 8):
+            raise ValueError(f"bin_log2 must be an integer in [0, 8], got {bin_log2!r}")
+        if not (isinstance(zero_bin, int) and 0 <= zero_bin <= 255):
+            raise ValueError(f"zero_bin must be an integer in [0, 255], got {zero_bin!r}")
+        if masking is not None and channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
+        b, n_bases = self._bases(basis, n, "basis")
+        mask = None
+        if masking is not None and masking[0] is not None:
+            mask = _mask_bytes(masking[0], self.device)
+            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
+                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+        sets = n if per_tile else 1
+        if n == 0 or h * w == 0:
+            out = torch.zeros((sets, self.QUANT_WORDS), dtype=torch.int64, device=self.device)
+        else:
+            images = images.contiguous()
+            out = torch.empty((sets, self.QUANT_WORDS), dtype=torch.int64, device=self.device)
+            flags = _native.MACENKO_CHANNELS_LAST if channels_last else 0
+            stream = _native.stream_ptr(self.device)
+            with _native.on_device(self.device):
+                if masking is not None:
+                    if mask is None:
+                        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+                        rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
+                        _native.check(rc, "sx_tissue_mask", self._lib)
+                    rc = self._lib.sx_deconv_quantify_masked(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, bin_log2, zero_bin, int(bool(per_tile)), out.data_ptr(),
+                                                             mask.data_ptr(), flags, stream)
+                    _native.check(rc, "sx_deconv_quantify_masked", self._lib)
+                else:
+                    rc = self._lib.sx_deconv_quantify(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, bin_log2, zero_bin, int(bool(per_tile)), out.data_ptr(), flags, stream)
+                    _native.check(rc, "sx_deconv_quantify", self._lib)
+        return out[:, :768].view(sets, 3, 256), out[:, 768:771], out[:, 771]
+
 
 class ReinhardHIP(TorchHIPBackendBase):
     """Reinhard LAB statistics matching on the GPU (numerics of ReinhardTorch, torch_backend.py:304-355)."""

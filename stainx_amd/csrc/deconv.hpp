@@ -81,6 +81,32 @@ __device__ __forceinline__ bool deconv_row_has_nan(const float* __restrict__ row
     return bad;
 }
 
+// The concentrations' twelve floats and their chain, ONE definition for the two kernels that hold concentrations (deconv_separate_kernel
+// writes them, deconv_quantify_kernel bins them): a pixel's float32 concentrations are the same bits in both.
+//   C_s = sum_j (-ln 2 inv[s][j]) L_j + ln 240 sum_j inv[s][j]
+struct ConcFold {
+    float ca[3][3], cb[3];
+    // (the one lane's prologue) 9 + 3 floats from the fp64 inverse
+    __device__ static __forceinline__ void fill(const double (&inv)[9], float* __restrict__ f) {
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) f[3 * s + j] = (float)(-0.69314718055994530942 * inv[3 * s + j]);      // ln 2
+            f[9 + s] = (float)(5.48063892334199 * (inv[3 * s] + inv[3 * s + 1] + inv[3 * s + 2]));      // ln 240
+        }
+    }
+    // (every lane, after the barrier) wave-uniform: scalar registers
+    __device__ __forceinline__ void read(const float* __restrict__ f) {
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ca[s][j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f[3 * s + j])));
+            cb[s] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f[9 + s])));
+        }
+    }
+    __device__ __forceinline__ float of(int s, float l0, float l1, float l2) const { return fmaf(ca[s][2], l2, fmaf(ca[s][1], l1, fmaf(ca[s][0], l0, cb[s]))); }
+};
+
 // The pixels of a pack set as the parents' loops take them: planar 16-byte packs non-temporally, everything else through load_pixels.
 template <typename T, int V, bool kInter>
 __device__ __forceinline__ void deconv_load(const T* __restrict__ img, int64_t pixels, int64_t p, float (&u)[3][V]) {
@@ -217,12 +243,7 @@ __global__ __launch_bounds__(kStreamThreads) void deconv_separate_kernel(const T
             const float al[3] = {s == 0 ? 1.0f : 0.0f, s == 1 ? 1.0f : 0.0f, s == 2 ? 1.0f : 0.0f}, be[3] = {0.0f, 0.0f, 0.0f};
             deconv_fold(b_src, inv, al, be, fold + 12 * s);
         }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) fold[36 + 3 * s + j] = (float)(-0.69314718055994530942 * inv[3 * s + j]);      // ln 2
-            fold[45 + s] = (float)(5.48063892334199 * (inv[3 * s] + inv[3 * s + 1] + inv[3 * s + 2]));      // ln 240
-        }
+        ConcFold::fill(inv, fold + 36);
     }
     tb.fill();
     __syncthreads();
@@ -272,18 +293,13 @@ __global__ __launch_bounds__(kStreamThreads) void deconv_separate_kernel(const T
             }
         }
         if (conc) {
-            float ca[3][3], cb[3];
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) ca[s][j] = uniform(36 + 3 * s + j);
-                cb[s] = uniform(45 + s);
-            }
+            ConcFold cf;
+            cf.read(fold + 36);
             float cc[3][V];
 #pragma unroll
             for (int i = 0; i < V; ++i)
 #pragma unroll
-                for (int s = 0; s < 3; ++s) cc[s][i] = fmaf(ca[s][2], l[2][i], fmaf(ca[s][1], l[1][i], fmaf(ca[s][0], l[0][i], cb[s])));
+                for (int s = 0; s < 3; ++s) cc[s][i] = cf.of(s, l[0][i], l[1][i], l[2][i]);
             bool stored = false;
             if constexpr (kInter && V == 4) {      // (H, W, 3) float32 in 16-byte packs: the images' staged store
                 if (full) {
@@ -343,6 +359,150 @@ __global__ __launch_bounds__(kStreamThreads) void deconv_combine_kernel(const fl
             }
         }
         store_pixels<O, V, kInter>(dst, a.pixels, q, res);
+    }
+}
+
+// sx_deconv_quantify / sx_deconv_quantify_masked: 256-bin integer histograms of the three concentrations, their fixed-point sums and the
+// number of counted pixels -- a pixel is read once and no map is written.  DESIGN.md 4o.
+// The concentrations are deconv_separate_kernel's bits (ConcFold).  Binning is an exact function of them:
+//   bin_s = clamp((int)floor(C_s 2^k) + z, 0, 255)      (the product with a power of two is exact)
+//   term_s = C_s 2^16 converted to int32, round to nearest even, saturating; summed as int64
+// A pixel counts iff its three concentrations are finite (and, kMask, its mask byte is set); a tile whose basis row holds a NaN counts
+// nothing.  Integers throughout: the result does not depend on the order of the adds, it is the same run to run and adds up exactly
+// over batches.
+// A workgroup keeps kQuantCopies bank-striped copies of the 3 x 256 uint32 histogram in LDS (lane l adds into copy l % 16: the lanes
+// of one ds_add_u32 that hit the SAME bin -- tissue clusters in a few bins -- spread over 16 addresses), the layout of
+// histogram_masked_kernel in histmatch.hip.  A work item is kQuantPixels pixels of one tile, whatever the pack width: eight pack sets of
+// float32, thirty-two sweeps of the scalar path.  Its flush -- 768 sums over the copies, a 64-bit global atomicAdd per NON-ZERO bin, three
+// sums and one pixel count per wave -- is then a few percent of its adds.
+constexpr int kQuantBins = 256;
+constexpr int kQuantCopies = 16;
+constexpr int kQuantPixels = 8192;                      // pixels per work item
+constexpr int kQuantWords = 3 * kQuantBins + 3 + 1;     // a row of the output: [counts 3 x 256][sums 3][pixels 1]
+
+struct QuantArgs {
+    const float* basis;             // n_bases x 9
+    unsigned long long* out;        // S x kQuantWords, zero when the kernel starts
+    int64_t pixels, n_tiles;        // P = H*W, N
+    int blocks;                     // work items per tile
+    int per_basis, per_tile;        // 1: row `tile` of the bases / of the output, 0: row 0
+    int zero_bin;                   // z
+    float scale;                    // 2^k
+};
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {      // (once per wave and stain: the shuffles' LDS round trips do not matter here)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;      // lane 0 holds the sum
+}
+
+template <typename T, int V, bool kInter, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void deconv_quantify_kernel(const T* __restrict__ images, QuantArgs a, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    static_assert(!(kInter && kMask), "the masked forms are planar");
+    static_assert(kQuantPixels % (kStreamThreads * V) == 0, "a work item is a whole number of pack sets");
+    constexpr int TPB = kStreamThreads;
+    __shared__ LevelTables<T> tb;
+    __shared__ float fold[13];      // (the last word: the tile's basis row holds a NaN)
+    __shared__ __attribute__((aligned(16))) uint32_t hist[3 * kQuantBins * kQuantCopies];      // (16 bytes: cleared in uint4 stores)
+    const int64_t tile = blockIdx.x / (unsigned)a.blocks;
+    const int chunk_id = (int)(blockIdx.x % (unsigned)a.blocks);
+    const uint8_t* msk = tile_mask(mk, tile, a.pixels);
+    const int64_t p_begin = (int64_t)chunk_id * kQuantPixels;
+    const int64_t p_end = min(p_begin + (int64_t)kQuantPixels, a.pixels);
+    const T* img = images + tile * 3 * a.pixels;
+
+    int64_t p = p_begin + (int64_t)threadIdx.x * V;
+    float u[3][V];
+    MaskPack<V> mp;
+    mp.clear();
+    if (p < p_end) {
+        deconv_load<T, V, kInter>(img, a.pixels, p, u);
+        if constexpr (kMask) mp.load(msk + p);
+    }
+
+    if (threadIdx.x == 0) {
+        const float* b_src = a.basis + (a.per_basis ? tile * 9 : 0);
+        double inv[9];
+        deconv_inverse(b_src, inv);
+        ConcFold::fill(inv, fold);
+        fold[12] = deconv_row_has_nan(b_src) ? 1.0f : 0.0f;
+    }
+    {
+        uint4* h4 = reinterpret_cast<uint4*>(hist);
+        for (int i = threadIdx.x; i < 3 * kQuantBins * kQuantCopies / 4; i += TPB) h4[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    tb.fill();
+    __syncthreads();
+    if (fold[12] != 0.0f) return;      // (uniform over the workgroup; the output is zero already)
+    ConcFold cf;
+    cf.read(fold);
+    const float scale = a.scale;
+    const int zero_bin = a.zero_bin;
+    uint32_t* mine = hist + (threadIdx.x & (kQuantCopies - 1));
+
+    long long sum[3] = {0ll, 0ll, 0ll};
+    uint32_t counted = 0u;      // wave-uniform: the wave's counted pixels
+    while (p < p_end) {
+        const int64_t p_next = p + (int64_t)TPB * V;
+        const bool more = p_next < p_end;
+        float un[3][V];
+        MaskPack<V> mn;
+        mn.clear();
+        if (more) {      // (the next pack set is on its way while this one is counted)
+            deconv_load<T, V, kInter>(img, a.pixels, p_next, un);
+            if constexpr (kMask) mn.load(msk + p_next);
+        }
+        uint32_t in_bits = ~0u;
+        if constexpr (kMask) in_bits = mp.bits();
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float l[3], c[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) l[k] = l2_of<T>(u[k][i], tb);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) c[s] = cf.of(s, l[0], l[1], l[2]);
+            constexpr float kInf = __builtin_huge_valf();
+            const bool ok = in_mask(in_bits, i) && fabsf(c[0]) < kInf && fabsf(c[1]) < kInf && fabsf(c[2]) < kInf;
+            counted += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ok));
+            if (ok) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const float f = fminf(fmaxf(floorf(c[s] * scale), -1024.0f), 1024.0f);      // (beyond every bin either way: the int conversion stays defined)
+                    const int bin = min(max((int)f + zero_bin, 0), kQuantBins - 1);
+                    atomicAdd(&mine[(s * kQuantBins + bin) * kQuantCopies], 1u);
+                    const float t = rintf(c[s] * 65536.0f);
+                    const int term = t >= 2147483648.0f ? 2147483647 : (t <= -2147483648.0f ? (-2147483647 - 1) : (int)t);      // v_cvt_i32_f32's saturation, spelled out
+                    sum[s] += (long long)term;
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) u[k][i] = un[k][i];
+            mp = mn;
+        }
+        p = p_next;
+    }
+    // (a thread without a pack never entered the loop: its ballots are missing from `counted`, which only lane 0 of a wave uses -- and
+    // lane 0 holds the lowest pixel of its wave, so it ran every sweep any lane of its wave ran)
+    __syncthreads();
+    unsigned long long* row = a.out + (a.per_tile ? tile : 0) * kQuantWords;
+    for (int i = threadIdx.x; i < 3 * kQuantBins; i += TPB) {      // thread t adds up the copies of its bins, starting at its own bank
+        uint32_t total = 0u;
+#pragma unroll
+        for (int k = 0; k < kQuantCopies; ++k) total += hist[i * kQuantCopies + ((threadIdx.x + k) & (kQuantCopies - 1))];
+        if (total) atomicAdd(&row[i], (unsigned long long)total);
+    }
+    const uint32_t wave_counted = (uint32_t)__builtin_amdgcn_readfirstlane((int)counted);
+    if (wave_counted) {      // (wave-uniform)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const long long total = wave_sum_i64(sum[s]);
+            if (lane_id() == 0 && total != 0ll) atomicAdd(&row[3 * kQuantBins + s], (unsigned long long)total);      // (two's complement: the 64-bit add is the signed add)
+        }
+        if (lane_id() == 0) atomicAdd(&row[3 * kQuantBins + 3], (unsigned long long)wave_counted);
     }
 }
 
@@ -447,6 +607,29 @@ static int deconv_combine_typed(const float* conc, void* out, DeconvArgs a, bool
         else hipLaunchKernelGGL((deconv_combine_kernel<O, 1, kUnit, false>), grid, block, 0, stream, conc, dst, a);
     }
     return check_launch("deconv combine");
+}
+
+template <typename T, int V, bool kInter, bool kMask = false>
+static int run_deconv_quantify(const T* images, QuantArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    a.blocks = (int)((a.pixels + kQuantPixels - 1) / kQuantPixels);
+    hipLaunchKernelGGL((deconv_quantify_kernel<T, V, kInter, kMask>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, a, mk);
+    return check_launch("deconv quantify");
+}
+
+// (the siblings' pack rule: 16-byte packs where the tile size and the image pointer allow it -- and, masked, the mask pointer, whose packs
+// are as wide as the pixels' --, single pixels otherwise)
+template <typename T, bool kMask = false>
+static int deconv_quantify_typed(const void* images, const QuantArgs& a, bool interleaved, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    constexpr int W = PackOf<T>::n;
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16);
+    const T* in = static_cast<const T*>(images);
+    if constexpr (kMask) {
+        vec = vec && aligned_for(mk.mask, W);
+        return vec ? run_deconv_quantify<T, W, false, true>(in, a, stream, mk) : run_deconv_quantify<T, 1, false, true>(in, a, stream, mk);
+    } else {
+        if (interleaved) return vec ? run_deconv_quantify<T, W, true>(in, a, stream) : run_deconv_quantify<T, 1, true>(in, a, stream);
+        return vec ? run_deconv_quantify<T, W, false>(in, a, stream) : run_deconv_quantify<T, 1, false>(in, a, stream);
+    }
 }
 
 }  // namespace macenko
@@ -569,4 +752,54 @@ extern "C" int sx_deconv_combine(const float* conc, void* out, int out_dtype, in
         case SX_F64: return unit ? deconv_combine_typed<double, true>(conc, out, a, inter, stream) : deconv_combine_typed<double, false>(conc, out, a, inter, stream);
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", out_dtype);
     }
+}
+
+template <bool kMask>
+static int deconv_quantify_call(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
+                                long long* out, const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
+    const char* who = kMask ? "sx_deconv_quantify_masked" : "sx_deconv_quantify";
+    int rc = deconv_common_ok(images, n, h, w, basis, n_bases, "images");
+    if (rc != SX_OK) return rc;
+    if (!out) return fail(SX_ERR_BAD_ARG, "out pointer is null");
+    if (kMask && !mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (bin_log2 < 0 || bin_log2 > 8) return fail(SX_ERR_BAD_ARG, "bin_log2 must lie in [0, 8] (bins of width 2^-bin_log2), got %d", bin_log2);
+    if (zero_bin < 0 || zero_bin > 255) return fail(SX_ERR_BAD_ARG, "zero_bin must lie in [0, 255] (the bin whose lower edge is concentration 0), got %d", zero_bin);
+    if (kMask && (flags & SX_MACENKO_CHANNELS_LAST)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes planar (N,3,H,W) tiles only (no SX_MACENKO_CHANNELS_LAST)", flags, who);
+    if (flags & ~(SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes SX_MACENKO_CHANNELS_LAST and SX_MACENKO_CLASSIC only (there is no output image)", flags, who);
+    QuantArgs a{};
+    a.basis = basis;
+    a.out = reinterpret_cast<unsigned long long*>(out);
+    a.pixels = h * w;
+    a.n_tiles = n;
+    a.per_basis = n_bases == n && n != 1 ? 1 : 0;
+    a.per_tile = per_tile ? 1 : 0;
+    a.zero_bin = zero_bin;
+    a.scale = (float)(1 << bin_log2);
+    const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    switch (dtype) {      // (before anything is enqueued)
+        case SX_U8: case SX_F16: case SX_BF16: case SX_F32: case SX_F64: break;
+        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
+    }
+    const size_t bytes = (size_t)(per_tile ? n : 1) * kQuantWords * sizeof(unsigned long long);
+    if (hipMemsetAsync(out, 0, bytes, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    MaskArgs<kMask> mk{};
+    if constexpr (kMask) mk.mask = mask_dev;
+    switch (dtype) {
+        case SX_U8: return deconv_quantify_typed<uint8_t, kMask>(images, a, inter, stream, mk);
+        case SX_F16: return deconv_quantify_typed<__half, kMask>(images, a, inter, stream, mk);
+        case SX_BF16: return deconv_quantify_typed<__hip_bfloat16, kMask>(images, a, inter, stream, mk);
+        case SX_F32: return deconv_quantify_typed<float, kMask>(images, a, inter, stream, mk);
+        default: return deconv_quantify_typed<double, kMask>(images, a, inter, stream, mk);
+    }
+}
+
+extern "C" int sx_deconv_quantify(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
+                                  long long* out, unsigned flags, void* stream_ptr) {
+    return deconv_quantify_call<false>(images, dtype, n, h, w, basis, n_bases, bin_log2, zero_bin, per_tile, out, nullptr, flags, stream_ptr);
+}
+
+extern "C" int sx_deconv_quantify_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
+                                         long long* out, const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
+    return deconv_quantify_call<true>(images, dtype, n, h, w, basis, n_bases, bin_log2, zero_bin, per_tile, out, mask_dev, flags, stream_ptr);
 }

@@ -5,7 +5,8 @@ fixed-matrix augmentors of tiatoolbox / torchstain offer it: the optical density
 by the inverse of a fixed (3, 3) basis -- no estimate, so it serves IHC slides (haematoxylin + DAB) that Macenko's H&E estimate does
 not, and it is lossless: the concentrations can be edited and the tile rebuilt.  ``ColorDeconvolution`` separates, applies
 (``C' = alpha * C + beta``, optionally rebuilt with another basis) and combines; ``HEDAugment`` is the "HED-light" jitter of Tellez et
-al. as an ``nn.Module``.  The conventions are the Macenko calls' (``OD = -ln((255 x + 1) / 240)``, ``level = clamp(240 exp(-OD'))``), so
+al. as an ``nn.Module``; ``ColorDeconvolution.quantify`` measures a slide -- integer histograms of the three concentrations
+(``StainHistograms``: positive-pixel fraction, H-score, mean, percentiles) in one streaming launch that writes no map.  The conventions are the Macenko calls' (``OD = -ln((255 x + 1) / 240)``, ``level = clamp(240 exp(-OD'))``), so
 an estimated H&E basis, complemented (``StainEstimate.complement()``), feeds the same path with the residual as a channel of its own.
 One kernel launch per call (include/stainx_hip.h: sx_deconv_*).
 """
@@ -13,7 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Any
+from typing import Any, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -88,6 +89,124 @@ class DeconvSeparation:
     images: torch.Tensor | None
     concentrations: torch.Tensor | None
     basis: torch.Tensor
+
+
+def _check_binning(bin_log2: Any, zero_bin: Any) -> tuple[int, int]:
+    if isinstance(bin_log2, bool) or not isinstance(bin_log2, int) or not 0 <= bin_log2 <= 8:
+        raise ValueError(f"bin_log2 must be an integer in [0, 8] (bins of width 2^-bin_log2), got {bin_log2!r}")
+    if isinstance(zero_bin, bool) or not isinstance(zero_bin, int) or not 0 <= zero_bin <= 255:
+        raise ValueError(f"zero_bin must be an integer in [0, 255] (the bin whose lower edge is concentration 0), got {zero_bin!r}")
+    return bin_log2, zero_bin
+
+
+class StainHistograms(NamedTuple):
+    """What ``ColorDeconvolution.quantify`` returns: integer histograms of the three stain concentrations of a batch, estimated in one
+    streaming launch -- no concentration map is written.  ``counts``: (S, 3, 256) int64, bin b of stain s of set S; ``sums``: (S, 3)
+    int64, the sum of the concentrations in fixed point (units of 2^-16); ``pixels``: (S,) int64, the pixels counted (finite
+    concentrations, and inside the mask if there is one).  S = N for a set per tile, 1 for one set pooled over the batch.  Bin b covers
+    ``[(b - zero_bin) 2^-bin_log2, (b + 1 - zero_bin) 2^-bin_log2)``; bins 0 and 255 also take everything below / above that range.
+
+    Everything is an integer, so results are the same run to run and sets of different batches, slides or ranks ADD UP EXACTLY
+    (:meth:`pool`, or ``all_reduce`` (SUM) on the three tensors).  The derived figures are plain torch ops where the tensors live (no
+    synchronisation).  The thresholds of :meth:`positive_fraction` and :meth:`h_score` must be bin edges: the figures are then exact --
+    the same numbers a threshold on the concentration map gives."""
+
+    counts: torch.Tensor
+    sums: torch.Tensor
+    pixels: torch.Tensor
+    bin_log2: int = 5
+    zero_bin: int = 64
+
+    @staticmethod
+    def pool(*items: "StainHistograms") -> "StainHistograms":
+        """One set, (1, 3, 256), (1, 3) and (1,): the sum of every set of every argument (exact).  ValueError on differing binning."""
+        if not items:
+            raise ValueError("pool needs at least one StainHistograms")
+        first = items[0]
+        counts = sums = pixels = None
+        for item in items:
+            if not isinstance(item, StainHistograms):
+                raise ValueError(f"pool takes StainHistograms, got {type(item).__name__}")
+            if (item.bin_log2, item.zero_bin) != (first.bin_log2, first.zero_bin):
+                raise ValueError(f"pool: the sets are binned differently (bin_log2, zero_bin) = {(first.bin_log2, first.zero_bin)} and {(item.bin_log2, item.zero_bin)}; "
+                                 "counts of different bins do not add up")
+            c, s, p = item.counts.sum(dim=0, keepdim=True), item.sums.sum(dim=0, keepdim=True), item.pixels.sum(dim=0, keepdim=True)
+            counts, sums, pixels = (c, s, p) if counts is None else (counts + c, sums + s, pixels + p)
+        return StainHistograms(counts, sums, pixels, first.bin_log2, first.zero_bin)
+
+    def edges(self) -> torch.Tensor:
+        """(257,) float64: the bin edges, ``(b - zero_bin) 2^-bin_log2`` for b = 0 .. 256."""
+        return (torch.arange(257, dtype=torch.float64, device=self.counts.device) - self.zero_bin) / float(1 << self.bin_log2)
+
+    def mean(self) -> torch.Tensor:
+        """(S, 3) float64: the mean concentration of each stain over the counted pixels, ``sums / 2^16 / pixels``; 0 where nothing was counted."""
+        p = self.pixels.to(torch.float64).unsqueeze(-1)
+        return torch.where(p > 0, self.sums.to(torch.float64) / 65536.0 / p.clamp(min=1.0), torch.zeros_like(p))
+
+    def _edge(self, threshold: Any, name: str = "threshold") -> int:
+        """The index e (1 .. 255) of the bin edge ``threshold`` is: ``C >= threshold`` is then ``bin >= e``, exactly."""
+        try:
+            t = float(threshold)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {threshold!r}") from None
+        scale = float(1 << self.bin_log2)
+        pos = t * scale      # (exact for every float that is an edge)
+        if not math.isfinite(t) or pos != math.floor(pos) or not 1 <= int(pos) + self.zero_bin <= 255:
+            lo, hi = (1 - self.zero_bin) / scale, (255 - self.zero_bin) / scale
+            if math.isfinite(t):
+                below, above = min(max(math.floor(pos) / scale, lo), hi), min(max(math.ceil(pos) / scale, lo), hi)
+                near = f"the nearest edges are {below!r} and {above!r}" if below != above else f"the nearest edge is {below!r}"
+            else:
+                near = "it is not finite"
+            raise ValueError(f"{name} = {threshold!r} is not a bin edge inside the range: edges are multiples of {1.0 / scale!r} from {lo!r} to {hi!r}; {near} "
+                             "(a threshold between two edges cannot be answered exactly from a histogram)")
+        return int(pos) + self.zero_bin
+
+    @staticmethod
+    def _stain(stain: Any) -> int:
+        if isinstance(stain, bool) or not isinstance(stain, int) or not 0 <= stain <= 2:
+            raise ValueError(f"stain must be 0, 1 or 2 (a column of the basis), got {stain!r}")
+        return stain
+
+    def _at_least(self, stain: int, edge: int) -> torch.Tensor:
+        return self.counts[:, stain, edge:].sum(dim=-1)
+
+    def _share(self, numerator: torch.Tensor, factor: float) -> torch.Tensor:
+        p = self.pixels.to(torch.float64)
+        return torch.where(p > 0, factor * numerator.to(torch.float64) / p.clamp(min=1.0), torch.zeros_like(p))
+
+    def positive_fraction(self, stain: int, threshold: float) -> torch.Tensor:
+        """(S,) float64: the share of the counted pixels with ``C_stain >= threshold`` (the positive-pixel fraction; DAB area fraction
+        with ``stain=1`` of ``"hdab"``); 0 where nothing was counted.  ``threshold`` must be a bin edge inside the range."""
+        return self._share(self._at_least(self._stain(stain), self._edge(threshold)), 1.0)
+
+    def h_score(self, stain: int, thresholds: tuple[float, float, float]) -> torch.Tensor:
+        """(S,) float64 in [0, 300]: the pixel-wise H-score ``100 (weak + 2 moderate + 3 strong) / pixels`` with weak = ``[t1, t2)``,
+        moderate = ``[t2, t3)``, strong = ``>= t3``; 0 where nothing was counted.  ``thresholds``: three ascending bin edges."""
+        stain = self._stain(stain)
+        if not isinstance(thresholds, (tuple, list)) or len(thresholds) != 3:
+            raise ValueError(f"thresholds must be three ascending bin edges (t1, t2, t3), got {thresholds!r}")
+        e = [self._edge(t, f"thresholds[{i}]") for i, t in enumerate(thresholds)]
+        if not e[0] <= e[1] <= e[2]:
+            raise ValueError(f"thresholds must be ascending, got {tuple(thresholds)!r}")
+        # (weak + 2 moderate + 3 strong = the pixels at or above t1, plus those at or above t2, plus those at or above t3)
+        return self._share(self._at_least(stain, e[0]) + self._at_least(stain, e[1]) + self._at_least(stain, e[2]), 100.0)
+
+    def quantile(self, stain: int, q: float) -> torch.Tensor:
+        """(S,) float64: the lower edge of the bin that holds the nearest-rank element of ``C_stain`` -- rank ``max(1, ceil(q pixels))``
+        in ascending order --; NaN where nothing was counted.  Within one bin width of the exact quantile for values inside the range."""
+        stain = self._stain(stain)
+        try:
+            q = float(q)
+        except (TypeError, ValueError):
+            raise ValueError(f"q must be a number in [0, 1], got {q!r}") from None
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"q must lie in [0, 1], got {q!r}")
+        rank = torch.ceil(q * self.pixels.to(torch.float64)).to(torch.int64).clamp(min=1)
+        cumulative = self.counts[:, stain].cumsum(dim=-1)
+        index = torch.searchsorted(cumulative, rank.unsqueeze(-1)).squeeze(-1).clamp(max=255)      # the first bin whose cumulative count reaches the rank
+        value = (index.to(torch.float64) - self.zero_bin) / float(1 << self.bin_log2)
+        return torch.where(self.pixels > 0, value, torch.full_like(value, float("nan")))
 
 
 def _cuda_device(device: Any, fallback: torch.device, who: str) -> torch.device:
@@ -207,6 +326,26 @@ class ColorDeconvolution:
         out = self._engine(device).apply(batch, *self._bases_on(device), alpha=alpha, beta=beta, normalize_to_0_1=self.normalize_to_0_1, channels_last=self.channels_last,
                                          masking=(explicit, self.luminosity_threshold) if masked else None)
         return out.squeeze(0) if single else out
+
+    def quantify(self, x: torch.Tensor, *, pooled: bool = False, bin_log2: int = 5, zero_bin: int = 64, mask: Any = None) -> StainHistograms:
+        """Measure instead of map: the 256-bin integer histograms of the three concentrations ``separate(x, concentrations=True)`` would
+        write (bit for bit those values), their fixed-point sums and the counted pixels -- a set per tile, or one set ``pooled`` over the
+        batch -- in ONE streaming launch that reads a pixel once and writes no map.  Bins are ``2^-bin_log2`` wide and bin ``zero_bin``
+        starts at concentration 0 (defaults: 1/32 over [-2, 6)).  ``mask``: as in ``apply`` -- only masked-in pixels count.  Pixels with a
+        non-finite concentration (NaN / Inf input, ``255 x + 1 <= 0``) are not counted.  See ``StainHistograms`` for the figures."""
+        batch, single = self._batch(x, "quantify")
+        n, h, w = self._dims(batch)
+        bin_log2, zero_bin = _check_binning(bin_log2, zero_bin)
+        self._rows_ok(n)
+        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
+        if masked and self.channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        counts, sums, pixels = self._engine(device).quantify(batch, self._bases_on(device)[0], bin_log2=bin_log2, zero_bin=zero_bin, per_tile=not pooled,
+                                                             channels_last=self.channels_last, masking=(explicit, self.luminosity_threshold) if masked else None)
+        return StainHistograms(counts, sums, pixels, bin_log2, zero_bin)
 
     def combine(self, concentrations: torch.Tensor, out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
         """``separate``'s inverse: (N, 3, H, W) float32 concentrations -> tiles of ``out_dtype``, rebuilt with ``basis``."""
