@@ -598,6 +598,50 @@ int sx_hm_transform_tiles(const void* images_dev, void* out_dev, int dtype, int6
 int sx_tissue_mask(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
                    double luminosity_threshold, uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
 
+/* ---- Tissue detection: a threshold taken from the data, and a clean-up of the mask -------------------
+ * What staintools', tiatoolbox's and HistomicsTK's users do before an estimate: an Otsu threshold on the lightness, then a morphological
+ * opening and closing of the mask.  Three device calls; the Otsu arithmetic itself is exact integer work on 256 counts per row and
+ * stays with the caller (stainx_amd.otsu_threshold).
+ *
+ * sx_luminosity_histogram: 256-bin integer histograms of lightness, one memset and one streaming launch.  counts_out_dev: rows x 256
+ *   uint64, rows = n_tiles, or 1 with pooled != 0 (required).  The bins are defined by the rule itself: with
+ *   cut[k] = sx_tissue_y_cut of k / 256, k = 1..255, a pixel's bin is the number of k with !(Y < cut[k]), Y the luminance every masked
+ *   kernel compares.  So the sum of bins 0..k-1 is EXACTLY the tissue count of sx_tissue_mask at luminosity_threshold = k / 256, for every
+ *   k, element type and layout; a NaN pixel lands in bin 255 (background at every threshold).  Arguments as sx_tissue_mask.
+ * sx_tissue_y_cut: host only.  The constant sx_tissue_mask derives from its threshold (a pixel is tissue iff Y < it); NaN for a
+ *   threshold outside (0, 1).  Strictly increasing over k / 256.
+ * sx_tissue_mask_tiles: sx_tissue_mask with a constant per tile.  tile_y_cut_dev: n_tiles floats in DEVICE memory read by the kernel (a
+ *   captured call replayed after new cuts were written uses them; NULL is SX_ERR_BAD_ARG); tile i is tissue where Y < tile_y_cut_dev[i],
+ *   and a NaN cut makes the whole tile background with count 0.  With every entry equal to the value sx_tissue_y_cut gives for t, mask
+ *   and counts are the bits of sx_tissue_mask at t.  One launch and the clear of the counts. */
+int sx_luminosity_histogram(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                            int pooled, unsigned long long* counts_out_dev, void* stream);
+float sx_tissue_y_cut(double luminosity_threshold);
+int sx_tissue_mask_tiles(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                         const float* tile_y_cut_dev, uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
+
+/* sx_mask_morphology: binary erosion, dilation, opening (erode, then dilate) and closing (dilate, then erode) of masks.
+ *   mask_in_dev    n_tiles x height x width bytes, non-zero = set;   mask_out_dev: the same shape, 1 / 0.  mask_out_dev == mask_in_dev
+ *                  is SX_ERR_BAD_ARG (not in place).
+ *   element        SX_ELEMENT_SQUARE: the (2r+1) x (2r+1) box; SX_ELEMENT_DISK: the offsets with dx^2 + dy^2 <= r^2 (scikit-image's disk(r))
+ *   radius         1 .. SX_MORPH_MAX_RADIUS; anything else is SX_ERR_BAD_ARG
+ *   scratch_dev    n_tiles x height x width bytes for SX_MORPH_OPEN / SX_MORPH_CLOSE (NULL, mask_in_dev or mask_out_dev there:
+ *                  SX_ERR_BAD_ARG); not read by erode / dilate, may be NULL
+ *   tile_counts_out_dev   n_tiles uint64, the set pixels of the result per tile; may be NULL
+ * Borders (OpenCV's default; scipy's binary_erosion(border_value=1) / binary_dilation(border_value=0)): what lies outside a tile never
+ * constrains the result -- erosion reads it as set, dilation as unset -- so tissue that touches a tile's edge is not eaten from the
+ * edge.  Tiles are independent.  One launch for erode / dilate, two for open / close, and the clear of the counts; every launch stages
+ * its pixels with their halo on chip once, a bit per pixel. */
+#define SX_MORPH_ERODE 0
+#define SX_MORPH_DILATE 1
+#define SX_MORPH_OPEN 2
+#define SX_MORPH_CLOSE 3
+#define SX_ELEMENT_SQUARE 0
+#define SX_ELEMENT_DISK 1
+#define SX_MORPH_MAX_RADIUS 31
+int sx_mask_morphology(const uint8_t* mask_in_dev, uint8_t* mask_out_dev, int64_t n_tiles, int64_t height, int64_t width, int op,
+                       int element, int radius, uint8_t* scratch_dev, unsigned long long* tile_counts_out_dev, void* stream);
+
 /* Reinhard.  per_tile != 0: every tile its own statistics (N rows, a tile's result does not depend on its neighbours); per_tile == 0: one
  * set pooled over the tissue of the whole batch (one row).  Workspace: sx_reinhard_masked_workspace_bytes(); any contents are accepted
  * and a workspace that was READY (sx_reinhard_transform_ready) is left ready, so the calls may alternate with that one and with

@@ -36,6 +36,9 @@ MACENKO_PARAM_FLOATS = 48
 PFIT_STATS_RECORD_BYTES = 49240
 PFIT_SUMS = 1033
 PFIT_COMPACT = 32768
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}      # sx_mask_morphology: SX_MORPH_*, SX_ELEMENT_*, SX_MORPH_MAX_RADIUS
+MORPH_ELEMENTS = {"square": 0, "disk": 1}
+MORPH_MAX_RADIUS = 31
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -118,6 +121,11 @@ SIGNATURES = {
     "sx_hm_counts_ready": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _sz, _vp]),
     # tissue masks: `mask_dev` may be None (the luminosity rule with the double that follows it)
     "sx_tissue_mask": (_int, [_vp, _int, _i64, _i64, _i64, _int, _c.c_double, _vp, _vp, _vp]),
+    # tissue detection: luminosity histograms (Otsu), the rule with a cut per tile in device memory, binary morphology on masks
+    "sx_luminosity_histogram": (_int, [_vp, _int, _i64, _i64, _i64, _int, _int, _vp, _vp]),
+    "sx_tissue_y_cut": (_c.c_float, [_c.c_double]),
+    "sx_tissue_mask_tiles": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "sx_mask_morphology": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "sx_reinhard_masked_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -79,6 +79,59 @@ def tissue_mask_native(images: torch.Tensor, luminosity_threshold: float, channe
     return mask, counts
 
 
+def _image_sizes(images: torch.Tensor, channels_last: bool) -> tuple[int, int, int]:
+    return (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
+
+
+def luminosity_histogram_native(images: torch.Tensor, pooled: bool, channels_last: bool) -> torch.Tensor:
+    """``stainx_amd.luminosity_histogram`` behind its checks: (rows, 256) int64 counts on the device (include/stainx_hip.h: sx_luminosity_histogram)."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images = images.to(base.device).contiguous()
+    n, h, w = _image_sizes(images, channels_last)
+    counts = torch.zeros((1 if pooled else n, 256), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return counts
+    with _native.on_device(base.device):
+        rc = base._lib.sx_luminosity_histogram(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), int(pooled), counts.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_luminosity_histogram")
+    return counts
+
+
+def tissue_mask_tiles_native(images: torch.Tensor, thresholds: torch.Tensor, channels_last: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """The rule with a threshold per tile (``thresholds``: (N,) float64 on the CPU, each in (0, 1)): (N, H, W) uint8 mask and (N,) int64 counts
+    (include/stainx_hip.h: sx_tissue_mask_tiles, with the constants sx_tissue_y_cut gives)."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images = images.to(base.device).contiguous()
+    n, h, w = _image_sizes(images, channels_last)
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return mask, counts
+    cuts = torch.tensor([base._lib.sx_tissue_y_cut(float(t)) for t in thresholds.tolist()], dtype=torch.float32).to(base.device)
+    with _native.on_device(base.device):
+        rc = base._lib.sx_tissue_mask_tiles(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), cuts.data_ptr(), mask.data_ptr(), counts.data_ptr(),
+                                            _native.stream_ptr(base.device))
+    _native.check(rc, "sx_tissue_mask_tiles")
+    return mask, counts
+
+
+def mask_morphology_native(mask: torch.Tensor, op: str, radius: int, element: str) -> tuple[torch.Tensor, torch.Tensor]:
+    """``stainx_amd.mask_morphology`` behind its checks: (N, H, W) uint8 result, 1 / 0, and (N,) int64 set pixels per tile (sx_mask_morphology)."""
+    base = TorchHIPBackendBase(mask.device)
+    src = _mask_bytes(mask, base.device)
+    n, h, w = src.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return out, counts
+    scratch = torch.empty_like(out) if op in ("open", "close") else None
+    with _native.on_device(base.device):
+        rc = base._lib.sx_mask_morphology(src.data_ptr(), out.data_ptr(), n, h, w, _native.MORPH_OPS[op], _native.MORPH_ELEMENTS[element], int(radius),
+                                          None if scratch is None else scratch.data_ptr(), counts.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_mask_morphology")
+    return out, counts
+
+
 class MacenkoHIP(TorchHIPBackendBase):
     """Macenko transform / fit on the GPU (numerics of MacenkoTorch, torch_backend.py:358-560)."""
 

@@ -1029,3 +1029,6 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
         default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
     }
 }
+
+// ---- tissue detection: luminosity histograms (for Otsu thresholds), per-tile cuts, binary morphology on masks ------------------------------
+#include "tissue_detect.hpp"

@@ -45,8 +45,11 @@ struct Source {
 
 // THE rule: linear-light R, G, B (of the unit value: the table for uint8, srgb_to_linear() otherwise) -> tissue or not.  Y by the
 // colour conversion's middle row (torch_backend.py:32); a NaN pixel is background.
+__device__ __forceinline__ float luminance(float lin_r, float lin_g, float lin_b) {      // (also what the luminosity histogram bins: tissue_detect.hpp)
+    return fmaf(0.072169f, lin_b, fmaf(0.715160f, lin_g, 0.212671f * lin_r));
+}
 __device__ __forceinline__ bool is_tissue(float lin_r, float lin_g, float lin_b, float y_cut) {
-    return fmaf(0.072169f, lin_b, fmaf(0.715160f, lin_g, 0.212671f * lin_r)) < y_cut;
+    return luminance(lin_r, lin_g, lin_b) < y_cut;
 }
 
 // linear-light value of one stored element, as the Reinhard passes compute it

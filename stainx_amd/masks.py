@@ -5,11 +5,14 @@ A mask has one value per pixel (a pixel's three channels are in or out together)
 (``u8 / 255``, floats as they are).  An explicit mask is a dense uint8 / bool tensor ``(N, H, W)`` or ``(N, 1, H, W)`` on the
 normaliser's device, non-zero = tissue.  Every kernel decides a pixel with the same device function (csrc/tissue.hpp), so the rule and
 a mask made by :func:`tissue_mask` give the same bits everywhere.
+
+Tissue detection (the second half of the file): :func:`luminosity_histogram`, :func:`otsu_threshold`, :func:`otsu_mask` -- a threshold taken
+from the data -- and :func:`mask_morphology`, :func:`refine_mask` -- opening and closing of a mask.
 """
 from __future__ import annotations
 
 import math
-from typing import Any
+from typing import Any, NamedTuple
 
 import torch
 
@@ -76,3 +79,199 @@ def tissue_mask(images: torch.Tensor, luminosity_threshold: float = DEFAULT_LUMI
     from stainx_amd.backends.torch_hip_backend import tissue_mask_native
 
     return tissue_mask_native(images, threshold, last)
+
+
+# ---------------------------------------------------------------------------------------------------------------- tissue detection
+# A threshold taken from the data (Otsu on the lightness) and a morphological clean-up of the mask: what staintools', tiatoolbox's and
+# HistomicsTK's users do on the CPU before an estimate.  The result is handed on as ``mask=det.mask``, which every masked call accepts.
+MORPHOLOGY_OPS = ("erode", "dilate", "open", "close")
+MORPHOLOGY_ELEMENTS = ("square", "disk")
+MAX_MORPHOLOGY_RADIUS = 31      # include/stainx_hip.h: SX_MORPH_MAX_RADIUS
+
+
+class LuminosityHistogram(NamedTuple):
+    """256-bin integer histograms of lightness (:func:`luminosity_histogram` returns it, :func:`otsu_threshold` takes it).  ``counts``: (rows,
+    256) int64, ``pixels``: (rows,) int64, the row sums; both on the device.  rows = N for a histogram per tile, 1 pooled over a batch.
+    Bin b holds the pixels that the luminosity rule calls tissue at threshold (b + 1) / 256 and not at b / 256 -- exactly: the bins are
+    defined by the rule's own compare, so ``counts[:, :k].sum(1)`` IS ``tissue_mask(images, k / 256)[1]``.  Integers add up exactly:
+    :meth:`pool` adds batches, slides or ranks into one row."""
+
+    counts: torch.Tensor
+    pixels: torch.Tensor
+
+    @staticmethod
+    def pool(*items: "LuminosityHistogram") -> "LuminosityHistogram":
+        """One row, (1, 256) and (1,): the sum of every row of every argument (a torch add where the tensors live; exact)."""
+        if not items:
+            raise ValueError("pool needs at least one LuminosityHistogram")
+        counts = pixels = None
+        for item in items:
+            c, p = _check_histogram(item)
+            c, p = c.sum(dim=0, keepdim=True), p.sum(dim=0, keepdim=True)
+            counts, pixels = (c, p) if counts is None else (counts + c, pixels + p)
+        return LuminosityHistogram(counts, pixels)
+
+
+class TissueDetection(NamedTuple):
+    """What :func:`otsu_mask` returns: ``mask`` (N, H, W) uint8, 1 = tissue, and ``counts`` (N,) int64 tissue pixels per tile, both on the
+    device; ``thresholds`` (N,) float64 on the CPU, the luminosity threshold each tile was cut at."""
+
+    mask: torch.Tensor
+    counts: torch.Tensor
+    thresholds: torch.Tensor
+
+
+def _check_histogram(hist: Any) -> tuple[torch.Tensor, torch.Tensor]:
+    if not (isinstance(hist, (tuple, list)) and len(hist) == 2 and all(isinstance(t, torch.Tensor) for t in hist)):
+        raise ValueError("expected a LuminosityHistogram (counts, pixels)")
+    counts, pixels = hist
+    if counts.dim() != 2 or counts.shape[1] != 256 or counts.shape[0] < 1:
+        raise ValueError(f"histogram counts must have shape (rows, 256) with rows >= 1, got {tuple(counts.shape)}")
+    if tuple(pixels.shape) != (counts.shape[0],):
+        raise ValueError(f"histogram pixels must have shape (rows,) = ({counts.shape[0]},), got {tuple(pixels.shape)}")
+    for name, value in (("counts", counts), ("pixels", pixels)):
+        if value.dtype != torch.int64:
+            raise ValueError(f"histogram {name} must have dtype int64, got {value.dtype}")
+    return counts, pixels
+
+
+def _check_images(images: Any, channel_axis: int, what: str) -> bool:
+    """The checks of :func:`tissue_mask` on its images; returns whether the channels come last."""
+    if not isinstance(images, torch.Tensor) or images.dim() != 4:
+        raise ValueError(f"{what} expects a 4-D image tensor, got {type(images).__name__} with shape {tuple(getattr(images, 'shape', ()))}")
+    last = channel_axis in (-1, 3)
+    if not last and channel_axis not in (1, -3):
+        raise ValueError(f"Unsupported channel_axis={channel_axis}")
+    if images.shape[-1 if last else 1] != 3:
+        raise ValueError(f"{what} expects 3 channels on axis {channel_axis}, got shape {tuple(images.shape)}")
+    return last
+
+
+def _check_radius(radius: Any, name: str, least: int) -> int:
+    if isinstance(radius, bool) or not isinstance(radius, int) or not least <= radius <= MAX_MORPHOLOGY_RADIUS:
+        raise ValueError(f"{name} must be an integer in {least}..{MAX_MORPHOLOGY_RADIUS}, got {radius!r}")
+    return radius
+
+
+def _check_element(element: Any) -> str:
+    if not isinstance(element, str) or element not in MORPHOLOGY_ELEMENTS:
+        raise ValueError(f"element must be one of {list(MORPHOLOGY_ELEMENTS)}, got {element!r}")
+    return element
+
+
+def _check_detection_mask(mask: Any) -> None:
+    """A mask handed to the morphology calls: :func:`check_mask_tensor`'s rules with the mask's own sizes, and it has to live on a GPU."""
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError(f"mask must be a uint8 / bool tensor, got {type(mask).__name__}")
+    if mask.dim() not in (3, 4) or (mask.dim() == 4 and mask.shape[1] != 1):
+        raise ValueError(f"mask shape must be (N, H, W) or (N, 1, H, W), got {tuple(mask.shape)}")
+    check_mask_tensor(mask, mask.shape[0], mask.shape[-2], mask.shape[-1], "cuda")
+
+
+def luminosity_histogram(images: torch.Tensor, *, pooled: bool = False, channel_axis: int = 1) -> LuminosityHistogram:
+    """256-bin integer histograms of lightness, per tile or (``pooled=True``) one for the batch: a memset and one streaming kernel
+    (include/stainx_hip.h: sx_luminosity_histogram).  ``images`` as for :func:`tissue_mask`.  See :class:`LuminosityHistogram` for what a
+    bin is; a NaN pixel lands in bin 255."""
+    last = _check_images(images, channel_axis, "luminosity_histogram")
+    from stainx_amd.backends.torch_hip_backend import luminosity_histogram_native
+
+    counts = luminosity_histogram_native(images, bool(pooled), last)
+    return LuminosityHistogram(counts, counts.sum(dim=1))
+
+
+def otsu_threshold(hist: LuminosityHistogram, *, fallback: float = DEFAULT_LUMINOSITY_THRESHOLD) -> torch.Tensor:
+    """Otsu's threshold of every row of ``hist``: float64 ``(rows,)`` on the CPU, each on the ``k / 256`` lattice (k = 1..255) -- what
+    :func:`tissue_mask` takes as ``luminosity_threshold``: class 0, the tissue, is the bins below k.
+
+    The between-class variance is computed over the bin indices from the integer counts in exact integer arithmetic on the host, so the
+    call copies ``rows x 256`` integers from the device: THIS IS A SYNCHRONISATION POINT (and the only one of :func:`otsu_mask`).  Among
+    the k that reach the exact maximum it takes ``(k_first + k_last) // 2``: between two separated modes every k of the gap is a
+    maximiser, and the first would put the cut on the tissue mode's shoulder.  A row in which no k has both classes populated (one
+    populated bin, or no pixels) gets ``fallback``.
+
+    Known hazard: Otsu ALWAYS splits.  On a tile without glass it splits the tissue itself, on a tile of glass alone it splits the glass.
+    Per-tile thresholds are for tiles that hold both; otherwise pool the histogram over the slide (:meth:`LuminosityHistogram.pool`,
+    ``pooled=True``) or threshold a thumbnail."""
+    counts, _ = _check_histogram(hist)
+    fallback = check_threshold(fallback)
+    out = []
+    for row in counts.cpu().tolist():
+        if any(c < 0 for c in row):
+            raise ValueError("histogram counts must not be negative")
+        total = sum(row)
+        weighted = sum(i * c for i, c in enumerate(row))
+        best_num, best_den, first, last = -1, 1, 0, 0
+        n0 = s0 = 0
+        for k in range(1, 256):
+            n0 += row[k - 1]
+            s0 += (k - 1) * row[k - 1]
+            n1 = total - n0
+            if n0 == 0 or n1 == 0:
+                continue
+            # w0 w1 (mu0 - mu1)^2 = (s0 n1 - s1 n0)^2 / (n0 n1 total^2): compared as fractions of integers
+            num, den = (s0 * n1 - (weighted - s0) * n0) ** 2, n0 * n1
+            side = num * best_den - best_num * den
+            if best_num < 0 or side > 0:
+                best_num, best_den, first, last = num, den, k, k
+            elif side == 0:
+                last = k
+        out.append((first + last) // 2 / 256.0 if best_num >= 0 else fallback)
+    return torch.tensor(out, dtype=torch.float64)
+
+
+def mask_morphology(mask: torch.Tensor, op: str, radius: int, *, element: str = "disk") -> tuple[torch.Tensor, torch.Tensor]:
+    """Binary morphology on a batch of masks: ``(mask, counts)`` -- (N, H, W) uint8, 1 / 0, and (N,) int64 set pixels per tile, on the device.
+    ``mask``: (N, H, W) or (N, 1, H, W), uint8 or bool, on the GPU, non-zero = set.  ``op``: "erode", "dilate", "open" (erode, then dilate)
+    or "close" (dilate, then erode); ``element``: "disk" (the offsets with dx^2 + dy^2 <= r^2, scikit-image's ``disk(r)``) or "square" (the
+    (2r+1)^2 box); ``radius``: 1..31.  Borders as OpenCV's default and scipy's ``binary_erosion(border_value=1)`` /
+    ``binary_dilation(border_value=0)``: what lies outside a tile never constrains the result, and tiles are independent.  One launch
+    for erode / dilate, two for open / close (include/stainx_hip.h: sx_mask_morphology)."""
+    if not isinstance(op, str) or op not in MORPHOLOGY_OPS:
+        raise ValueError(f"op must be one of {list(MORPHOLOGY_OPS)}, got {op!r}")
+    _check_radius(radius, "radius", 1)
+    _check_element(element)
+    _check_detection_mask(mask)
+    from stainx_amd.backends.torch_hip_backend import mask_morphology_native
+
+    return mask_morphology_native(mask, op, radius, element)
+
+
+def refine_mask(mask: torch.Tensor, *, open_radius: int = 0, close_radius: int = 0, element: str = "disk") -> tuple[torch.Tensor, torch.Tensor]:
+    """The clean-up of a tissue mask: an opening (specks of dust go) of ``open_radius``, then a closing (holes go) of ``close_radius``; a
+    radius of 0 skips its step.  Returns ``(mask, counts)`` as :func:`mask_morphology`; with both radii 0, the mask's own bytes as 1 / 0."""
+    _check_radius(open_radius, "open_radius", 0)
+    _check_radius(close_radius, "close_radius", 0)
+    _check_element(element)
+    _check_detection_mask(mask)
+    out = mask[:, 0] if mask.dim() == 4 else mask
+    counts = None
+    if open_radius:
+        out, counts = mask_morphology(out, "open", open_radius, element=element)
+    if close_radius:
+        out, counts = mask_morphology(out, "close", close_radius, element=element)
+    if counts is None:
+        out = (out != 0).to(torch.uint8)
+        counts = out.sum(dim=(1, 2), dtype=torch.int64)
+    return out, counts
+
+
+def otsu_mask(images: torch.Tensor, *, pooled: bool = False, channel_axis: int = 1, fallback: float = DEFAULT_LUMINOSITY_THRESHOLD, open_radius: int = 0,
+              close_radius: int = 0, element: str = "disk") -> TissueDetection:
+    """Tissue detection on a batch: the luminosity histogram, Otsu's threshold per tile (``pooled=True``: one for the batch, repeated), the
+    rule at each tile's threshold (sx_tissue_mask_tiles), then :func:`refine_mask`.  Without radii tile i's mask has the bits of
+    ``tissue_mask(images[i:i+1], thresholds[i])``.  One synchronisation point: :func:`otsu_threshold`, which also states the hazard --
+    Otsu always splits, so per-tile thresholds are for tiles that hold both tissue and glass; otherwise pool, or threshold a thumbnail."""
+    last = _check_images(images, channel_axis, "otsu_mask")
+    fallback = check_threshold(fallback)
+    _check_radius(open_radius, "open_radius", 0)
+    _check_radius(close_radius, "close_radius", 0)
+    _check_element(element)
+    from stainx_amd.backends.torch_hip_backend import tissue_mask_tiles_native
+
+    thresholds = otsu_threshold(luminosity_histogram(images, pooled=pooled, channel_axis=channel_axis), fallback=fallback)
+    if pooled:
+        thresholds = thresholds.repeat(images.shape[0])
+    mask, counts = tissue_mask_tiles_native(images, thresholds, last)
+    if open_radius or close_radius:
+        mask, counts = refine_mask(mask, open_radius=open_radius, close_radius=close_radius, element=element)
+    return TissueDetection(mask, counts, thresholds)
