@@ -3,7 +3,8 @@
 the sampled `precision="fast"` mode, how a batch is split over GPUs (one process per GPU, no collective for
 `transform`), the slide-level use: one source estimate, applied to batch after batch, per-tile statistics for Reinhard and
 histogram matching on a batch of tiles from different slides, their tissue masks for tiles with slide background, and slide-level
-histogram matching (histograms added up over batches, one table, one launch per batch).  Run on a ROCm GPU:  python examples/normalize_tiles.py
+histogram matching (histograms added up over batches, one table, one launch per batch), and a tissue mask detected on the device and
+cleaned by area (small objects go, small holes are filled).  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -15,7 +16,8 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from stainx_amd import HistogramMatching, HistogramStatistics, Macenko, Reinhard, StainNormalizerTransform, synth, tissue_mask  # noqa: E402
+from stainx_amd import (HistogramMatching, HistogramStatistics, Macenko, Reinhard, StainNormalizerTransform, mask_components, otsu_mask, remove_small_holes,  # noqa: E402
+                        remove_small_objects, synth, tissue_mask)
 from stainx_amd import distributed as sxd  # noqa: E402
 from stainx_amd.backends.torch_hip_backend import MacenkoHIP  # noqa: E402
 
@@ -117,6 +119,18 @@ def main() -> None:
     out = torch.cat([hm.apply(b, table) for b in batches])
     assert torch.equal(out, HistogramMatching(device=dev, statistics="batch", mask="luminosity").fit(reference.to(dev)).transform(slide_tiles))      # the slide as ONE batch, bit for bit
     print(f"[rank {rank}] HistogramMatching slide     {tuple(out.shape)} in {len(batches)} batches  tissue pixels {slide_hist.pixels.item()}")
+
+    # 10. a mask DETECTED on the device and cleaned BY AREA: Otsu's threshold pooled over the batch, then objects below 64 pixels go (dust,
+    #     pen specks) and holes below 256 pixels are filled (fat, lumina) -- what an opening and a closing cannot do without eating the
+    #     tissue's boundary and bridging its fragments.  Nothing returns to the host but Otsu's 256 counts.  A "hole" is ANY component of
+    #     the background, the glass at a tile's edge included: keep min_hole_area below a tile's glass, or threshold a thumbnail.
+    det = otsu_mask(edge, pooled=True, min_object_area=64, min_hole_area=256)
+    raw = otsu_mask(edge, pooled=True)
+    assert torch.equal(det.mask, remove_small_holes(remove_small_objects(raw.mask, 64)[0], 256)[0])      # the single calls, in that order
+    found = mask_components(det.mask)                                # MaskComponents: canonical labels, areas at the first pixels, counts
+    largest = found.areas.flatten(1).max(dim=1).values               # e.g. the largest tissue object of every tile, without leaving the device
+    out = Macenko(device=dev).fit(reference.to(dev)).transform(edge, mask=det.mask)
+    print(f"[rank {rank}] detected tissue mask        {tuple(out.shape)}  objects per tile {found.counts.tolist()}  largest {largest.tolist()}  tissue pixels {det.counts.tolist()}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

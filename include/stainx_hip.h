@@ -642,6 +642,43 @@ int sx_tissue_mask_tiles(const void* images_dev, int dtype, int64_t n_tiles, int
 int sx_mask_morphology(const uint8_t* mask_in_dev, uint8_t* mask_out_dev, int64_t n_tiles, int64_t height, int64_t width, int op,
                        int element, int radius, uint8_t* scratch_dev, unsigned long long* tile_counts_out_dev, void* stream);
 
+/* ---- Mask components: labelling and area filters ------------------------------------------------------
+ * What morphology cannot do: remove objects, and fill holes, BY AREA (tiatoolbox's MorphologicalMasker min_region_size, the object and
+ * hole filters of HistomicsTK- and CLAM-style pipelines, scikit-image's remove_small_objects / remove_small_holes on the Otsu mask).
+ * Masks as sx_mask_morphology takes them: n_tiles x height x width bytes, non-zero = set; tiles are independent, nothing outside a
+ * tile belongs to a component and no component continues into the next tile.
+ *   connectivity   4: the edge neighbours (scipy's generate_binary_structure(2, 1), scikit-image's connectivity=1); 8: the diagonals
+ *                  too (np.ones((3, 3)), connectivity=2, OpenCV's default).  Anything else is SX_ERR_BAD_ARG.
+ *   label          of a set pixel: 1 + (y * width + x) of the FIRST pixel of its component in raster order, within its tile; 0 of an
+ *                  unset pixel.  A function of the mask alone (scipy.ndimage.label, canonicalised).  int32: height x width must not
+ *                  exceed 2^31 - 2 (SX_ERR_BAD_ARG).
+ *
+ * sx_mask_components: replaces scipy.ndimage.label / skimage.measure.label + np.bincount on the host.
+ *   invert                   != 0: the components of the COMPLEMENT are labelled (the "holes": a background region that touches the
+ *                            tile's edge is one of them)
+ *   labels_out_dev           n_tiles x height x width int32 (required)
+ *   areas_out_dev            the same shape, int32: at a component's first pixel its pixel count, 0 everywhere else; may be NULL
+ *   tile_components_out_dev  n_tiles uint64, the components per tile; may be NULL
+ *   Three launches (two where a tile is one block of 256 x 64) and the clear of the counts; no workspace.
+ * sx_mask_area_filter: replaces skimage.morphology.remove_small_objects (holes == 0) and remove_small_holes (holes != 0).
+ *   holes == 0: every set pixel whose component has fewer than min_area pixels is cleared (an area equal to min_area stays);
+ *   holes != 0: every unset pixel whose component OF THE COMPLEMENT has fewer than min_area pixels is set -- scikit-image's rule, under
+ *   which glass that touches the tile's edge counts as a hole: choose min_area below a tile's glass.  Bit for bit
+ *   holes(m) == 1 - objects(1 - m).
+ *   mask_out_dev         n_tiles x height x width bytes, 1 / 0; must be neither mask_in_dev nor inside the workspace (SX_ERR_BAD_ARG)
+ *   min_area             at least 1 (SX_ERR_BAD_ARG below); 1 gives the mask's own bits as 1 / 0; above height x width everything is
+ *                        removed (filled)
+ *   workspace_dev        sx_mask_components_workspace_bytes() bytes, any contents
+ *   tile_counts_out_dev  n_tiles uint64, the set pixels of the result per tile; may be NULL
+ *   The launches of sx_mask_components, one pixel-local launch and the clear of the counts.
+ * sx_mask_components_workspace_bytes: host only; 0 for non-positive sizes, 8 bytes per pixel (labels and areas) and room to align. */
+size_t sx_mask_components_workspace_bytes(int64_t n_tiles, int64_t height, int64_t width);
+int sx_mask_components(const uint8_t* mask_in_dev, int64_t n_tiles, int64_t height, int64_t width, int connectivity, int invert,
+                       int32_t* labels_out_dev, int32_t* areas_out_dev, unsigned long long* tile_components_out_dev, void* stream);
+int sx_mask_area_filter(const uint8_t* mask_in_dev, uint8_t* mask_out_dev, int64_t n_tiles, int64_t height, int64_t width,
+                        int connectivity, int holes, int64_t min_area, void* workspace_dev, unsigned long long* tile_counts_out_dev,
+                        void* stream);
+
 /* Reinhard.  per_tile != 0: every tile its own statistics (N rows, a tile's result does not depend on its neighbours); per_tile == 0: one
  * set pooled over the tissue of the whole batch (one row).  Workspace: sx_reinhard_masked_workspace_bytes(); any contents are accepted
  * and a workspace that was READY (sx_reinhard_transform_ready) is left ready, so the calls may alternate with that one and with

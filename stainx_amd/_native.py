@@ -39,6 +39,7 @@ PFIT_COMPACT = 32768
 MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}      # sx_mask_morphology: SX_MORPH_*, SX_ELEMENT_*, SX_MORPH_MAX_RADIUS
 MORPH_ELEMENTS = {"square": 0, "disk": 1}
 MORPH_MAX_RADIUS = 31
+CONNECTIVITIES = (4, 8)      # sx_mask_components, sx_mask_area_filter
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -126,6 +127,10 @@ SIGNATURES = {
     "sx_tissue_y_cut": (_c.c_float, [_c.c_double]),
     "sx_tissue_mask_tiles": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "sx_mask_morphology": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    # mask components: canonical labels, areas at the first pixels, area filters on objects and holes
+    "sx_mask_components_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "sx_mask_components": (_int, [_vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "sx_mask_area_filter": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp]),
     "sx_reinhard_masked_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -132,6 +132,41 @@ def mask_morphology_native(mask: torch.Tensor, op: str, radius: int, element: st
     return out, counts
 
 
+def mask_components_native(mask: torch.Tensor, connectivity: int, holes: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``stainx_amd.mask_components`` behind its checks: (N, H, W) int32 labels and areas, (N,) int64 components per tile (sx_mask_components)."""
+    base = TorchHIPBackendBase(mask.device)
+    src = _mask_bytes(mask, base.device)
+    n, h, w = src.shape
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=base.device)
+    areas = torch.empty((n, h, w), dtype=torch.int32, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return labels, areas, counts
+    with _native.on_device(base.device):
+        rc = base._lib.sx_mask_components(src.data_ptr(), n, h, w, int(connectivity), int(holes), labels.data_ptr(), areas.data_ptr(), counts.data_ptr(),
+                                          _native.stream_ptr(base.device))
+    _native.check(rc, "sx_mask_components")
+    return labels, areas, counts
+
+
+def mask_area_filter_native(mask: torch.Tensor, min_area: int, connectivity: int, holes: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """``stainx_amd.remove_small_objects`` / ``remove_small_holes`` behind their checks: (N, H, W) uint8 result, 1 / 0, and (N,) int64 set pixels per
+    tile (sx_mask_area_filter; the workspace comes from its size query)."""
+    base = TorchHIPBackendBase(mask.device)
+    src = _mask_bytes(mask, base.device)
+    n, h, w = src.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return out, counts
+    workspace = torch.empty((int(base._lib.sx_mask_components_workspace_bytes(n, h, w)),), dtype=torch.uint8, device=base.device)
+    with _native.on_device(base.device):
+        rc = base._lib.sx_mask_area_filter(src.data_ptr(), out.data_ptr(), n, h, w, int(connectivity), int(holes), int(min_area), workspace.data_ptr(), counts.data_ptr(),
+                                           _native.stream_ptr(base.device))
+    _native.check(rc, "sx_mask_area_filter")
+    return out, counts
+
+
 class MacenkoHIP(TorchHIPBackendBase):
     """Macenko transform / fit on the GPU (numerics of MacenkoTorch, torch_backend.py:358-560)."""
 

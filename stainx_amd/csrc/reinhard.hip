@@ -1032,3 +1032,6 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
 
 // ---- tissue detection: luminosity histograms (for Otsu thresholds), per-tile cuts, binary morphology on masks ------------------------------
 #include "tissue_detect.hpp"
+
+// ---- connected components of masks, and the area filters on them ----------------------------------------------------------------------
+#include "components.hpp"

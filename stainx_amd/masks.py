@@ -7,7 +7,8 @@ normaliser's device, non-zero = tissue.  Every kernel decides a pixel with the s
 a mask made by :func:`tissue_mask` give the same bits everywhere.
 
 Tissue detection (the second half of the file): :func:`luminosity_histogram`, :func:`otsu_threshold`, :func:`otsu_mask` -- a threshold taken
-from the data -- and :func:`mask_morphology`, :func:`refine_mask` -- opening and closing of a mask.
+from the data -- and :func:`mask_morphology`, :func:`refine_mask` -- opening and closing of a mask; :func:`mask_components`,
+:func:`remove_small_objects`, :func:`remove_small_holes` -- connected components and the filters by area that morphology cannot do.
 """
 from __future__ import annotations
 
@@ -87,6 +88,7 @@ def tissue_mask(images: torch.Tensor, luminosity_threshold: float = DEFAULT_LUMI
 MORPHOLOGY_OPS = ("erode", "dilate", "open", "close")
 MORPHOLOGY_ELEMENTS = ("square", "disk")
 MAX_MORPHOLOGY_RADIUS = 31      # include/stainx_hip.h: SX_MORPH_MAX_RADIUS
+CONNECTIVITIES = (4, 8)         # 4: edge neighbours (scikit-image's connectivity=1); 8: diagonals too (connectivity=2, OpenCV's default)
 
 
 class LuminosityHistogram(NamedTuple):
@@ -119,6 +121,18 @@ class TissueDetection(NamedTuple):
     mask: torch.Tensor
     counts: torch.Tensor
     thresholds: torch.Tensor
+
+
+class MaskComponents(NamedTuple):
+    """What :func:`mask_components` returns, all on the device.  ``labels``: (N, H, W) int32 -- a set pixel holds ``1 + (y * W + x)`` of the first
+    pixel of its component in raster order within its tile, an unset pixel 0: a function of the mask alone, the same on every run
+    (``scipy.ndimage.label``, canonicalised).  ``areas``: (N, H, W) int32 -- at a component's first pixel its pixel count, 0 everywhere
+    else (``areas[labels - 1]`` gathers a pixel's area; ``areas.flatten(1).topk(k)`` finds the k largest).  ``counts``: (N,) int64, the
+    components per tile."""
+
+    labels: torch.Tensor
+    areas: torch.Tensor
+    counts: torch.Tensor
 
 
 def _check_histogram(hist: Any) -> tuple[torch.Tensor, torch.Tensor]:
@@ -157,6 +171,18 @@ def _check_element(element: Any) -> str:
     if not isinstance(element, str) or element not in MORPHOLOGY_ELEMENTS:
         raise ValueError(f"element must be one of {list(MORPHOLOGY_ELEMENTS)}, got {element!r}")
     return element
+
+
+def _check_area(area: Any, name: str, least: int) -> int:
+    if isinstance(area, bool) or not isinstance(area, int) or area < least:
+        raise ValueError(f"{name} must be an integer of at least {least}, got {area!r}")
+    return area
+
+
+def _check_connectivity(connectivity: Any) -> int:
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {list(CONNECTIVITIES)}, got {connectivity!r}")
+    return connectivity
 
 
 def _check_detection_mask(mask: Any) -> None:
@@ -236,19 +262,72 @@ def mask_morphology(mask: torch.Tensor, op: str, radius: int, *, element: str = 
     return mask_morphology_native(mask, op, radius, element)
 
 
-def refine_mask(mask: torch.Tensor, *, open_radius: int = 0, close_radius: int = 0, element: str = "disk") -> tuple[torch.Tensor, torch.Tensor]:
-    """The clean-up of a tissue mask: an opening (specks of dust go) of ``open_radius``, then a closing (holes go) of ``close_radius``; a
-    radius of 0 skips its step.  Returns ``(mask, counts)`` as :func:`mask_morphology`; with both radii 0, the mask's own bytes as 1 / 0."""
+def mask_components(mask: torch.Tensor, *, connectivity: int = 8, holes: bool = False) -> MaskComponents:
+    """Connected components of a batch of masks: :class:`MaskComponents` ``(labels, areas, counts)``.  ``mask`` as for :func:`mask_morphology`;
+    tiles are independent: nothing outside a tile belongs to a component, and none continues into the next tile.  ``connectivity``: 4
+    (edge neighbours: scipy's ``generate_binary_structure(2, 1)``, scikit-image's ``connectivity=1``) or 8 (diagonals too: ``np.ones((3, 3))``,
+    ``connectivity=2``, OpenCV's default).  ``holes=True`` labels the components of the COMPLEMENT under the same connectivity -- a
+    background region that touches the tile's edge is one of them.  Three launches, no synchronisation (include/stainx_hip.h:
+    sx_mask_components)."""
+    _check_connectivity(connectivity)
+    _check_detection_mask(mask)
+    from stainx_amd.backends.torch_hip_backend import mask_components_native
+
+    return MaskComponents(*mask_components_native(mask, connectivity, bool(holes)))
+
+
+def remove_small_objects(mask: torch.Tensor, min_area: int, *, connectivity: int = 8) -> tuple[torch.Tensor, torch.Tensor]:
+    """Clears every set pixel whose component has fewer than ``min_area`` pixels (an area equal to ``min_area`` stays): scikit-image's
+    ``remove_small_objects``, tiatoolbox's ``min_region_size``.  Returns ``(mask, counts)`` as :func:`mask_morphology`; ``min_area=1`` gives the
+    mask's own bits as 1 / 0, a value above H * W clears everything.  Components as in :func:`mask_components`.  No synchronisation
+    (include/stainx_hip.h: sx_mask_area_filter)."""
+    _check_area(min_area, "min_area", 1)
+    _check_connectivity(connectivity)
+    _check_detection_mask(mask)
+    from stainx_amd.backends.torch_hip_backend import mask_area_filter_native
+
+    return mask_area_filter_native(mask, min_area, connectivity, False)
+
+
+def remove_small_holes(mask: torch.Tensor, min_area: int, *, connectivity: int = 8) -> tuple[torch.Tensor, torch.Tensor]:
+    """Sets every unset pixel whose component OF THE COMPLEMENT (same connectivity) has fewer than ``min_area`` pixels: scikit-image's
+    ``remove_small_holes``.  Bit for bit ``1 - remove_small_objects(1 - mask, min_area)``.  Returns ``(mask, counts)`` as
+    :func:`mask_morphology`; ``min_area=1`` gives the mask's own bits as 1 / 0, a value above H * W sets everything.
+
+    Known hazard: a hole is ANY component of the complement -- a background region that touches the tile's edge counts as one.  On a
+    tile whose glass is smaller than ``min_area`` THE GLASS IS FILLED.  Threshold a thumbnail, or choose ``min_area`` below a tile's glass."""
+    _check_area(min_area, "min_area", 1)
+    _check_connectivity(connectivity)
+    _check_detection_mask(mask)
+    from stainx_amd.backends.torch_hip_backend import mask_area_filter_native
+
+    return mask_area_filter_native(mask, min_area, connectivity, True)
+
+
+def refine_mask(mask: torch.Tensor, *, open_radius: int = 0, close_radius: int = 0, element: str = "disk", min_object_area: int = 0, min_hole_area: int = 0,
+                connectivity: int = 8) -> tuple[torch.Tensor, torch.Tensor]:
+    """The clean-up of a tissue mask, in this order: objects below ``min_object_area`` pixels go (:func:`remove_small_objects`), an opening
+    (specks of dust go) of ``open_radius``, a closing (holes go) of ``close_radius``, holes below ``min_hole_area`` pixels are filled
+    (:func:`remove_small_holes`, whose hazard applies: glass smaller than ``min_hole_area`` is filled, edge-touching or not).  A radius or an
+    area of 0 skips its step: filtering by area first lets the opening stay small, and filling last measures what the closing left.
+    Returns ``(mask, counts)`` as :func:`mask_morphology`; with every step skipped, the mask's own bytes as 1 / 0."""
     _check_radius(open_radius, "open_radius", 0)
     _check_radius(close_radius, "close_radius", 0)
     _check_element(element)
+    _check_area(min_object_area, "min_object_area", 0)
+    _check_area(min_hole_area, "min_hole_area", 0)
+    _check_connectivity(connectivity)
     _check_detection_mask(mask)
     out = mask[:, 0] if mask.dim() == 4 else mask
     counts = None
+    if min_object_area:
+        out, counts = remove_small_objects(out, min_object_area, connectivity=connectivity)
     if open_radius:
         out, counts = mask_morphology(out, "open", open_radius, element=element)
     if close_radius:
         out, counts = mask_morphology(out, "close", close_radius, element=element)
+    if min_hole_area:
+        out, counts = remove_small_holes(out, min_hole_area, connectivity=connectivity)
     if counts is None:
         out = (out != 0).to(torch.uint8)
         counts = out.sum(dim=(1, 2), dtype=torch.int64)
@@ -256,9 +335,10 @@ def refine_mask(mask: torch.Tensor, *, open_radius: int = 0, close_radius: int =
 
 
 def otsu_mask(images: torch.Tensor, *, pooled: bool = False, channel_axis: int = 1, fallback: float = DEFAULT_LUMINOSITY_THRESHOLD, open_radius: int = 0,
-              close_radius: int = 0, element: str = "disk") -> TissueDetection:
+              close_radius: int = 0, element: str = "disk", min_object_area: int = 0, min_hole_area: int = 0, connectivity: int = 8) -> TissueDetection:
     """Tissue detection on a batch: the luminosity histogram, Otsu's threshold per tile (``pooled=True``: one for the batch, repeated), the
-    rule at each tile's threshold (sx_tissue_mask_tiles), then :func:`refine_mask`.  Without radii tile i's mask has the bits of
+    rule at each tile's threshold (sx_tissue_mask_tiles), then :func:`refine_mask` with the radii and areas given (its order: small objects
+    go, opening, closing, small holes are filled -- and its hazard: glass below ``min_hole_area`` is filled).  Without them tile i's mask has the bits of
     ``tissue_mask(images[i:i+1], thresholds[i])``.  One synchronisation point: :func:`otsu_threshold`, which also states the hazard --
     Otsu always splits, so per-tile thresholds are for tiles that hold both tissue and glass; otherwise pool, or threshold a thumbnail."""
     last = _check_images(images, channel_axis, "otsu_mask")
@@ -266,12 +346,16 @@ def otsu_mask(images: torch.Tensor, *, pooled: bool = False, channel_axis: int =
     _check_radius(open_radius, "open_radius", 0)
     _check_radius(close_radius, "close_radius", 0)
     _check_element(element)
+    _check_area(min_object_area, "min_object_area", 0)
+    _check_area(min_hole_area, "min_hole_area", 0)
+    _check_connectivity(connectivity)
     from stainx_amd.backends.torch_hip_backend import tissue_mask_tiles_native
 
     thresholds = otsu_threshold(luminosity_histogram(images, pooled=pooled, channel_axis=channel_axis), fallback=fallback)
     if pooled:
         thresholds = thresholds.repeat(images.shape[0])
     mask, counts = tissue_mask_tiles_native(images, thresholds, last)
-    if open_radius or close_radius:
-        mask, counts = refine_mask(mask, open_radius=open_radius, close_radius=close_radius, element=element)
+    if open_radius or close_radius or min_object_area or min_hole_area:
+        mask, counts = refine_mask(mask, open_radius=open_radius, close_radius=close_radius, element=element, min_object_area=min_object_area,
+                                   min_hole_area=min_hole_area, connectivity=connectivity)
     return TissueDetection(mask, counts, thresholds)
