@@ -679,6 +679,44 @@ int sx_mask_area_filter(const uint8_t* mask_in_dev, uint8_t* mask_out_dev, int64
                         int connectivity, int holes, int64_t min_area, void* workspace_dev, unsigned long long* tile_counts_out_dev,
                         void* stream);
 
+/* ---- Saturation-channel tissue detection: saturation maps, a median filter, level histograms and thresholds ----
+ * The front half of CLAM's segmentTissue: threshold the HSV saturation ("is the pixel coloured") after a median filter, where the
+ * luminosity rule asks "is the pixel dark".  A grey pixel -- shadow, coverslip edge, colourless dust -- has saturation 0.  Every result
+ * is an integer and every definition exact.  Level maps are n_tiles x height x width bytes; tiles are independent.
+ *
+ * The 8-bit level of a stored element: a uint8 element is its own level; any other type starts from its unit value v (float32; a
+ *   double is rounded to float first) and the level is rintf(fminf(fmaxf(255.0f * v, 0.0f), 255.0f)): one float32 multiply, a clamp,
+ *   round-half-even; +inf gives 255, -inf 0.  A u / 255 float32 or float64 tile has the levels of its uint8 original.  So has an
+ *   f16 or bf16 tile rounded from u / 255, but bf16 only just: its rounding moves 255 v by up to 0.498 of a level, so any further
+ *   arithmetic on a bf16 tile loses levels.
+ * sx_saturation_map: levels_out_dev[pixel] = S, one streaming launch.  With M and m the largest and smallest of the pixel's three
+ *   levels: S = 0 if M == 0, else (510 (M - m) + M) / (2 M) in integer division -- 255 (M - m) / M rounded half up, in 0..255.  A pixel
+ *   with a NaN in any channel has S = 0 (background, as under the luminosity rule).  This is the library's own exact rule; it is not
+ *   pinned to any other library's table-based conversion.  images_dev, dtype, channels_last as sx_tissue_mask; NULL pointers and
+ *   non-positive sizes are SX_ERR_BAD_ARG, an unknown dtype SX_ERR_DTYPE.
+ * sx_median_filter_u8: levels_out_dev[pixel] = the value of rank (size^2 + 1) / 2 among the size x size window centred on the pixel,
+ *   the window read with replicated borders (cv2.medianBlur's border, scipy.ndimage.median_filter(mode="nearest")) inside the pixel's
+ *   own tile.  On a 0 / 1 mask this is the majority filter.
+ *   size             odd, 3 .. SX_MEDIAN_MAX_SIZE; anything else is SX_ERR_BAD_ARG
+ *   levels_out_dev   must not be levels_in_dev (SX_ERR_BAD_ARG: not in place)
+ *   One launch, no workspace, no synchronisation: a workgroup stages its 64 x 64 block with the halo on chip once, as eight bit planes.
+ * sx_level_histogram: counts_out_dev[row][b] = the pixels of level b; rows = n_tiles, or 1 with pooled != 0.  rows x 256 uint64
+ *   (required).  One memset and one launch.
+ * sx_level_mask_tiles: mask_out_dev = 1 where level > tile_thresholds_dev[tile], else 0 (cv2's THRESH_BINARY, CLAM's sthresh).
+ *   tile_thresholds_dev   n_tiles int32 in DEVICE memory read by the kernel (a captured call replayed after new thresholds were
+ *                         written uses them; NULL is SX_ERR_BAD_ARG).  A negative threshold sets the whole tile, one >= 255 clears it.
+ *   mask_out_dev, tile_counts_out_dev (n_tiles uint64 set pixels per tile): either may be NULL, not both.
+ *   One launch and the clear of the counts. */
+#define SX_MEDIAN_MAX_SIZE 15
+int sx_saturation_map(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                      uint8_t* levels_out_dev, void* stream);
+int sx_median_filter_u8(const uint8_t* levels_in_dev, uint8_t* levels_out_dev, int64_t n_tiles, int64_t height, int64_t width, int size,
+                        void* stream);
+int sx_level_histogram(const uint8_t* levels_dev, int64_t n_tiles, int64_t height, int64_t width, int pooled,
+                       unsigned long long* counts_out_dev, void* stream);
+int sx_level_mask_tiles(const uint8_t* levels_dev, int64_t n_tiles, int64_t height, int64_t width, const int32_t* tile_thresholds_dev,
+                        uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
+
 /* Reinhard.  per_tile != 0: every tile its own statistics (N rows, a tile's result does not depend on its neighbours); per_tile == 0: one
  * set pooled over the tissue of the whole batch (one row).  Workspace: sx_reinhard_masked_workspace_bytes(); any contents are accepted
  * and a workspace that was READY (sx_reinhard_transform_ready) is left ready, so the calls may alternate with that one and with

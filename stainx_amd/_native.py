@@ -40,6 +40,7 @@ MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}      # sx_mask_morp
 MORPH_ELEMENTS = {"square": 0, "disk": 1}
 MORPH_MAX_RADIUS = 31
 CONNECTIVITIES = (4, 8)      # sx_mask_components, sx_mask_area_filter
+MEDIAN_MAX_SIZE = 15         # sx_median_filter_u8: SX_MEDIAN_MAX_SIZE
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -131,6 +132,11 @@ SIGNATURES = {
     "sx_mask_components_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "sx_mask_components": (_int, [_vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "sx_mask_area_filter": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _int, _i64, _vp, _vp, _vp]),
+    # saturation-channel tissue detection: saturation maps, the median filter, level histograms, level thresholds per tile
+    "sx_saturation_map": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp]),
+    "sx_median_filter_u8": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp]),
+    "sx_level_histogram": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp]),
+    "sx_level_mask_tiles": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sx_reinhard_masked_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

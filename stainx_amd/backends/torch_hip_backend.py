@@ -167,6 +167,64 @@ def mask_area_filter_native(mask: torch.Tensor, min_area: int, connectivity: int
     return out, counts
 
 
+def saturation_map_native(images: torch.Tensor, channels_last: bool) -> torch.Tensor:
+    """``stainx_amd.saturation_map`` behind its checks: (N, H, W) uint8 saturation levels on the device (include/stainx_hip.h: sx_saturation_map)."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images = images.to(base.device).contiguous()
+    n, h, w = _image_sizes(images, channels_last)
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    if n == 0 or h * w == 0:
+        return out
+    with _native.on_device(base.device):
+        rc = base._lib.sx_saturation_map(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), out.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_saturation_map")
+    return out
+
+
+def median_filter_native(levels: torch.Tensor, size: int) -> torch.Tensor:
+    """``stainx_amd.median_filter`` behind its checks: (N, H, W) uint8 medians of the size x size windows (sx_median_filter_u8)."""
+    base = TorchHIPBackendBase(levels.device)
+    src = _mask_bytes(levels, base.device)
+    n, h, w = src.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    if n == 0 or h * w == 0:
+        return out
+    with _native.on_device(base.device):
+        rc = base._lib.sx_median_filter_u8(src.data_ptr(), out.data_ptr(), n, h, w, int(size), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_median_filter_u8")
+    return out
+
+
+def level_histogram_native(levels: torch.Tensor, pooled: bool) -> torch.Tensor:
+    """``stainx_amd.level_histogram`` behind its checks: (rows, 256) int64 counts on the device (sx_level_histogram)."""
+    base = TorchHIPBackendBase(levels.device)
+    src = _mask_bytes(levels, base.device)
+    n, h, w = src.shape
+    counts = torch.zeros((1 if pooled else n, 256), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return counts
+    with _native.on_device(base.device):
+        rc = base._lib.sx_level_histogram(src.data_ptr(), n, h, w, int(pooled), counts.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_level_histogram")
+    return counts
+
+
+def level_mask_native(levels: torch.Tensor, thresholds: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``stainx_amd.level_mask`` behind its checks (``thresholds``: (N,) int32 on the device): (N, H, W) uint8 mask, 1 where level > threshold, and
+    (N,) int64 set pixels per tile (sx_level_mask_tiles)."""
+    base = TorchHIPBackendBase(levels.device)
+    src = _mask_bytes(levels, base.device)
+    n, h, w = src.shape
+    mask = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
+    if n == 0 or h * w == 0:
+        return mask, counts
+    with _native.on_device(base.device):
+        rc = base._lib.sx_level_mask_tiles(src.data_ptr(), n, h, w, thresholds.data_ptr(), mask.data_ptr(), counts.data_ptr(), _native.stream_ptr(base.device))
+    _native.check(rc, "sx_level_mask_tiles")
+    return mask, counts
+
+
 class MacenkoHIP(TorchHIPBackendBase):
     """Macenko transform / fit on the GPU (numerics of MacenkoTorch, torch_backend.py:358-560)."""
 

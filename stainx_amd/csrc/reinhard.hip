@@ -1035,3 +1035,6 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
 
 // ---- connected components of masks, and the area filters on them ----------------------------------------------------------------------
 #include "components.hpp"
+
+// ---- saturation-channel tissue detection: saturation maps, the median filter, level histograms and level thresholds ------------------------
+#include "saturation.hpp"

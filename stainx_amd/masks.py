@@ -9,6 +9,10 @@ a mask made by :func:`tissue_mask` give the same bits everywhere.
 Tissue detection (the second half of the file): :func:`luminosity_histogram`, :func:`otsu_threshold`, :func:`otsu_mask` -- a threshold taken
 from the data -- and :func:`mask_morphology`, :func:`refine_mask` -- opening and closing of a mask; :func:`mask_components`,
 :func:`remove_small_objects`, :func:`remove_small_holes` -- connected components and the filters by area that morphology cannot do.
+
+Saturation-channel detection (the end of the file; CLAM's ``segmentTissue``): :func:`saturation_map`, :func:`median_filter`,
+:func:`level_histogram`, :func:`otsu_level`, :func:`level_mask` and the pipeline :func:`saturation_mask` -- "is the pixel coloured" where the
+luminosity rule asks "is the pixel dark".
 """
 from __future__ import annotations
 
@@ -359,3 +363,177 @@ def otsu_mask(images: torch.Tensor, *, pooled: bool = False, channel_axis: int =
         mask, counts = refine_mask(mask, open_radius=open_radius, close_radius=close_radius, element=element, min_object_area=min_object_area,
                                    min_hole_area=min_hole_area, connectivity=connectivity)
     return TissueDetection(mask, counts, thresholds)
+
+
+# ------------------------------------------------------------------------------------------------ saturation-channel tissue detection
+# The front half of CLAM's segmentTissue: the HSV saturation as 8-bit levels, a median filter on it, a threshold (fixed, or Otsu on the
+# level histogram), and the mask ``level > t``.  What follows the mask -- refine_mask, the area filters, every ``mask=`` -- takes it as it is.
+MEDIAN_SIZES = (3, 5, 7, 9, 11, 13, 15)      # include/stainx_hip.h: odd, 3 .. SX_MEDIAN_MAX_SIZE
+DEFAULT_SATURATION_FALLBACK = 8              # CLAM's sthresh
+
+
+class LevelHistogram(NamedTuple):
+    """256-bin integer histograms of a level map (:func:`level_histogram` returns it; :func:`otsu_level` and :func:`otsu_threshold` take it).
+    ``counts``: (rows, 256) int64, bin b = the pixels of level b; ``pixels``: (rows,) int64, the row sums; both on the device.  rows = N for
+    a histogram per tile, 1 pooled over a batch.  Integers add up exactly: :meth:`pool` adds batches, slides or ranks into one row."""
+
+    counts: torch.Tensor
+    pixels: torch.Tensor
+
+    @staticmethod
+    def pool(*items: "LevelHistogram") -> "LevelHistogram":
+        """One row, (1, 256) and (1,): the sum of every row of every argument (a torch add where the tensors live; exact)."""
+        if not items:
+            raise ValueError("pool needs at least one LevelHistogram")
+        return LevelHistogram(*LuminosityHistogram.pool(*items))
+
+
+class SaturationDetection(NamedTuple):
+    """What :func:`saturation_mask` returns: ``mask`` (N, H, W) uint8, 1 = tissue, and ``counts`` (N,) int64 tissue pixels per tile, both on the
+    device; ``thresholds`` (N,) int64 on the CPU, the saturation level each tile was cut at (tissue iff level > threshold)."""
+
+    mask: torch.Tensor
+    counts: torch.Tensor
+    thresholds: torch.Tensor
+
+
+def _check_levels(levels: Any, what: str) -> None:
+    """A level map: uint8 (a bool mask counts as 0 / 1), (N, H, W) or (N, 1, H, W), on a GPU."""
+    if not isinstance(levels, torch.Tensor):
+        raise ValueError(f"{what} expects a uint8 / bool tensor of levels, got {type(levels).__name__}")
+    if levels.dim() not in (3, 4) or (levels.dim() == 4 and levels.shape[1] != 1):
+        raise ValueError(f"levels shape must be (N, H, W) or (N, 1, H, W), got {tuple(levels.shape)}")
+    if levels.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"levels dtype must be uint8 or bool, got {levels.dtype}")
+    if levels.device.type != "cuda":
+        raise ValueError(f"levels device must be a GPU, got {levels.device}")
+
+
+def _check_median_size(size: Any, name: str = "size") -> int:
+    if isinstance(size, bool) or not isinstance(size, int) or size not in MEDIAN_SIZES:
+        raise ValueError(f"{name} must be an odd integer in 3..{MEDIAN_SIZES[-1]}, got {size!r}")
+    return size
+
+
+def _check_level(level: Any, name: str) -> int:
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= 254:
+        raise ValueError(f"{name} must be an integer level in 0..254, got {level!r}")
+    return level
+
+
+def saturation_map(images: torch.Tensor, *, channel_axis: int = 1) -> torch.Tensor:
+    """The HSV saturation of a batch as 8-bit levels: (N, H, W) uint8 on the device, one streaming kernel (include/stainx_hip.h:
+    sx_saturation_map).  ``images`` as for :func:`tissue_mask`.
+
+    The 8-bit level of a stored element: a uint8 is its own level; any other type gives ``rint(clip(255 * v, 0, 255))`` of its unit value
+    in float32 (a double is rounded to float first; round-half-even; +inf is 255, -inf 0).  So a ``u / 255`` float32 or float64 tile has
+    the levels, and the map, of its uint8 original.  So has an f16 or bf16 tile rounded from ``u / 255``, but bf16 only just: its
+    rounding moves ``255 * v`` by up to 0.498 of a level, and any further arithmetic on a bf16 tile loses levels.  With M and m the largest and
+    smallest of a pixel's three levels, ``S = 0`` if ``M == 0``, else ``(510 * (M - m) + M) // (2 * M)``: 255 (M - m) / M rounded half up, in
+    0..255.  A pixel with a NaN in any channel has S = 0: background, as under the luminosity rule.  This is the package's own exact
+    rule; it is not pinned to OpenCV's table-based conversion."""
+    last = _check_images(images, channel_axis, "saturation_map")
+    from stainx_amd.backends.torch_hip_backend import saturation_map_native
+
+    return saturation_map_native(images, last)
+
+
+def median_filter(levels: torch.Tensor, size: int) -> torch.Tensor:
+    """The ``size x size`` median of a batch of level maps: (N, H, W) uint8 on the device, each the value of rank ``(size**2 + 1) // 2`` among
+    the window centred on the pixel.  ``levels``: (N, H, W) or (N, 1, H, W) uint8 on the GPU; a bool mask is read as 0 / 1, on which the
+    median is the majority filter.  ``size``: odd, 3..15.  The window is read with replicated borders inside the pixel's own tile
+    (``cv2.medianBlur``'s border; bit for bit ``scipy.ndimage.median_filter(size=size, mode="nearest")``); tiles never see each other.
+    One launch, no workspace, no synchronisation (include/stainx_hip.h: sx_median_filter_u8)."""
+    _check_median_size(size)
+    _check_levels(levels, "median_filter")
+    from stainx_amd.backends.torch_hip_backend import median_filter_native
+
+    return median_filter_native(levels, size)
+
+
+def level_histogram(levels: torch.Tensor, *, pooled: bool = False) -> LevelHistogram:
+    """256-bin integer histograms of level maps, per tile or (``pooled=True``) one for the batch: bin b counts the pixels of level b.  A
+    memset and one launch (include/stainx_hip.h: sx_level_histogram).  ``levels`` as for :func:`median_filter`."""
+    _check_levels(levels, "level_histogram")
+    from stainx_amd.backends.torch_hip_backend import level_histogram_native
+
+    counts = level_histogram_native(levels, bool(pooled))
+    return LevelHistogram(counts, counts.sum(dim=1))
+
+
+def otsu_level(hist: LevelHistogram, *, fallback: int = DEFAULT_SATURATION_FALLBACK) -> torch.Tensor:
+    """Otsu's threshold of every row of a level histogram as a LEVEL: int64 ``(rows,)`` on the CPU, what :func:`level_mask` takes.  It is
+    ``256 * otsu_threshold(hist, fallback=(fallback + 1) / 256) - 1``: class 0, the background, is the levels <= t (cv2's Otsu convention) and
+    tissue is ``level > t``.  ``fallback``: 0..254, the level of a row with no split (one populated bin, or no pixels); 8 is CLAM's ``sthresh``.
+
+    It inherits everything :func:`otsu_threshold` states: the synchronisation point, the plateau rule (among the exact maximisers the
+    middle of the first and the last, so two separated modes are cut in the middle of the gap) and the hazard -- Otsu ALWAYS splits: a
+    tile of tissue alone, or of glass alone, is split all the same.  Pool the histogram (:meth:`LevelHistogram.pool`, ``pooled=True``), or
+    use a fixed level, where tiles do not hold both."""
+    fallback = _check_level(fallback, "fallback")
+    cut = otsu_threshold(hist, fallback=(fallback + 1) / 256.0)
+    return (cut * 256.0).round().to(torch.int64) - 1
+
+
+def level_mask(levels: torch.Tensor, thresholds: Any) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mask, counts)``: (N, H, W) uint8, tile i set where ``level > thresholds[i]`` (cv2's ``THRESH_BINARY``, CLAM's ``sthresh``), and (N,) int64 set
+    pixels per tile, on the device.  ``thresholds``: an int (every tile), or an (N,) integer tensor on either device; a negative threshold
+    sets the whole tile, one >= 255 clears it.  The kernel reads the thresholds from device memory: nothing here synchronises, and a
+    captured call replayed after new thresholds were written into a device tensor uses them.  One launch and the clear of the counts
+    (include/stainx_hip.h: sx_level_mask_tiles).  ``levels`` as for :func:`median_filter`."""
+    _check_levels(levels, "level_mask")
+    n = levels.shape[0]
+    if isinstance(thresholds, torch.Tensor):
+        if thresholds.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) or tuple(thresholds.shape) != (n,):
+            raise ValueError(f"thresholds must be an int or an integer tensor of shape ({n},), got {thresholds.dtype} {tuple(thresholds.shape)}")
+        cuts = thresholds.to(torch.int64).clamp(-1, 255).to(device=levels.device, dtype=torch.int32).contiguous()      # (widened first: -1 is no uint8)
+    elif isinstance(thresholds, int) and not isinstance(thresholds, bool):
+        cuts = torch.full((n,), min(max(thresholds, -1), 255), dtype=torch.int32, device=levels.device)
+    else:
+        raise ValueError(f"thresholds must be an int or an integer tensor of shape ({n},), got {type(thresholds).__name__}")
+    from stainx_amd.backends.torch_hip_backend import level_mask_native
+
+    return level_mask_native(levels, cuts)
+
+
+def saturation_mask(images: torch.Tensor, *, threshold: int | None = None, median_size: int = 7, pooled: bool = False, channel_axis: int = 1,
+                    fallback: int = DEFAULT_SATURATION_FALLBACK, open_radius: int = 0, close_radius: int = 0, element: str = "disk", min_object_area: int = 0,
+                    min_hole_area: int = 0, connectivity: int = 8) -> SaturationDetection:
+    """Tissue detection on the saturation channel (the front half of CLAM's ``segmentTissue``), in this order: :func:`saturation_map`; the
+    :func:`median_filter` of ``median_size`` (0 skips it); the threshold; :func:`level_mask`; then :func:`refine_mask` with the radii and areas
+    given, when any is non-zero.  ``threshold=None``: Otsu by :func:`level_histogram` and :func:`otsu_level`, per tile or (``pooled=True``) one for
+    the batch, repeated -- the one synchronisation point.  ``threshold`` an integer in 0..254: that level for every tile; this path does
+    not synchronise and can be captured in a graph.  CLAM's defaults are ``saturation_mask(x, threshold=8, median_size=7, close_radius=4,
+    element="square")`` followed by the area filters.
+
+    Known hazards.  Near-black pixels have an unstable, often high, saturation -- (10, 10, 12) has S = 43 -- so BLACK MARKER PASSES this
+    rule, as it does in CLAM: AND the result with :func:`tissue_mask` where that matters.  COLOURED PEN is saturated and passes too.  And
+    with ``threshold=None`` Otsu ALWAYS splits (:func:`otsu_level`): per-tile thresholds are for tiles that hold both tissue and glass."""
+    last = _check_images(images, channel_axis, "saturation_mask")
+    if threshold is not None:
+        _check_level(threshold, "threshold")
+    if isinstance(median_size, bool) or not isinstance(median_size, int) or median_size != 0:
+        _check_median_size(median_size, "median_size")
+    fallback = _check_level(fallback, "fallback")
+    _check_radius(open_radius, "open_radius", 0)
+    _check_radius(close_radius, "close_radius", 0)
+    _check_element(element)
+    _check_area(min_object_area, "min_object_area", 0)
+    _check_area(min_hole_area, "min_hole_area", 0)
+    _check_connectivity(connectivity)
+    levels = saturation_map(images, channel_axis=channel_axis)
+    if median_size:
+        levels = median_filter(levels, median_size)
+    n = levels.shape[0]
+    if threshold is None:
+        thresholds = otsu_level(level_histogram(levels, pooled=pooled), fallback=fallback)
+        if pooled:
+            thresholds = thresholds.repeat(n)
+        mask, counts = level_mask(levels, thresholds)
+    else:
+        thresholds = torch.full((n,), threshold, dtype=torch.int64)
+        mask, counts = level_mask(levels, threshold)
+    if open_radius or close_radius or min_object_area or min_hole_area:
+        mask, counts = refine_mask(mask, open_radius=open_radius, close_radius=close_radius, element=element, min_object_area=min_object_area,
+                                   min_hole_area=min_hole_area, connectivity=connectivity)
+    return SaturationDetection(mask, counts, thresholds)
