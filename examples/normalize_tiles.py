@@ -4,7 +4,7 @@ the sampled `precision="fast"` mode, how a batch is split over GPUs (one process
 `transform`), the slide-level use: one source estimate, applied to batch after batch, per-tile statistics for Reinhard and
 histogram matching on a batch of tiles from different slides, their tissue masks for tiles with slide background, and slide-level
 histogram matching (histograms added up over batches, one table, one launch per batch), and a tissue mask detected on the device and
-cleaned by area (small objects go, small holes are filled).  Run on a ROCm GPU:  python examples/normalize_tiles.py
+cleaned by area (small objects go, small holes are filled), and Vahadane's stain estimate behind the same surface.  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -17,7 +17,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from stainx_amd import (HistogramMatching, HistogramStatistics, Macenko, Reinhard, StainNormalizerTransform, mask_components, otsu_mask, remove_small_holes,  # noqa: E402
-                        remove_small_objects, synth, tissue_mask)
+                        remove_small_objects, synth, tissue_mask, Vahadane)
 from stainx_amd import distributed as sxd  # noqa: E402
 from stainx_amd.backends.torch_hip_backend import MacenkoHIP  # noqa: E402
 
@@ -131,6 +131,17 @@ def main() -> None:
     largest = found.areas.flatten(1).max(dim=1).values               # e.g. the largest tissue object of every tile, without leaving the device
     out = Macenko(device=dev).fit(reference.to(dev)).transform(edge, mask=det.mask)
     print(f"[rank {rank}] detected tissue mask        {tuple(out.shape)}  objects per tile {found.counts.tolist()}  largest {largest.tolist()}  tissue pixels {det.counts.tolist()}")
+    # 11. Vahadane's estimator (sparse NMF of the optical density) behind Macenko's surface: a fixed number of rounds, so the call is
+    #     deterministic and never synchronises; the estimate runs over the luminosity mask by default and glass is copied through.
+    #     Its StainEstimate goes wherever Macenko's goes; max_concentrations() completes a basis that was estimated elsewhere.
+    vahadane = Vahadane(device=dev, regularizer=0.1, iterations=30).fit(reference.to(dev))
+    out = vahadane.transform(edge)
+    slide = vahadane.estimate(edge, pooled=True)                     # one basis for the batch: apply() is one launch per batch afterwards
+    out_slide = vahadane.apply(edge, slide)
+    max_c = vahadane.max_concentrations(edge, slide.stain_matrices, pooled=True)
+    assert torch.equal(max_c, slide.max_concentrations)
+    print(f"[rank {rank}] Vahadane                    {tuple(out.shape)} + {tuple(out_slide.shape)} {out.dtype}  H = {[round(v, 3) for v in slide.stain_matrices[0, :, 0].tolist()]}  "
+          f"E = {[round(v, 3) for v in slide.stain_matrices[0, :, 1].tolist()]}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

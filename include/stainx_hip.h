@@ -801,6 +801,51 @@ int sx_hm_apply_tables_masked(const void* images_dev, void* out_dev, int dtype, 
                               int channels_last, const float* lut_dev, int64_t n_sources, const uint8_t* mask_dev,
                               double luminosity_threshold, void* stream);
 
+/* ---------------------------------------------------------------- Vahadane -----------------------
+ * The other H&E estimator (Vahadane et al. 2016; staintools, tiatoolbox): sparse non-negative matrix factorisation of the optical
+ * density with two atoms.  An extension: the reference has no counterpart.  What the calls write is a stain basis and its maximal
+ * concentrations in sx_macenko_estimate's layout, so sx_macenko_apply(_masked) and sx_macenko_separate_apply(_masked) take them as they are.
+ *
+ * A GROUP is a tile, or with pooled != 0 the whole batch (rows = n_tiles, or 1).  S is the group's masked-in pixels (mask_dev: one
+ * byte per pixel, (N, H*W), non-zero = in, sx_tissue_mask's layout; NULL: every pixel).  V (3,|S|) is the optical density of the
+ * transform, -log((level + 1) / 240).  Values under masked-out pixels never matter, NaN included; a non-finite masked-in pixel makes
+ * the group's result undefined.  Images are planar (N,3,H,W) of any of the five element types.
+ *
+ * sx_vahadane_estimate minimises 0.5 |V - W H|^2 + lambda |H|_1 over W (3,2) >= 0 with unit columns and H (2,|S|) >= 0 by exactly
+ * `iterations` rounds (1..1000, no early exit: nothing synchronises, the call can be captured, two calls give the same bits):
+ *   coding step      per pixel, float32, from the float32 rounding of W: with g = w1.w2, b = W^T v - lambda, d = 1 - g^2 the
+ *                    candidate h = ((b1 - g b2)/d, (b2 - g b1)/d) if both components are > 0 (and d > 1e-6); else (b1, 0) if b1 > 0
+ *                    and b2 - g b1 <= 0; else (0, b2) if b2 > 0; else (0, 0) -- the exact two-variable non-negative lasso
+ *   dictionary step  per group, fp64, from A = H H^T and B = V H^T: for j = 0, 1: u = W[:,j] + (B[:,j] - W A[:,j]) / A[j,j],
+ *                    u = max(u, 0), W[:,j] = u / |u|; an atom with A[j,j] == 0 or |u| == 0 keeps its column
+ * and then, if W[0,0] < W[0,1], swaps the columns (haematoxylin: the larger red optical density) and rounds to float32.
+ *   init_he_dev    n_init x 6 floats, (3,2) row-major, columns normalised on the device; n_init is 1 or rows
+ *   lambda         >= 0, finite (staintools / tiatoolbox: 0.1)
+ *   he_out_dev     rows x 6 floats; a group without a masked-in pixel gets NaN
+ *   max_c_out_dev  rows x 2 floats, or NULL to skip them: what sx_stain_max_concentrations returns for he_out_dev
+ *   pixels_out_dev rows uint64, or NULL: |S|, exact
+ * Two launches per round (a streaming pass with fixed-order reductions, no floating-point atomics; one workgroup per group).  A tile's
+ * row has the same bits alone or inside a batch, and a pooled estimate of a one-tile batch has the bits of that tile's row.
+ *
+ * sx_stain_max_concentrations: for GIVEN bases he_dev (n_sources x 6 floats; n_sources is 1 or rows) the two nearest-rank 99th
+ * percentiles, k = 1 + round(0.01 * 99 * (|S| - 1)) half to even, over S of the float32 concentrations that
+ * sx_macenko_separate_apply(_masked) writes in own-basis mode for that basis -- bit for bit.  An exact radix selection: a memset,
+ * three streaming passes with integer histograms and three one-workgroup steps.  A group without a masked-in pixel gets NaN.
+ *
+ * flags: SX_MACENKO_CLASSIC (a no-op) only; anything else, SX_MACENKO_CHANNELS_LAST included, is SX_ERR_BAD_ARG.  Argument errors
+ * (a NULL required pointer; n, h, w not positive or overflowing; iterations outside 1..1000; lambda negative or not finite; n_init /
+ * n_sources other than 1 or rows: SX_ERR_BAD_ARG; an unknown element type: SX_ERR_DTYPE; a workspace smaller than
+ * sx_vahadane_workspace_bytes() or misaligned: SX_ERR_WORKSPACE) are returned before anything is enqueued. */
+size_t sx_vahadane_workspace_bytes(int dtype, int64_t n_tiles, int64_t height, int64_t width);
+int sx_vahadane_estimate(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, const uint8_t* mask_dev,
+                         int pooled, const float* init_he_dev, int64_t n_init, double lambda, int iterations, float* he_out_dev,
+                         float* max_c_out_dev, unsigned long long* pixels_out_dev, unsigned flags, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+int sx_stain_max_concentrations(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                                const uint8_t* mask_dev, int pooled, const float* he_dev, int64_t n_sources, float* max_c_out_dev,
+                                unsigned long long* pixels_out_dev, unsigned flags, void* workspace_dev, size_t workspace_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

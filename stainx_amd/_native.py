@@ -150,6 +150,10 @@ SIGNATURES = {
     "sx_hm_tables": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sx_hm_apply_tables": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp]),
     "sx_hm_apply_tables_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _c.c_double, _vp]),
+    # Vahadane stain estimation (sparse NMF, two atoms) and the percentile concentrations of a given basis; `mask_dev` may be None
+    "sx_vahadane_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
+    "sx_vahadane_estimate": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _c.c_double, _int, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
+    "sx_stain_max_concentrations": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _vp, _vp, _uint, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1094,6 +1094,70 @@ class MacenkoHIP(TorchHIPBackendBase):
                 "n_candidates": raw[:, 19:23].long(), "cov": raw[:, 23:32].reshape(-1, 3, 3), "stamps_us": raw[:, 32:48]}
 
 
+class VahadaneHIP(MacenkoHIP):
+    """Vahadane's estimate (sparse NMF of the optical density with two atoms; include/stainx_hip.h: sx_vahadane_estimate) and the
+    percentile concentrations of a given basis (sx_stain_max_concentrations).  Everything downstream of an estimate -- ``apply*``,
+    ``separate_apply*`` -- is the Macenko engine's."""
+
+    def _planar(self, images: torch.Tensor, what: str) -> torch.Tensor:
+        images = images.to(self.device)
+        self._check_images(images, what)
+        return images.contiguous()
+
+    def _vahadane_workspace(self, code: int, n: int, h: int, w: int) -> torch.Tensor:
+        return self._scratch.get(self._lib.sx_vahadane_workspace_bytes(code, n, h, w), self.device)
+
+    def vahadane_estimate(self, images: torch.Tensor, init: torch.Tensor, *, regularizer: float = 0.1, iterations: int = 30, pooled: bool = False, masked: bool = False,
+                          mask: torch.Tensor | None = None, luminosity_threshold: float = 0.8, max_conc: bool = True) -> dict[str, torch.Tensor | None]:
+        """``he`` (rows, 3, 2), ``max_c`` (rows, 2) or None, ``pixels`` (rows,) int64 -- the exact |S| --; rows = N, or 1 with ``pooled``.
+        ``init``: (1, 3, 2) or (rows, 3, 2).  ``masked``: over ``mask`` (N, H, W), or with ``mask=None`` over the luminosity rule's
+        mask (an ``sx_tissue_mask`` launch in front).  A group without a masked-in pixel has NaN rows and 0 pixels."""
+        images = self._planar(images, "estimate")
+        n, _, h, w = images.shape
+        rows = 1 if pooled else n
+        init = self._f32(init).reshape(-1, 3, 2)
+        if init.shape[0] not in (1, rows):
+            raise ValueError(f"init must hold 1 or {rows} stain matrices, got {init.shape[0]}")
+        out = {
+            "he": torch.empty((rows, 3, 2), dtype=torch.float32, device=self.device),
+            "max_c": torch.empty((rows, 2), dtype=torch.float32, device=self.device) if max_conc else None,
+            "pixels": torch.empty((rows,), dtype=torch.int64, device=self.device),
+        }
+        if n == 0 or h * w == 0:
+            return out
+        code = _dtype_code(images)
+        with _native.on_device(self.device):
+            mask = self._mask_for(images, mask, luminosity_threshold) if masked else None
+            ws = self._vahadane_workspace(code, n, h, w)
+            rc = self._lib.sx_vahadane_estimate(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), init.data_ptr(), init.shape[0],
+                                                float(regularizer), int(iterations), out["he"].data_ptr(), out["max_c"].data_ptr() if max_conc else None,
+                                                out["pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_vahadane_estimate", self._lib)
+        return out
+
+    def max_concentrations(self, images: torch.Tensor, stain_matrices: torch.Tensor, *, pooled: bool = False, masked: bool = False, mask: torch.Tensor | None = None,
+                           luminosity_threshold: float = 0.8) -> dict[str, torch.Tensor]:
+        """The nearest-rank 99th percentiles of the concentrations of GIVEN bases (1 or rows) over each group's masked-in pixels:
+        ``max_c`` (rows, 2) float32 and ``pixels`` (rows,) int64."""
+        images = self._planar(images, "max_concentrations")
+        n, _, h, w = images.shape
+        rows = 1 if pooled else n
+        he = self._f32(stain_matrices).reshape(-1, 3, 2)
+        if he.shape[0] not in (1, rows):
+            raise ValueError(f"stain_matrices must hold 1 or {rows} stain matrices, got {he.shape[0]}")
+        out = {"max_c": torch.empty((rows, 2), dtype=torch.float32, device=self.device), "pixels": torch.empty((rows,), dtype=torch.int64, device=self.device)}
+        if n == 0 or h * w == 0:
+            return out
+        code = _dtype_code(images)
+        with _native.on_device(self.device):
+            mask = self._mask_for(images, mask, luminosity_threshold) if masked else None
+            ws = self._vahadane_workspace(code, n, h, w)
+            rc = self._lib.sx_stain_max_concentrations(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), he.data_ptr(), he.shape[0],
+                                                       out["max_c"].data_ptr(), out["pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+            _native.check(rc, "sx_stain_max_concentrations", self._lib)
+        return out
+
+
 class DeconvHIP(TorchHIPBackendBase):
     """Three-stain colour deconvolution with a GIVEN (3, 3) basis (include/stainx_hip.h: sx_deconv_*): one kernel launch per call, no
     estimate, no workspace, no host synchronisation.  Bases, factors and masks are read on the device: a captured call replayed after

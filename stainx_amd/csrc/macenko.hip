@@ -5495,3 +5495,6 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 
 // Three-stain colour deconvolution with a given basis (sx_deconv_*): kernels, launchers and entry points, on the helpers above.
 #include "deconv.hpp"
+
+// Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
+#include "vahadane.hpp"
