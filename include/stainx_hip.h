@@ -846,6 +846,51 @@ int sx_stain_max_concentrations(const void* images_dev, int dtype, int64_t n_til
                                 unsigned long long* pixels_out_dev, unsigned flags, void* workspace_dev, size_t workspace_bytes,
                                 void* stream);
 
+/* ---------------------------------------------------------------- luminosity standardisation -----
+ * staintools' LuminosityStandardizer.standardize, exact and on the device: take a percentile of the lightness L*, scale L* so that the
+ * percentile becomes white, clip at white, leave a* and b* alone.  An extension: the reference has no counterpart.  Images are planar
+ * (N,3,H,W) of any of the five element types.
+ *
+ * Y of a pixel is the float32 luminance sx_tissue_mask, sx_tissue_mask_tiles and sx_luminosity_histogram compare (the colour
+ * conversion's middle row on the linear-light values; a double is rounded to float first).  L* is monotone in Y, so the percentile of
+ * L* is L* of the percentile of Y and the selection runs on Y.
+ *
+ * sx_luminosity_percentile: a ROW is a tile, or with pooled != 0 the whole batch (rows = n_tiles, or 1).  S is the row's masked-in
+ * pixels (mask_dev: one byte per pixel, (N, H*W), non-zero = in, sx_tissue_mask's layout; NULL: every pixel) whose Y is not NaN.  The
+ * result is the nearest rank with the rule of sx_stain_max_concentrations, k = 1 + rint(0.01 * percentile * (|S| - 1)), half to even,
+ * in doubles: the k-th smallest Y of S, a float32 that occurs in the data.  (Not numpy's method="nearest", and not staintools' linear
+ * interpolation over 8-bit LAB.)
+ *   percentile         in (0, 100], finite
+ *   luminance_out_dev  rows floats; NaN for an empty S
+ *   pixels_out_dev     rows uint64, or NULL: |S|, exact
+ * An exact radix selection: a memset, three streaming passes with integer histograms and three one-workgroup steps on `stream`; no
+ * floating-point atomics, no host synchronisation, the call can be captured.  A tile's row has the same bits alone or inside a batch,
+ * and a pooled one-tile batch gives the bits of that tile's row.
+ *
+ * sx_luminosity_apply: ONE launch on `stream`, no workspace.  luminance_dev: n_sources floats in DEVICE memory read by the kernel
+ * (n_sources is 1: row 0 for every tile, or n_tiles: row `tile`).  From the row's Y_p, in fp64: f_p = Y_p > 0.008856 ? cbrt(Y_p) :
+ * 7.787 Y_p + 16/116, L_p = 116 f_p - 16, g = 100 / L_p.  Per pixel, in float32, with (f_x, f_y, f_z) of the LAB conversion:
+ * f_y' = min(g f_y + (16/116)(1 - g), 1), f_x' = f_y' + (f_x - f_y), f_z' = f_y' - (f_y - f_z), and back to sRGB as
+ * sx_reinhard_apply_stats goes: L*' = min(100 L* / L_p, 100), a* and b* unchanged, nothing quantised on the way.  A row that is NaN or
+ * gives L_p <= 0 (a black tile) copies its tiles through bit for bit.  What a NaN pixel becomes is unspecified.  Not in place.
+ *
+ * Argument errors (a NULL required pointer; n, h, w not positive or overflowing; a percentile outside (0, 100] or not finite;
+ * n_sources other than 1 or n_tiles; out_dev == images_dev: SX_ERR_BAD_ARG; an unknown element type: SX_ERR_DTYPE; a workspace
+ * smaller than sx_luminosity_workspace_bytes() or misaligned: SX_ERR_WORKSPACE) are returned before anything is enqueued. */
+size_t sx_luminosity_workspace_bytes(int dtype, int64_t n_tiles, int64_t height, int64_t width);
+int sx_luminosity_percentile(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, const uint8_t* mask_dev,
+                             int pooled, double percentile, float* luminance_out_dev, unsigned long long* pixels_out_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
+int sx_luminosity_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                        const float* luminance_dev, int64_t n_sources, void* stream);
+#ifdef SX_DIAG
+/* Diagnostic build: sx_luminosity_percentile with one LDS add per pixel instead of one per run of equal bins -- same result; what the run
+ * counting is measured against on glass. */
+int sx_luminosity_percentile_plain(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                                   const uint8_t* mask_dev, int pooled, double percentile, float* luminance_out_dev,
+                                   unsigned long long* pixels_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

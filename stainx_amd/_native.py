@@ -154,6 +154,10 @@ SIGNATURES = {
     "sx_vahadane_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_vahadane_estimate": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _c.c_double, _int, _vp, _vp, _vp, _uint, _vp, _sz, _vp]),
     "sx_stain_max_concentrations": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _vp, _vp, _uint, _vp, _sz, _vp]),
+    # luminosity standardisation: the exact percentile of the luminance (`mask_dev` may be None), the one-launch L* map
+    "sx_luminosity_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
+    "sx_luminosity_percentile": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "sx_luminosity_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp]),
 }
 
 _lib = None
@@ -165,6 +169,7 @@ _diag_lib = None
 DIAG_SIGNATURES = {
     "sx_hm_workspace_parity_offset": (_sz, []),
     "sx_debug_hm_stamp_offset": (_sz, []),
+    "sx_luminosity_percentile_plain": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _c.c_double, _vp, _vp, _vp, _sz, _vp]),      # one LDS add per pixel (no runs)
 }
 
 

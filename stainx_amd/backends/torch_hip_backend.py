@@ -1158,6 +1158,46 @@ class VahadaneHIP(MacenkoHIP):
         return out
 
 
+class LuminosityHIP(TorchHIPBackendBase):
+    """Luminosity standardisation (include/stainx_hip.h: sx_luminosity_percentile, sx_luminosity_apply): the exact nearest-rank percentile
+    of the luminance per tile or over the batch, and the one-launch map that makes it white.  Nothing synchronises; the percentile stays
+    on the device and the apply pass reads it there."""
+
+    def percentile(self, images: torch.Tensor, percentile: float, *, pooled: bool = False, mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(luminance, pixels)``: (rows,) float32 -- NaN for an empty set -- and (rows,) int64, rows = N or 1 with ``pooled``.  ``mask``:
+        (N, H, W) uint8 / bool, which pixels enter the set."""
+        images = images.to(self.device).contiguous()
+        n, _, h, w = images.shape
+        rows = 1 if pooled else n
+        luminance = torch.full((rows,), float("nan"), dtype=torch.float32, device=self.device)
+        pixels = torch.zeros((rows,), dtype=torch.int64, device=self.device)
+        if n == 0 or h * w == 0:
+            return luminance, pixels
+        code = _dtype_code(images)
+        mask = _mask_bytes(mask, self.device)
+        with _native.on_device(self.device):
+            ws = self._scratch.get(self._lib.sx_luminosity_workspace_bytes(code, n, h, w), self.device)
+            rc = self._lib.sx_luminosity_percentile(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), float(percentile),
+                                                    luminance.data_ptr(), pixels.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+        _native.check(rc, "sx_luminosity_percentile", self._lib)
+        return luminance, pixels
+
+    def apply(self, images: torch.Tensor, luminance: torch.Tensor) -> torch.Tensor:
+        """The map with GIVEN percentiles: ``luminance`` holds one row, or one per tile."""
+        images = images.to(self.device).contiguous()
+        n, _, h, w = images.shape
+        luminance = self._f32(luminance).reshape(-1)
+        if luminance.shape[0] not in (1, n):
+            raise ValueError(f"luminance must hold 1 or {n} rows, got {luminance.shape[0]}")
+        out = torch.empty_like(images)
+        if n == 0 or h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            rc = self._lib.sx_luminosity_apply(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, luminance.data_ptr(), luminance.shape[0], _native.stream_ptr(self.device))
+        _native.check(rc, "sx_luminosity_apply", self._lib)
+        return out
+
+
 class DeconvHIP(TorchHIPBackendBase):
     """Three-stain colour deconvolution with a GIVEN (3, 3) basis (include/stainx_hip.h: sx_deconv_*): one kernel launch per call, no
     estimate, no workspace, no host synchronisation.  Bases, factors and masks are read on the device: a captured call replayed after

@@ -1038,3 +1038,6 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
 
 // ---- saturation-channel tissue detection: saturation maps, the median filter, level histograms and level thresholds ------------------------
 #include "saturation.hpp"
+
+// ---- luminosity standardisation: the exact percentile of the luminance, the one-launch L* map ------------------------------------------------
+#include "luminosity.hpp"

@@ -20,26 +20,25 @@
 // memory -- each followed by a one-workgroup step that finds the bin of the wanted rank.  Integer sums: exact and deterministic.
 #pragma once
 
+#include "radix_select.hpp"
+
 namespace sx {
 namespace vahadane {
 
 using namespace sx::macenko;
+using radix::kBinsAll;      // (11 / 11 / 10 bits, 5120 counts per (group, stain): radix_select.hpp, shared with the luminosity percentile)
+using radix::kBits0;
+using radix::kBits1;
+using radix::kBits2;
+using radix::PassBins;
+using radix::SelectState;
 
 constexpr int kVChunk = 16384;        // pixels per work item: a multiple of kStreamThreads * 16 (the widest pack)
 constexpr int kVals = 10;             // A00 A01 A11  B00 B01 B10 B11 B20 B21  count
 constexpr int kStateDoubles = 8;      // W (3,2) row-major in fp64, two spare
 constexpr int kUpdateThreads = 256;
 constexpr int kUpdateRows = 16;       // the update step adds partials m, m + 16, ... per row, then the sixteen rows in order
-constexpr int kBits0 = 11, kBits1 = 11, kBits2 = 10;
-constexpr int kBinsAll = (1 << kBits0) + (1 << kBits1) + (1 << kBits2);      // 5120 counts per (group, stain)
 static_assert(kVChunk % (kStreamThreads * 16) == 0, "a work item is whole sweeps of every pack width");
-
-struct SelectState {      // per (group, stain)
-    unsigned long long rank;      // the wanted rank (1-based) among the keys that share `prefix`
-    unsigned long long count;     // |S|
-    uint32_t prefix;              // the key's leading bits found so far
-    uint32_t pad;
-};
 
 struct Layout {
     size_t state, partials, hist, select, total;
@@ -260,11 +259,6 @@ struct MaxcArgs {
     SelectState* select;              // rows x 2
     int64_t pixels, n_tiles;
     int blocks, pooled, per_row;
-};
-template <int kPass> struct PassBins {
-    static constexpr int bits = kPass == 0 ? kBits0 : (kPass == 1 ? kBits1 : kBits2);
-    static constexpr int offset = kPass == 0 ? 0 : (kPass == 1 ? (1 << kBits0) : (1 << kBits0) + (1 << kBits1));
-    static constexpr int below = kPass == 0 ? kBits1 + kBits2 : (kPass == 1 ? kBits2 : 0);      // key bits below this pass's digit
 };
 
 template <typename T, bool kVec, bool kMask, int kPass>
