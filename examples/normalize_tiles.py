@@ -4,7 +4,8 @@ the sampled `precision="fast"` mode, how a batch is split over GPUs (one process
 `transform`), the slide-level use: one source estimate, applied to batch after batch, per-tile statistics for Reinhard and
 histogram matching on a batch of tiles from different slides, their tissue masks for tiles with slide background, and slide-level
 histogram matching (histograms added up over batches, one table, one launch per batch), and a tissue mask detected on the device and
-cleaned by area (small objects go, small holes are filled), and Vahadane's stain estimate behind the same surface.  Run on a ROCm GPU:  python examples/normalize_tiles.py
+cleaned by area (small objects go, small holes are filled), and Vahadane's stain estimate behind the same surface, and a Macenko estimate on
+tissue pixels sampled from several batches.  Run on a ROCm GPU:  python examples/normalize_tiles.py
 Under torchrun (`python -m torch.distributed.run --nproc-per-node N examples/normalize_tiles.py`) every rank works on
 its own slice of the batch and the last section pools a Macenko fit over all ranks."""
 from __future__ import annotations
@@ -16,8 +17,8 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from stainx_amd import (HistogramMatching, HistogramStatistics, Macenko, Reinhard, StainNormalizerTransform, mask_components, otsu_mask, remove_small_holes,  # noqa: E402
-                        remove_small_objects, synth, tissue_mask, Vahadane)
+from stainx_amd import (HistogramMatching, HistogramStatistics, Macenko, PixelSample, Reinhard, StainNormalizerTransform, mask_components, otsu_mask,  # noqa: E402
+                        remove_small_holes, remove_small_objects, sample_pixels, synth, tissue_mask, Vahadane)
 from stainx_amd import distributed as sxd  # noqa: E402
 from stainx_amd.backends.torch_hip_backend import MacenkoHIP  # noqa: E402
 
@@ -142,6 +143,18 @@ def main() -> None:
     assert torch.equal(max_c, slide.max_concentrations)
     print(f"[rank {rank}] Vahadane                    {tuple(out.shape)} + {tuple(out_slide.shape)} {out.dtype}  H = {[round(v, 3) for v in slide.stain_matrices[0, :, 0].tolist()]}  "
           f"E = {[round(v, 3) for v in slide.stain_matrices[0, :, 1].tolist()]}")
+    # 12. a slide-level MACENKO estimate over several batches.  Percentiles do not add up the way histograms do, so every batch gives a
+    #     bounded sample of its REAL tissue pixels -- an exact integer stride over the masked-in pixels of the batch, copied bit for bit
+    #     into a fixed-shape tile with a validity mask --, the samples are concatenated, and ONE pooled masked estimate reads them; then
+    #     `apply` per batch.  The sampler never synchronises (here only Otsu's 256 counts return to the host), and a thumbnail's mixed
+    #     edge pixels never enter the estimate.
+    mk = Macenko(device=dev).fit(reference.to(dev))
+    samples = [sample_pixels(b, (64, 64), mask=otsu_mask(b, pooled=True).mask, pooled=True) for b in batches]
+    sample = PixelSample.cat(*samples)                               # pixels (batches, 3, 64, 64), valid (batches, 64, 64): a small batch with a mask
+    slide = mk.estimate(sample.pixels, pooled=True, mask=sample.valid)
+    out = torch.cat([mk.apply(b, slide) for b in batches])
+    print(f"[rank {rank}] Macenko on sampled tissue   {tuple(out.shape)} in {len(batches)} batches  sampled {sample.taken.tolist()} of {sample.population.tolist()} tissue pixels  "
+          f"maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

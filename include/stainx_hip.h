@@ -891,6 +891,42 @@ int sx_luminosity_percentile_plain(const void* images_dev, int dtype, int64_t n_
                                    unsigned long long* pixels_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 #endif
 
+/* ---------------------------------------------------------------- tissue pixel sampling -----------
+ * HistomicsTK's sample_pixels on the device, exact: from a batch and a mask, a fixed-shape tile of at most K masked-in pixels per
+ * GROUP -- a tile, or with pooled != 0 the whole batch (groups = n_tiles, or 1) -- chosen by an integer rule and copied bit for bit, plus
+ * a validity mask.  The result is an ordinary small planar tile with an explicit mask: every masked estimate above takes it as it is,
+ * and samples of any number of batches, concatenated along the group axis, make one bounded pooled estimate of a slide.  An extension:
+ * the reference has no counterpart.
+ *
+ * The rule.  A group's population is its masked-in pixels (mask_dev: one byte per pixel, (N, H*W), non-zero = in, the layout every
+ * masked entry point reads; NULL: every pixel), ranked 0 .. n-1 in raster order, pooled: tile after tile in batch order.  K = sample_size;
+ * the slots 0 .. K-1 are the pixels of the output tile in raster order.
+ *   n <= K   slot r holds the pixel of rank r, valid = 1; the slots n .. K-1 hold zero bytes, valid = 0; offset is not used.
+ *   n >  K   slot j holds the pixel of rank (j * n + o) div K with o = offset mod n, in 64-bit integers, valid = 1: the ranks are
+ *            strictly increasing in j and the largest is below n.
+ * A pixel is moved as its three values in the element type of the images -- no conversion: NaN payloads and -0.0 survive.
+ *   images_dev          (N,3,H,W), or (N,H,W,3) with channels_last != 0, any of the five element types
+ *   sample_size         1 .. 2^24
+ *   offset              >= 0; another offset takes another sample of a group with n > K
+ *   pixels_out_dev      groups x 3 x K elements of the images' type: ALWAYS planar, slot j of channel c of group g at (g * 3 + c) * K + j
+ *   valid_out_dev       groups x K bytes, 1 / 0
+ *   taken_out_dev       groups int32: min(n, K)
+ *   population_out_dev  groups int64: n
+ *   workspace_dev       sx_sample_workspace_bytes() bytes, 8-byte aligned; any contents
+ * Three launches on `stream` -- chunk counts read from the mask with 16-byte loads, one workgroup per group for the prefix over the
+ * chunks, the copy -- with every byte of the four outputs written by exactly one thread: no memset, no atomics, no workgroup that waits
+ * for another, no host synchronisation; the call can be captured.  A group's row has the same bits alone or inside a batch.
+ *
+ * Errors, returned before anything is enqueued.  SX_ERR_BAD_ARG: a NULL required pointer (mask_dev may be NULL); n, h, w not positive
+ * (a batch of zero tiles is the caller's to skip, as everywhere above); sample_size outside 1 .. 2^24; offset < 0; a group of 2^31
+ * pixels or more; a workspace that is NULL, misaligned or smaller than the size query says.  SX_ERR_DTYPE: an unknown element type.
+ * The size query returns 0 for sizes the call refuses. */
+size_t sx_sample_workspace_bytes(int64_t n_tiles, int64_t height, int64_t width);
+int sx_sample_pixels(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                     const uint8_t* mask_dev, int pooled, int64_t sample_size, int64_t offset,
+                     void* pixels_out_dev, uint8_t* valid_out_dev, int32_t* taken_out_dev, int64_t* population_out_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ MORPH_ELEMENTS = {"square": 0, "disk": 1}
 MORPH_MAX_RADIUS = 31
 CONNECTIVITIES = (4, 8)      # sx_mask_components, sx_mask_area_filter
 MEDIAN_MAX_SIZE = 15         # sx_median_filter_u8: SX_MEDIAN_MAX_SIZE
+MAX_SAMPLE_SIZE = 1 << 24    # sx_sample_pixels: sample_size
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -158,6 +159,9 @@ SIGNATURES = {
     "sx_luminosity_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_luminosity_percentile": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
     "sx_luminosity_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp]),
+    # tissue pixel sampling: a fixed-shape tile of at most K masked-in pixels per tile or per batch, copied bit for bit; `mask_dev` may be None
+    "sx_sample_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "sx_sample_pixels": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

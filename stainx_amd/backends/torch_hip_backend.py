@@ -225,6 +225,35 @@ def level_mask_native(levels: torch.Tensor, thresholds: torch.Tensor) -> tuple[t
     return mask, counts
 
 
+def sample_pixels_native(images: torch.Tensor, mask: torch.Tensor | None, height: int, width: int, pooled: bool, offset: int,
+                         channels_last: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``stainx_amd.sample_pixels`` behind its checks (``mask``: an explicit mask or None, every pixel): (G, 3, height, width) pixels of the images'
+    type, (G, height, width) uint8 validity, (G,) int32 taken and (G,) int64 population, G = 1 pooled, else N (include/stainx_hip.h:
+    sx_sample_pixels; the workspace comes from its size query).  Nothing synchronises."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images = images.to(base.device).contiguous()
+    n, h, w = _image_sizes(images, channels_last)
+    groups = 1 if pooled else n
+    if n == 0 or h * w == 0:      # nothing to rank: empty groups (a pooled call keeps its one row)
+        return (torch.zeros((groups, 3, height, width), dtype=images.dtype, device=base.device), torch.zeros((groups, height, width), dtype=torch.uint8, device=base.device),
+                torch.zeros((groups,), dtype=torch.int32, device=base.device), torch.zeros((groups,), dtype=torch.int64, device=base.device))
+    code = _dtype_code(images)
+    src = _mask_bytes(mask, base.device)
+    pixels = torch.empty((groups, 3, height, width), dtype=images.dtype, device=base.device)
+    valid = torch.empty((groups, height, width), dtype=torch.uint8, device=base.device)
+    taken = torch.empty((groups,), dtype=torch.int32, device=base.device)
+    population = torch.empty((groups,), dtype=torch.int64, device=base.device)
+    nbytes = int(base._lib.sx_sample_workspace_bytes(n, h, w))
+    if nbytes == 0:
+        raise ValueError(f"sample_pixels: a tile of {h} x {w} pixels is too large for one call (a group holds fewer than 2^31 pixels)")
+    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=base.device)
+    with _native.on_device(base.device):
+        rc = base._lib.sx_sample_pixels(images.data_ptr(), code, n, h, w, int(channels_last), None if src is None else src.data_ptr(), int(pooled), height * width, int(offset),
+                                        pixels.data_ptr(), valid.data_ptr(), taken.data_ptr(), population.data_ptr(), workspace.data_ptr(), nbytes, _native.stream_ptr(base.device))
+    _native.check(rc, "sx_sample_pixels")
+    return pixels, valid, taken, population
+
+
 class MacenkoHIP(TorchHIPBackendBase):
     """Macenko transform / fit on the GPU (numerics of MacenkoTorch, torch_backend.py:358-560)."""
 

@@ -26,3 +26,6 @@ int check_launch(const char* what) {
 
 extern "C" int sx_version(void) { return SX_ABI_VERSION; }
 extern "C" const char* sx_last_error_string(void) { return sx::err_buf(); }
+
+// Tissue pixel sampling: chunk counts, a prefix per group, the copy of the chosen pixels.
+#include "sample.hpp"
