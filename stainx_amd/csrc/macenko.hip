@@ -396,13 +396,23 @@ template <typename F> struct LevelTables<Coded<F>> {
 // lane % kCodeCopies: with one copy half of the LDS pipe's cycles were bank conflicts in the tile-resident kernel).
 // code_pack(): a pack's 3 x V elements -> their codes (one 32-bit word per plane, stored to the tile's code planes), their optical
 // densities, and whether any element of the wave's packs is not a grey level (then: the densities by the expression, the tile marked).
+// One entry of that table, and the test every user of it makes (code_quad below, the prior of the two-pass form): the nearest grey level of
+// an element, and whether the element's bits are that level's.
+template <typename F> __device__ __forceinline__ uint2 code_entry(int k) {
+    const float v = code_value<F>(k);
+    return make_uint2(__float_as_uint(v), __float_as_uint(optical_density<F>(v)));
+}
+// nearest grey level: 255 x + 2^23 has it in the low bits of its mantissa (round to nearest even; an x outside [0, 1] or a NaN leaves
+// some other byte there, and level_differs() is non-zero).  bfloat16 tiles: x = k / 255 rounded to eight bits is off by at most
+// k 2^-9 < 0.5 after the multiplication -- still level k, and 256 different values (1 / 255 exceeds the format's spacing below 1)
+__device__ __forceinline__ uint32_t nearest_level(float x) { return __float_as_uint(fmaf(x, 255.0f, 8388608.0f)) & 0xFFu; }
+__device__ __forceinline__ uint32_t level_differs(float x, uint32_t entry_x) { return entry_x ^ __float_as_uint(x); }      // entry_x: code_entry(nearest_level(x)).x
 template <typename F, int kCodeCopies> struct CodeTable {      // (4 copies = 8 KB in the moments pass; 2 in pass A of the two-pass form, whose four workgroups per CU leave 4 KB each)
     static constexpr int copies = kCodeCopies;
     uint2 e[256 * kCodeCopies];
     __device__ __forceinline__ void fill() {
         for (int t = threadIdx.x; t < 256; t += blockDim.x) {
-            const float v = code_value<F>(t);
-            const uint2 entry = make_uint2(__float_as_uint(v), __float_as_uint(optical_density<F>(v)));
+            const uint2 entry = code_entry<F>(t);
 #pragma unroll
             for (int c = 0; c < kCodeCopies; ++c) e[t * kCodeCopies + c] = entry;
         }
@@ -636,7 +646,8 @@ __device__ __forceinline__ void store_codes(const Geometry& g, const Workspace& 
 // Four pixels of a pack (i0 ... i0 + 3: one 32-bit word of codes per plane) at a time: twelve optical densities live, not 3 V (a pack of
 // eight bf16 / f16 pixels at once spilled the moments pass and pass A to scratch).
 template <typename T, int V, bool kInter, class Table>
-__device__ __forceinline__ void code_quad(const PixelPacks<T, V, kInter>& u, int i0, const LevelTables<T>& tb, const Table& ct, const Geometry& g, const Workspace& ws, int64_t tile, float (&od_quad)[4][3], uint32_t (&word)[3][V / 4]) {
+__device__ __forceinline__ void code_quad(const PixelPacks<T, V, kInter>& u, int i0, const LevelTables<T>& tb, const Table& ct, const Geometry& g, const Workspace& ws, int64_t tile, float (&od_quad)[4][3], uint32_t (&word)[3][V / 4],
+                                          uint32_t* also_mark = nullptr, uint32_t mark_bits = 0u) {      // also_mark: a word that gets mark_bits (atomic or) where the tile is marked
     static_assert((V == 4 || V == 8) && !kInter, "a pack's codes are one or two 32-bit words of a plane");
     constexpr int kCodeCopies = Table::copies;
     uint32_t differ = 0u;
@@ -647,13 +658,9 @@ __device__ __forceinline__ void code_quad(const PixelPacks<T, V, kInter>& u, int
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
             const float x = u.value(c, i0 + ii);
-            // nearest grey level: 255 x + 2^23 has it in the low bits of its mantissa (round to nearest even; an x outside [0, 1] or a
-            // NaN leaves some other byte there, and the comparison below fails).  bfloat16 tiles: x = k / 255 rounded to eight bits is off
-            // by at most k 2^-9 < 0.5 after the multiplication -- still level k, and 256 different values (1 / 255 exceeds the format's
-            // spacing below 1)
-            const uint32_t k = __float_as_uint(fmaf(x, 255.0f, 8388608.0f)) & 0xFFu;
+            const uint32_t k = nearest_level(x);
             const uint2 entry = ct.e[k * kCodeCopies + copy];
-            differ |= entry.x ^ __float_as_uint(x);
+            differ |= level_differs(x, entry.x);
             od_quad[ii][c] = __uint_as_float(entry.y);
             w |= k << (8 * ii);
         }
@@ -668,7 +675,10 @@ __device__ __forceinline__ void code_quad(const PixelPacks<T, V, kInter>& u, int
                 asm volatile("" : "+v"(x));      // (a real branch: without this the logarithms are computed for every pack and selected away)
                 od_quad[ii][c] = od_of<T>(x, tb);
             }
-        if (differ != 0u) put(&ws.code_bad[tile], g.code_epoch);
+        if (differ != 0u) {
+            put(&ws.code_bad[tile], g.code_epoch);
+            if (also_mark) atomicOr(also_mark, mark_bits);
+        }
     }
 }
 

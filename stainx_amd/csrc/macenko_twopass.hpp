@@ -88,6 +88,8 @@ struct alignas(128) PriorRecord {
     int32_t mode;                  // 0: speculate, 1: slow (the stages select over the whole tile)
     int32_t min_first;
     uint32_t open;                 // bit i: angle boundary i is open (nothing is excluded on that side)
+    uint32_t coded;                // 1: a coded call, and every element of the presample is an 8-bit level -- pass A (dense records) looks the tile's
+                                   // optical densities up and leaves its candidates as 4-byte code records; 0: plain pass A, 16-byte records
 };
 
 // ---- fused transform (macenko_fused.hpp): what its roles hand each other inside ONE launch -------------------------------
@@ -142,6 +144,7 @@ struct alignas(16) PriorScratch {
     float bkey[4], blevel[4];          // the four boundaries as diamond keys (before an open side is given its stand-in) and their quantile levels
     uint32_t cmax[4];
     uint32_t open;
+    uint32_t not_level[kGroupThreads / kWave];      // per wave: some element of its share of the presample is not an 8-bit level
 };
 
 // One wave: the bin of a kPriorBins-bin histogram that holds 0-based rank `rank`: kPriorBins / 64 consecutive bins per lane,
@@ -216,6 +219,7 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
     __shared__ PriorScratch sh;
     const int tile = blockIdx.x, tid = threadIdx.x, wave = tid / kWave;
     const uint32_t lane = lane_id();
+    constexpr bool kCodes = kVec && Codable<T, 4, kInter>::value;      // the instantiation that serves coded calls (g.code_epoch != 0)
     GroupState& st = ws.state[tile];
     PriorRecord* pr = &ws.prior[tile];
     const T* img = images + (int64_t)tile * 3 * g.pixels;
@@ -247,11 +251,22 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
         bool have_quad[kPriorSweeps];
 #pragma unroll
         for (int s = 0; s < kPriorSweeps; ++s) have_quad[s] = prior_fetch<T, kVec, kInter>(img, g, s, raw[s]);
+        uint32_t differ = 0u;      // (coded calls) some sampled element is not an 8-bit level: the test of code_quad() on every element of the sample
 #pragma unroll
         for (int s = 0; s < kPriorSweeps; ++s) {
             float od[4][3];
             prior_densities<T>(raw[s], od);
             const bool have = have_quad[s];
+            if constexpr (kCodes) {
+                if (g.code_epoch != 0u) {      // (uniform over the launch; the level's float by its expression, as CodeTable::fill() computes it: no table in LDS, no barrier in front of the first look)
+                    uint32_t d = 0u;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) d |= level_differs(raw[s][c][i], __float_as_uint(code_value<T>((int)nearest_level(raw[s][c][i]))));
+                    differ |= have ? d : 0u;
+                }
+            }
             // (kept for the second look in fp16: brackets and thresholds of a SAMPLE need no more, and reading the pixels again
             // -- from L2, with their logarithms -- was 3 us of this kernel)
 #pragma unroll
@@ -285,6 +300,10 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
             const float s = wave_total_f32(m[k]);
             if (lane == kWave - 1) sh.red[wave][k] = (double)s;
         }
+        if constexpr (kCodes) {
+            const uint64_t any = __ballot(differ != 0u);
+            if (lane == 0) sh.not_level[wave] = any ? 1u : 0u;
+        }
     }
     __syncthreads();
     if (tid < kMoments) {
@@ -292,6 +311,21 @@ __global__ __launch_bounds__(kGroupThreads) void prior_kernel(const T* __restric
         if (tid < kPartial)
             for (int w = 0; w < kGroupThreads / kWave; ++w) s += sh.red[w][tid];
         sh.mom[tid] = s;
+    }
+    // The verdict pass A and the stages branch on, written whether or not the speculation goes on below.  A sample with a non-level marks
+    // the tile for the reconstruct pass here: pass A then neither looks its elements up nor stores codes.
+    if (tid == kWave) {
+        uint32_t coded = 0u;
+        if constexpr (kCodes) {
+            if (g.code_epoch != 0u) {
+                uint32_t bad = 0u;
+#pragma unroll
+                for (int w = 0; w < kGroupThreads / kWave; ++w) bad |= sh.not_level[w];
+                coded = bad ? 0u : 1u;
+                if (bad) put(&ws.code_bad[tile], g.code_epoch);
+            }
+        }
+        put(&pr->coded, coded);
     }
     __syncthreads();
     const int m_kept = (int)sh.mom[0];
@@ -638,9 +672,48 @@ __device__ __forceinline__ void write_records_fused(const uint32_t (*__restrict_
     }
 }
 
+// Tiles of 8-bit levels (PriorRecord::coded, pass_a_kernel<kDense>): an optical-density triple there is a function of the pixel's three
+// codes, so a record is ONE word -- code0 | code1 << 8 | code2 << 16 | slot flags << 24 -- both in the wave's LDS queue (one plane) and in
+// the slot's area of the record array (the same areas as the 16-byte form, a quarter filled: record i of slot s at byte
+// (s cap) 16 + 4 i).  Room is reserved exactly as write_records_fused does; the stage turns the codes back into the very floats
+// pass A held (its own copy of the code table).
+constexpr int kQueueCodes = 4 * kQueue2;               // one-word records a wave queues before it must flush (the LDS of the four-plane queue)
+constexpr int kCodeRecordAux = 16;                     // the records' stores: sc1, write-through (measured against plain stores: DESIGN.md 4a)
+__device__ __forceinline__ void write_records_codes(const uint32_t* __restrict__ queue, uint32_t n, uint4* __restrict__ rec_tile, uint32_t cap, uint32_t* __restrict__ ncand) {
+    if (n == 0) return;
+    const uint32_t lane = lane_id();
+    uint32_t count[kSlots] = {0u, 0u, 0u, 0u};
+    for (uint32_t i0 = 0; i0 < n; i0 += kWave) {
+        const uint32_t i = i0 + lane, flags = i < n ? queue[i] >> 24 : 0u;
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) count[s] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(((flags >> s) & 1u) != 0));
+    }
+    uint32_t base = 0;
+    {
+        const uint32_t mine = lane == 0 ? count[0] : (lane == 1 ? count[1] : (lane == 2 ? count[2] : count[3]));
+        if (lane < (uint32_t)kSlots && mine) base = __hip_atomic_fetch_add(&ncand[lane], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    uint32_t at0[kSlots];
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) at0[s] = (uint32_t)__builtin_amdgcn_readlane((int)base, s);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(rec_tile, 0, (int)(kSlots * cap * 16u), 0x00020000);      // (rec_tile is wave-uniform; `at < cap` below keeps every store inside its slot's area)
+    for (uint32_t i0 = 0; i0 < n; i0 += kWave) {
+        const uint32_t i = i0 + lane, rec = i < n ? queue[i] : 0u;
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const bool has = ((rec >> (24 + s)) & 1u) != 0;
+            const uint64_t mask = __builtin_amdgcn_ballot_w64(has);
+            const uint32_t at = at0[s] + rank_in_mask(mask);
+            if (has && at < cap) __builtin_amdgcn_raw_buffer_store_b32(rec, rsrc, (int)((uint32_t)s * cap * 16u + at * 4u), 0, kCodeRecordAux);
+            at0[s] += (uint32_t)__popcll(mask);
+        }
+    }
+}
+
 // kEmit: the pass also leaves the tile as 8-bit codes for the reconstruct pass to read (Coded<F>, code_pack() in macenko.hip): the
 // optical densities of a pack of grey levels then come from the code table instead of three v_log_f32 per pixel.
-template <typename T, int V, int TPB, bool kInter, bool kFused = false, bool kEmit = false>
+// kCodeRec (with kFused and kEmit; a tile the prior found coded): one-word code records, see write_records_codes.
+template <typename T, int V, int TPB, bool kInter, bool kFused = false, bool kEmit = false, bool kCodeRec = false>
 __device__ __forceinline__ void pass_a_item(const T* __restrict__ images, const Geometry& g, const Workspace& ws, int64_t tile, int chunk_id, int64_t item, PassAScratch<TPB>* sh, const LevelTables<T>& tb,
                                             const CodeTable<T, 2>* __restrict__ ct = nullptr) {
     const int64_t p_begin = (int64_t)chunk_id * g.chunk;
@@ -676,12 +749,17 @@ __device__ __forceinline__ void pass_a_item(const T* __restrict__ images, const 
 #pragma unroll
     for (int k = 0; k < kPartial; ++k) m[k] = 0.0f;
 
+    static_assert(!kCodeRec || (kFused && kEmit), "code records: dense arrays, looked-up optical densities");
     uint32_t (*queue)[kQueue2] = sh->queue[wave];
+    uint32_t* const queue_codes = &sh->queue[wave][0][0];      // (kCodeRec: the same LDS as one plane of kQueueCodes words)
+    constexpr uint32_t kQueueRoom = kCodeRec ? kQueueCodes : kQueue2;
     uint32_t n_q = 0, have[kSlots] = {0u, 0u, 0u, 0u}, below_a = 0, below_b = 0;
     float* cand_tile = ws.cand_od + (size_t)tile * kSlots * 3 * g.cap2;
     const uint32_t seg = (uint32_t)chunk_id * (TPB / kWave) + (uint32_t)wave, seg_base = seg * g.seg_cap;
     auto flush = [&]() {
-        if constexpr (kFused)
+        if constexpr (kCodeRec)
+            write_records_codes(queue_codes, n_q, ws.cand_rec + (size_t)tile * kSlots * g.fused_cap, g.fused_cap, ws.ftile[tile].ncand);
+        else if constexpr (kFused)
             write_records_fused(queue, n_q, ws.cand_rec + (size_t)tile * kSlots * g.fused_cap, g.fused_cap, ws.ftile[tile].ncand);
         else
             write_records(queue, n_q, have, cand_tile, g, seg_base, st.over_count);
@@ -710,11 +788,12 @@ __device__ __forceinline__ void pass_a_item(const T* __restrict__ images, const 
             // rate, 46 -> 55 us -- 49 us with the stores left out, and no cheaper with the stores held back until just before the next
             // pack's request (59 us) or with conflict-free table copies: the reconstruct pass gets 20 us back)
             float od_quad[4][3];
+            uint32_t word[3][1] = {{0u}, {0u}, {0u}};
             if constexpr (kEmit) {      // (the whole pack in front of the pixel loop: looked up quad by quad inside it, the pass took 61 us instead of 54)
                 static_assert(!kEmit || V == 4, "one quad per pack");
                 if (live) {
-                    uint32_t word[3][1];
-                    code_quad(u, 0, tb, *ct, g, ws, tile, od_quad, word);
+                    // (kCodeRec: a non-level the presample missed -- the tile's records mean nothing then, and its four slots take the stage's whole-tile select)
+                    if constexpr (kCodeRec) code_quad(u, 0, tb, *ct, g, ws, tile, od_quad, word, &st.spec, kSpecSlow); else code_quad(u, 0, tb, *ct, g, ws, tile, od_quad, word);
                     store_codes<1>(g, ws, tile, base_p + mine, word);
                 }
             }
@@ -789,14 +868,19 @@ __device__ __forceinline__ void pass_a_item(const T* __restrict__ images, const 
                             flags |= __builtin_amdgcn_inverse_ballot_w64(c_d) ? 8u : 0u;
                             if (__builtin_amdgcn_inverse_ballot_w64(any)) {
                                 const uint32_t at = n_q + rank_in_mask(any);
-                                queue[0][at] = __float_as_uint(o[0]);
-                                queue[1][at] = __float_as_uint(o[1]);
-                                queue[2][at] = __float_as_uint(o[2]);
-                                queue[3][at] = flags;
+                                if constexpr (kCodeRec) {
+                                    const int at_byte = 8 * ((i0 + gi) % 4);
+                                    queue_codes[at] = ((word[0][0] >> at_byte) & 0xFFu) | (((word[1][0] >> at_byte) & 0xFFu) << 8) | (((word[2][0] >> at_byte) & 0xFFu) << 16) | (flags << 24);
+                                } else {
+                                    queue[0][at] = __float_as_uint(o[0]);
+                                    queue[1][at] = __float_as_uint(o[1]);
+                                    queue[2][at] = __float_as_uint(o[2]);
+                                    queue[3][at] = flags;
+                                }
                             }
                             n_q += (uint32_t)__popcll(any);
                         }
-                        if (__builtin_expect(n_q > (uint32_t)(kQueue2 - kWave), 0)) flush();      // the next pixel adds at most 64 records
+                        if (__builtin_expect(n_q > kQueueRoom - (uint32_t)kWave, 0)) flush();      // the next pixel adds at most 64 records
                     }
                 }
                 // (narrow pixels: 8 or 16 of these bodies in a row, and the scheduler would start all their table reads and
@@ -880,10 +964,12 @@ __global__ __launch_bounds__(kStreamThreads, (Codable<T, V, kInter>::value ? 4 :
     __shared__ LevelTables<T> tb;
     tb.fill();
     if constexpr (Codable<T, V, kInter>::value) {
-        if (g.code_epoch != 0u) {      // (uniform over the launch)
+        // Dense records: the prior has decided per tile, before this launch, whether the tile is 8-bit levels (PriorRecord::coded) -- one
+        // record format per tile, and a tile of ordinary floats pays for no lookup that fails.  The segment form finds out wave by wave.
+        if (g.code_epoch != 0u && (!kDense || get(&ws.prior[blockIdx.x / g.blocks_per_tile].coded) != 0u)) {      // (uniform over the workgroup)
             __shared__ CodeTable<T, 2> ct;
             ct.fill();
-            pass_a_item<T, V, kStreamThreads, kInter, kDense, true>(images, g, ws, blockIdx.x / g.blocks_per_tile, blockIdx.x % g.blocks_per_tile, blockIdx.x, &sh, tb, &ct);
+            pass_a_item<T, V, kStreamThreads, kInter, kDense, true, kDense>(images, g, ws, blockIdx.x / g.blocks_per_tile, blockIdx.x % g.blocks_per_tile, blockIdx.x, &sh, tb, &ct);
             return;
         }
     }
@@ -1020,21 +1106,56 @@ __device__ __forceinline__ void prefetch_candidates_dense(CandPrefetch<kPre>& pf
         for (int c = 0; c < 3; ++c) pf.od[u][c] = __uint_as_float(rec[c]);
     }
 }
+// The one-word code records of a coded tile (write_records_codes) have a prefetch of their own -- one register per prefetched record --
+// and share the walk below, which takes its records from `pc` and four bytes apart where `codes` (workgroup-uniform) is set: the same
+// walk and the same prefetch depths in records, a quarter of the bytes.  (A second copy of the walk for this format -- every key lambda
+// of the stage inlined twice more -- made the compiler keep the kernel's arguments in scratch memory, 248 bytes per lane.)
+// `od_of_code` is the stage's copy of the code table's optical densities (code_entry().y: the bits pass A held), read once the barrier
+// behind its filling has passed.
+template <int kPre> struct CodePrefetch {
+    uint32_t rec[kPre];
+};
+template <int kPre>
+__device__ __forceinline__ void prefetch_candidates_codes(CodePrefetch<kPre>& pc, __amdgpu_buffer_rsrc_t rsrc) {
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) pc.rec[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((threadIdx.x + (uint32_t)u * blockDim.x) * 4u), 0, 0);
+}
+__device__ __forceinline__ void code_record_densities(uint32_t rec, const float* __restrict__ od_of_code, float (&od)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) od[c] = od_of_code[(rec >> (8 * c)) & 0xFFu];
+}
 template <int kPre, class Fn>
-__device__ __forceinline__ void for_each_candidate_dense(const CandPrefetch<kPre>& pf, uint32_t n, __amdgpu_buffer_rsrc_t rsrc, Fn fn) {
+__device__ __forceinline__ void for_each_candidate_dense(const CandPrefetch<kPre>& pf, const CodePrefetch<kPre>& pc, bool codes, const float* __restrict__ od_of_code, uint32_t n, __amdgpu_buffer_rsrc_t rsrc, Fn fn) {
 #pragma unroll
     for (int u = 0; u < kPre; ++u) {
         const uint32_t i = threadIdx.x + (uint32_t)u * blockDim.x;
-        if (i < n) fn(i, pf.od[u]);
+        if (i < n) {
+            float od[3];
+            if (codes) {
+                code_record_densities(pc.rec[u], od_of_code, od);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) od[c] = pf.od[u][c];
+            }
+            fn(i, od);
+        }
     }
     constexpr int kFlight = 4;
     for (uint32_t i0 = threadIdx.x + (uint32_t)kPre * blockDim.x; i0 < n; i0 += blockDim.x * kFlight) {
         float od[kFlight][3];
+        if (codes) {
+            uint32_t rec[kFlight];
 #pragma unroll
-        for (int u = 0; u < kFlight; ++u) {
-            const sx_u4 rec = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((i0 + (uint32_t)u * blockDim.x) * 16u), 0, 0);
+            for (int u = 0; u < kFlight; ++u) rec[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((i0 + (uint32_t)u * blockDim.x) * 4u), 0, 0);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) od[u][c] = __uint_as_float(rec[c]);
+            for (int u = 0; u < kFlight; ++u) code_record_densities(rec[u], od_of_code, od[u]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < kFlight; ++u) {
+                const sx_u4 rec = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((i0 + (uint32_t)u * blockDim.x) * 16u), 0, 0);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) od[u][c] = __uint_as_float(rec[c]);
+            }
         }
 #pragma unroll
         for (int u = 0; u < kFlight; ++u) {
@@ -1399,6 +1520,8 @@ template <typename T, bool kDense = false>
 __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* __restrict__ images, Geometry g, Workspace ws, const float* __restrict__ target_max_conc,
                                                                        uint32_t* __restrict__ key_scratch) {
     __shared__ SlotScratch sh;
+    constexpr bool kCodeRec = kDense && Codable<T, 4, false>::value;      // tiles the prior found coded carry one-word code records (write_records_codes)
+    __shared__ float od_of_code[kCodeRec ? 256 : 1];
     const int tile = blockIdx.x >> 1, j = blockIdx.x & 1, slot = 2 + j;
     // the slow exact path's key scratch: plane j of the tile's (not yet written) output, one word per pixel
     uint32_t* keep = key_scratch ? key_scratch + ((size_t)tile * 3 + j) * (size_t)g.pixels * (sizeof(T) >= 4 ? sizeof(T) / 4 : 1) : nullptr;
@@ -1406,6 +1529,8 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
     const PriorRecord* pr = &ws.prior[tile];
     const uint32_t below = get(&st.below[j]), spec = get(&st.spec);
     const int mode = get(&pr->mode);
+    bool coded = false;      // (workgroup-uniform)
+    if constexpr (kCodeRec) coded = g.code_epoch != 0u && get(&pr->coded) != 0u;
     const bool stamps = j == 0;
     if (stamps) SX_STAMP(st, 8);
     const float* c0 = ws.cand_od + ((size_t)tile * kSlots + j) * 3 * g.cap2;
@@ -1429,7 +1554,15 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
         }
         if (threadIdx.x == kWave && mode == 0) phi_bin_setup(pr, j, &sh.phi_bins);
         CandPrefetch<8> pf;
-        if constexpr (kDense) prefetch_candidates_dense(pf, rsrc_phi); else prefetch_candidates(pf, g, c0);
+        CodePrefetch<8> pc;
+        if constexpr (kDense) {
+            if (coded) prefetch_candidates_codes(pc, rsrc_phi); else prefetch_candidates_dense(pf, rsrc_phi);
+        } else {
+            prefetch_candidates(pf, g, c0);
+        }
+        if constexpr (kCodeRec) {      // (the barrier at the top of exact_plane lies between this and the first lookup)
+            if (coded && threadIdx.x < 256) od_of_code[threadIdx.x] = __uint_as_float(code_entry<T>((int)threadIdx.x).y);
+        }
         select_prepare(&sh);
         if constexpr (kDense) dense_count(&sh, g, ws, tile, j); else segment_prefix(&sh, g, ws, tile, j);
         // The range of the level-0 bins is known BEFORE the keys are made (phi_bin_range), so the histogram is filled while they are made.
@@ -1458,7 +1591,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
                 if (i < (uint32_t)kLdsKeys) sh.keys[i] = k; else put(&spill[i - kLdsKeys], k);
                 atomicAdd(&hist[bin_of(k, origin, scale)], 1u);
             };
-            if constexpr (kDense) for_each_candidate_dense(pf, n, rsrc_phi, phi_key_of); else for_each_candidate(pf, &sh, g, c0, phi_key_of);
+            if constexpr (kDense) for_each_candidate_dense(pf, pc, coded, od_of_code, n, rsrc_phi, phi_key_of); else for_each_candidate(pf, &sh, g, c0, phi_key_of);
             if (threadIdx.x == kGroupThreads - 1) sh.ok = phi_slot_check(&sh.prior, v, j, sh.check, g.spec_rot) ? 1 : 0;
             __syncthreads();
             if (stamps) SX_STAMP(st, 10);
@@ -1496,7 +1629,12 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
     if (stamps) SX_STAMP(st, 12);
     const float* c1 = ws.cand_od + ((size_t)tile * kSlots + slot) * 3 * g.cap2;
     CandPrefetch<12> pf;
-    if constexpr (kDense) prefetch_candidates_dense(pf, rsrc_conc); else prefetch_candidates(pf, g, c1);      // in flight while the partner finishes
+    CodePrefetch<12> pc;
+    if constexpr (kDense) {      // in flight while the partner finishes
+        if (coded) prefetch_candidates_codes(pc, rsrc_conc); else prefetch_candidates_dense(pf, rsrc_conc);
+    } else {
+        prefetch_candidates(pf, g, c1);
+    }
     __syncthreads();                     // everyone is done with the first selection's scratch
     select_prepare(&sh, true);           // (the bins' range comes from vectors_and_check: [k_floor, k_ceil])
     if constexpr (kDense) dense_count(&sh, g, ws, tile, slot); else segment_prefix(&sh, g, ws, tile, slot);      // (wave 0)
@@ -1571,7 +1709,7 @@ __global__ __launch_bounds__(kGroupThreads) void estimate_stage_kernel(const T* 
             if (i < (uint32_t)kLdsKeys) sh.keys[i] = k; else put(&spill[i - kLdsKeys], k);
             if (k < k_floor) ++under; else atomicAdd(&hist[bin_of(k, origin, scale)], 1u);
         };
-        if constexpr (kDense) for_each_candidate_dense(pf, n, rsrc_conc, conc_key_of); else for_each_candidate(pf, &sh, g, c1, conc_key_of);
+        if constexpr (kDense) for_each_candidate_dense(pf, pc, coded, od_of_code, n, rsrc_conc, conc_key_of); else for_each_candidate(pf, &sh, g, c1, conc_key_of);
         under = wave_total_u32(under);
         if (lane_id() == 0 && under) atomicAdd(&sh.n_under, under);
         __syncthreads();
