@@ -510,7 +510,7 @@ __global__ __launch_bounds__(kStreamThreads) void deconv_quantify_kernel(const T
 // four for one-byte output, sixteen sweeps on the scalar path) ----
 template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
 static int run_deconv_apply(const T* images, O* out, DeconvArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    constexpr int VR = pack_for<O, V>();
     a.chunk = kStreamThreads * VR * (V == 1 ? 16 : apply_sets<O>());
     a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
     hipLaunchKernelGGL((deconv_apply_kernel<T, O, VR, kUnit, kInter, kMask>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, out, a, mk);
@@ -519,39 +519,21 @@ static int run_deconv_apply(const T* images, O* out, DeconvArgs a, hipStream_t s
 
 template <typename T, bool kMask = false>
 static int deconv_apply_typed(const void* images, void* out, const DeconvArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    const bool u8_half = sizeof(T) == 1 && out_code != 0;
-    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
     constexpr int W = PackOf<T>::n;
-    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem_bytes(sizeof(T), out_code, unit) * W);
     if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);      // (the mask's packs are as wide as the pixels': its pointer has a say of its own)
     const T* in = static_cast<const T*>(images);
-#define SX_RUN_DECONV(O, U)                                                                                                                         \
-    if constexpr (kMask)                                                                                                                            \
-        return vec ? run_deconv_apply<T, O, W, U, false, true>(in, static_cast<O*>(out), a, stream, mk) : run_deconv_apply<T, O, 1, U, false, true>(in, static_cast<O*>(out), a, stream, mk); \
-    else                                                                                                                                            \
-    return interleaved ? (vec ? run_deconv_apply<T, O, W, U, true>(in, static_cast<O*>(out), a, stream) : run_deconv_apply<T, O, 1, U, true>(in, static_cast<O*>(out), a, stream)) \
-                       : (vec ? run_deconv_apply<T, O, W, U, false>(in, static_cast<O*>(out), a, stream) : run_deconv_apply<T, O, 1, U, false>(in, static_cast<O*>(out), a, stream));
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && out_code == SX_BF16) {
-            if (unit) { SX_RUN_DECONV(__hip_bfloat16, true) } else { SX_RUN_DECONV(__hip_bfloat16, false) }
-        }
-        if (u8_half) {
-            if (unit) { SX_RUN_DECONV(__half, true) } else { SX_RUN_DECONV(__half, false) }
-        }
-        if (u8_unit) {
-            SX_RUN_DECONV(float, true)
-        }
-        SX_RUN_DECONV(T, false)
-    } else {
-        if (unit) { SX_RUN_DECONV(T, true) } else { SX_RUN_DECONV(T, false) }
-    }
-#undef SX_RUN_DECONV
+    return with_out<T>(out_code, unit, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) {
+            return run_deconv_apply<T, O, decltype(v)::value, decltype(u)::value, decltype(inter)::value, kMask>(in, static_cast<O*>(out), a, stream, mk);
+        });
+    });
 }
 
 template <typename T, typename O, int V, bool kUnit, bool kInter>
 static int run_deconv_separate(const T* images, DeconvArgs a, hipStream_t stream) {
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    constexpr int VR = pack_for<O, V>();
     a.chunk = kStreamThreads * VR * (VR == 1 ? 16 : 1);
     a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
     hipLaunchKernelGGL((deconv_separate_kernel<T, O, VR, kUnit, kInter>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, a);
@@ -561,34 +543,16 @@ static int run_deconv_separate(const T* images, DeconvArgs a, hipStream_t stream
 template <typename T>
 static int deconv_separate_typed(const void* images, const DeconvArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream) {
     const bool stains = a.stains != nullptr;
-    const bool u8_half = stains && sizeof(T) == 1 && out_code != 0;
-    const bool u8_unit = stains && unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = !stains ? sizeof(float) : (u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T)));
     constexpr int W = PackOf<T>::n;
-    const bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(a.stains, out_elem * W)) && (!a.conc || aligned_for(a.conc, 16));
+    const bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(a.stains, out_elem_bytes(sizeof(T), out_code, unit) * W)) && (!a.conc || aligned_for(a.conc, 16));
     const T* in = static_cast<const T*>(images);
     // (O: the images' element -- float for a call without images)
-#define SX_RUN_DSEP(O, U)                                                                                                              \
-    return interleaved ? (vec ? run_deconv_separate<T, O, W, U, true>(in, a, stream) : run_deconv_separate<T, O, 1, U, true>(in, a, stream)) \
-                       : (vec ? run_deconv_separate<T, O, W, U, false>(in, a, stream) : run_deconv_separate<T, O, 1, U, false>(in, a, stream));
-    if (!stains) {
-        SX_RUN_DSEP(float, false)
-    }
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && out_code == SX_BF16) {
-            if (unit) { SX_RUN_DSEP(__hip_bfloat16, true) } else { SX_RUN_DSEP(__hip_bfloat16, false) }
-        }
-        if (u8_half) {
-            if (unit) { SX_RUN_DSEP(__half, true) } else { SX_RUN_DSEP(__half, false) }
-        }
-        if (u8_unit) {
-            SX_RUN_DSEP(float, true)
-        }
-        SX_RUN_DSEP(T, false)
-    } else {
-        if (unit) { SX_RUN_DSEP(T, true) } else { SX_RUN_DSEP(T, false) }
-    }
-#undef SX_RUN_DSEP
+    return with_out<T>(out_code, unit, stains, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W>(vec, interleaved, [&](auto v, auto inter) {
+            return run_deconv_separate<T, O, decltype(v)::value, decltype(u)::value, decltype(inter)::value>(in, a, stream);
+        });
+    });
 }
 
 // (two pack widths: four float32 concentrations per plane and lane where the pointers and the tile size allow it, single pixels otherwise)
@@ -599,14 +563,10 @@ static int deconv_combine_typed(const float* conc, void* out, DeconvArgs a, bool
     a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
     const dim3 grid((unsigned)(a.n_tiles * a.blocks)), block(kStreamThreads);
     O* dst = static_cast<O*>(out);
-    if (interleaved) {
-        if (vec) hipLaunchKernelGGL((deconv_combine_kernel<O, 4, kUnit, true>), grid, block, 0, stream, conc, dst, a);
-        else hipLaunchKernelGGL((deconv_combine_kernel<O, 1, kUnit, true>), grid, block, 0, stream, conc, dst, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((deconv_combine_kernel<O, 4, kUnit, false>), grid, block, 0, stream, conc, dst, a);
-        else hipLaunchKernelGGL((deconv_combine_kernel<O, 1, kUnit, false>), grid, block, 0, stream, conc, dst, a);
-    }
-    return check_launch("deconv combine");
+    return with_layout<4>(vec, interleaved, [&](auto v, auto inter) {
+        hipLaunchKernelGGL((deconv_combine_kernel<O, decltype(v)::value, kUnit, decltype(inter)::value>), grid, block, 0, stream, conc, dst, a);
+        return check_launch("deconv combine");
+    });
 }
 
 template <typename T, int V, bool kInter, bool kMask = false>
@@ -623,13 +583,8 @@ static int deconv_quantify_typed(const void* images, const QuantArgs& a, bool in
     constexpr int W = PackOf<T>::n;
     bool vec = (a.pixels % W == 0) && aligned_for(images, 16);
     const T* in = static_cast<const T*>(images);
-    if constexpr (kMask) {
-        vec = vec && aligned_for(mk.mask, W);
-        return vec ? run_deconv_quantify<T, W, false, true>(in, a, stream, mk) : run_deconv_quantify<T, 1, false, true>(in, a, stream, mk);
-    } else {
-        if (interleaved) return vec ? run_deconv_quantify<T, W, true>(in, a, stream) : run_deconv_quantify<T, 1, true>(in, a, stream);
-        return vec ? run_deconv_quantify<T, W, false>(in, a, stream) : run_deconv_quantify<T, 1, false>(in, a, stream);
-    }
+    if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
+    return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) { return run_deconv_quantify<T, decltype(v)::value, decltype(inter)::value, kMask>(in, a, stream, mk); });
 }
 
 }  // namespace macenko
@@ -649,9 +604,7 @@ static int deconv_flags_ok(unsigned flags, int dtype, bool planar_only, const ch
     const unsigned allowed = SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16 | (planar_only ? 0u : SX_MACENKO_CHANNELS_LAST);
     if (planar_only && (flags & SX_MACENKO_CHANNELS_LAST)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes planar (N,3,H,W) tiles only (no SX_MACENKO_CHANNELS_LAST)", flags, who);
     if (flags & ~allowed) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags, who);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
-    return SX_OK;
+    return out_flags_ok(flags, dtype);
 }
 
 template <bool kMask>
@@ -661,7 +614,7 @@ static int deconv_apply_call(const void* images, void* out, int dtype, int64_t n
     int rc = deconv_common_ok(images, n, h, w, basis, n_bases, "images");
     if (rc != SX_OK) return rc;
     if (!out) return fail(SX_ERR_BAD_ARG, "out pointer is null");
-    if (kMask && !mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (kMask && (rc = check_mask(mask_dev)) != SX_OK) return rc;
     if (target && n_targets != 1 && n_targets != n) return fail(SX_ERR_BAD_ARG, "n_targets must be 1 (one target basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_targets);
     if ((alpha == nullptr) != (beta == nullptr)) return fail(SX_ERR_BAD_ARG, "alpha and beta: both given or both null");
     rc = deconv_flags_ok(flags, dtype, kMask, who);
@@ -675,20 +628,13 @@ static int deconv_apply_call(const void* images, void* out, int dtype, int64_t n
     a.n_tiles = n;
     a.per_basis = n_bases == n && n != 1 ? 1 : 0;
     a.per_target = target && n_targets == n && n != 1 ? 1 : 0;
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const int out_code = out_code_of(flags);
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     MaskArgs<kMask> mk{};
     if constexpr (kMask) mk.mask = mask_dev;
-    switch (dtype) {
-        case SX_U8: return deconv_apply_typed<uint8_t, kMask>(images, out, a, out_code, inter, unit, stream, mk);
-        case SX_F16: return deconv_apply_typed<__half, kMask>(images, out, a, out_code, inter, unit, stream, mk);
-        case SX_BF16: return deconv_apply_typed<__hip_bfloat16, kMask>(images, out, a, out_code, inter, unit, stream, mk);
-        case SX_F32: return deconv_apply_typed<float, kMask>(images, out, a, out_code, inter, unit, stream, mk);
-        case SX_F64: return deconv_apply_typed<double, kMask>(images, out, a, out_code, inter, unit, stream, mk);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return deconv_apply_typed<typename decltype(t)::type, kMask>(images, out, a, out_code, inter, unit, stream, mk); });
 }
 
 extern "C" int sx_deconv_apply(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, const float* target, int64_t n_targets,
@@ -715,18 +661,11 @@ extern "C" int sx_deconv_separate(const void* images, void* stains_out, float* c
     a.pixels = h * w;
     a.n_tiles = n;
     a.per_basis = n_bases == n && n != 1 ? 1 : 0;
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const int out_code = out_code_of(flags);
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return deconv_separate_typed<uint8_t>(images, a, out_code, inter, unit, stream);
-        case SX_F16: return deconv_separate_typed<__half>(images, a, out_code, inter, unit, stream);
-        case SX_BF16: return deconv_separate_typed<__hip_bfloat16>(images, a, out_code, inter, unit, stream);
-        case SX_F32: return deconv_separate_typed<float>(images, a, out_code, inter, unit, stream);
-        case SX_F64: return deconv_separate_typed<double>(images, a, out_code, inter, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return deconv_separate_typed<typename decltype(t)::type>(images, a, out_code, inter, unit, stream); });
 }
 
 extern "C" int sx_deconv_combine(const float* conc, void* out, int out_dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, unsigned flags, void* stream_ptr) {
@@ -744,14 +683,12 @@ extern "C" int sx_deconv_combine(const float* conc, void* out, int out_dtype, in
     a.per_basis = n_bases == n && n != 1 ? 1 : 0;
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (out_dtype) {
-        case SX_U8: return deconv_combine_typed<uint8_t, false>(conc, out, a, inter, stream);
-        case SX_F16: return unit ? deconv_combine_typed<__half, true>(conc, out, a, inter, stream) : deconv_combine_typed<__half, false>(conc, out, a, inter, stream);
-        case SX_BF16: return unit ? deconv_combine_typed<__hip_bfloat16, true>(conc, out, a, inter, stream) : deconv_combine_typed<__hip_bfloat16, false>(conc, out, a, inter, stream);
-        case SX_F32: return unit ? deconv_combine_typed<float, true>(conc, out, a, inter, stream) : deconv_combine_typed<float, false>(conc, out, a, inter, stream);
-        case SX_F64: return unit ? deconv_combine_typed<double, true>(conc, out, a, inter, stream) : deconv_combine_typed<double, false>(conc, out, a, inter, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", out_dtype);
-    }
+    // (the output's element; uint8 has no fused / 255: refused above)
+    return with_dtype(out_dtype, [&](auto t) {
+        using O = typename decltype(t)::type;
+        if constexpr (sizeof(O) == 1) return deconv_combine_typed<O, false>(conc, out, a, inter, stream);
+        else return unit ? deconv_combine_typed<O, true>(conc, out, a, inter, stream) : deconv_combine_typed<O, false>(conc, out, a, inter, stream);
+    });
 }
 
 template <bool kMask>
@@ -761,7 +698,7 @@ static int deconv_quantify_call(const void* images, int dtype, int64_t n, int64_
     int rc = deconv_common_ok(images, n, h, w, basis, n_bases, "images");
     if (rc != SX_OK) return rc;
     if (!out) return fail(SX_ERR_BAD_ARG, "out pointer is null");
-    if (kMask && !mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
+    if (kMask && (rc = check_mask(mask_dev)) != SX_OK) return rc;
     if (bin_log2 < 0 || bin_log2 > 8) return fail(SX_ERR_BAD_ARG, "bin_log2 must lie in [0, 8] (bins of width 2^-bin_log2), got %d", bin_log2);
     if (zero_bin < 0 || zero_bin > 255) return fail(SX_ERR_BAD_ARG, "zero_bin must lie in [0, 255] (the bin whose lower edge is concentration 0), got %d", zero_bin);
     if (kMask && (flags & SX_MACENKO_CHANNELS_LAST)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes planar (N,3,H,W) tiles only (no SX_MACENKO_CHANNELS_LAST)", flags, who);
@@ -777,21 +714,12 @@ static int deconv_quantify_call(const void* images, int dtype, int64_t n, int64_
     a.scale = (float)(1 << bin_log2);
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {      // (before anything is enqueued)
-        case SX_U8: case SX_F16: case SX_BF16: case SX_F32: case SX_F64: break;
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    if ((rc = dtype_ok(dtype)) != SX_OK) return rc;      // (before anything is enqueued)
     const size_t bytes = (size_t)(per_tile ? n : 1) * kQuantWords * sizeof(unsigned long long);
     if (hipMemsetAsync(out, 0, bytes, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
     MaskArgs<kMask> mk{};
     if constexpr (kMask) mk.mask = mask_dev;
-    switch (dtype) {
-        case SX_U8: return deconv_quantify_typed<uint8_t, kMask>(images, a, inter, stream, mk);
-        case SX_F16: return deconv_quantify_typed<__half, kMask>(images, a, inter, stream, mk);
-        case SX_BF16: return deconv_quantify_typed<__hip_bfloat16, kMask>(images, a, inter, stream, mk);
-        case SX_F32: return deconv_quantify_typed<float, kMask>(images, a, inter, stream, mk);
-        default: return deconv_quantify_typed<double, kMask>(images, a, inter, stream, mk);
-    }
+    return with_dtype(dtype, [&](auto t) { return deconv_quantify_typed<typename decltype(t)::type, kMask>(images, a, inter, stream, mk); });
 }
 
 extern "C" int sx_deconv_quantify(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,

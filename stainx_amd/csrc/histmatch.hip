@@ -14,6 +14,7 @@
 // typed LUT, 16-byte loads and stores, writes the final dtype directly (the reference's native path
 // takes three more passes: histogram_matching.cu:153-166).
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "tissue.hpp"
 
 #include <algorithm>
@@ -987,14 +988,7 @@ static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t
     if (!ws || ws_bytes < workspace_bytes()) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", workspace_bytes(), ws_bytes);
     if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return run<uint8_t>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
-        case SX_F16: return run<__half>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
-        case SX_BF16: return run<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
-        case SX_F32: return run<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
-        case SX_F64: return run<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return run<typename decltype(t)::type>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready); });
 }
 
 // sx_hm_estimate: one clear, the histogram pass of run_tiles() (per tile) or run() (pooled), the export launch.  The workspace has the
@@ -1082,14 +1076,7 @@ static int dispatch_apply_tables(const void* images, void* out, int dtype, int64
     if (masked && !mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const tissue::Source tis{mask, (masked && !mask) ? tissue::y_cut_of(threshold) : 0.0f};
-    switch (dtype) {
-        case SX_U8: return run_apply_tables<uint8_t>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
-        case SX_F16: return run_apply_tables<__half>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
-        case SX_BF16: return run_apply_tables<__hip_bfloat16>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
-        case SX_F32: return run_apply_tables<float>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
-        case SX_F64: return run_apply_tables<double>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return run_apply_tables<typename decltype(t)::type>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream); });
 }
 
 }  // namespace histmatch

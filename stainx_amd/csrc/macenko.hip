@@ -22,6 +22,7 @@
 //   * seven stream-ordered launches per transform, no host synchronisation; the pooled fit (one group over
 //     all tiles) runs the first six with one group.
 #include "common.hpp"
+#include "dispatch.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -245,71 +246,55 @@ enum WorkspaceLevel { kWsBase = 0, kWsFused = 1, kWsTwoPass = 2 };
 // coded four passes (float32 tiles of whole 16-pixel packs, batches of at least 2^20 pixels): the codes and the per-tile flags, behind the base level
 static bool coded_size(int64_t n_tiles, int64_t pixels) { return pixels % 16 == 0 && n_tiles * pixels >= (1ll << 20); }
 static size_t coded_bytes(int64_t n_tiles, int64_t pixels) { return align_up(sizeof(uint32_t) * (size_t)n_tiles, 256) + align_up((size_t)3 * pixels * n_tiles, 256); }
-static size_t workspace_bytes(int64_t n_tiles, int64_t pixels, int level = kWsTwoPass) {
-    const size_t b = (size_t)blocks_per_tile_for(pixels), n = (size_t)n_tiles;
-    size_t total = align_up(sizeof(GroupState) * n, 256);
-    total += 2 * align_up(sizeof(double) * kPartial * b * n, 256);
-    total += align_up(sizeof(uint32_t) * cand_words(n_tiles, pixels), 256);
-    total += align_up(sizeof(uint32_t) * 512 * b * n, 256);
-    total += align_up(sizeof(float) * 3 * kSample * n, 256);
-    total += align_up(sizeof(PoolState), 256);
-    if (level >= kWsFused && two_pass_size(pixels)) {
-        total += align_up(kPriorRecordBytes * n, 256);
-        total += kFusedSchedBytes;
-        total += align_up(kFusedTileBytes * n, 256);
-        if (fused_size(pixels)) total += align_up(sizeof(uint4) * kSlots * (size_t)record_cap_for(pixels) * n, 256);
-        if (fused_size(pixels)) total += align_up(sizeof(uint32_t) * kSlots * dense_spill_words(pixels) * n, 256);
-    }
-    if (level >= kWsTwoPass && two_pass_size(pixels)) {
-        total += align_up(sizeof(float) * 3 * kSlots * (size_t)cap2_for(pixels) * n, 256);
-        total += align_up(sizeof(uint32_t) * kSlots * 256 * n, 256);
-        total += align_up(sizeof(uint32_t) * kSlots * key_spill_words(pixels) * n, 256);
-    }
-    return total;
-}
-
+// ONE walk over the areas, in their order in memory: it yields the pointers of a workspace at `base` and the end of every level (what
+// workspace_bytes() and carve() both are).
 // codes_at: where the coded passes' area lies (bytes from the base): behind the level of the form the call takes (0: behind the base level)
-static Workspace carve(void* base, int64_t n_tiles, int64_t pixels, size_t codes_at = 0) {
-    Workspace w;
-    char* p = static_cast<char*>(base);
+struct WorkspaceLayout {
+    Workspace ws;
+    size_t end[3];      // [WorkspaceLevel]
+};
+static WorkspaceLayout workspace_layout(void* base, int64_t n_tiles, int64_t pixels, size_t codes_at = 0) {
+    WorkspaceLayout l{};
+    Workspace& w = l.ws;
+    const uintptr_t at = reinterpret_cast<uintptr_t>(base);
     const size_t b = (size_t)blocks_per_tile_for(pixels), n = (size_t)n_tiles;
-    w.state = reinterpret_cast<GroupState*>(p);
-    p += align_up(sizeof(GroupState) * n, 256);
-    w.partial = reinterpret_cast<double*>(p);
-    p += align_up(sizeof(double) * kPartial * b * n, 256);
-    w.partial_all = reinterpret_cast<double*>(p);
-    p += align_up(sizeof(double) * kPartial * b * n, 256);
-    w.cand = reinterpret_cast<uint32_t*>(p);
-    p += align_up(sizeof(uint32_t) * cand_words(n_tiles, pixels), 256);
-    w.block_hist = reinterpret_cast<uint32_t*>(p);
-    p += align_up(sizeof(uint32_t) * 512 * b * n, 256);
-    w.sample_od = reinterpret_cast<float*>(p);
-    p += align_up(sizeof(float) * 3 * kSample * n, 256);
-    w.pool = reinterpret_cast<PoolState*>(p);
-    p += align_up(sizeof(PoolState), 256);
-    // (beyond the base level the pointers are only used by the forms whose workspace level includes them)
-    {
-        char* c = codes_at ? static_cast<char*>(base) + codes_at : p;
-        w.code_bad = reinterpret_cast<uint32_t*>(c);
-        w.codes = reinterpret_cast<uint8_t*>(c + align_up(sizeof(uint32_t) * n, 256));
+    size_t off = 0;
+    auto area = [&](auto*& field, size_t bytes) {
+        field = reinterpret_cast<std::remove_reference_t<decltype(field)>>(at + off);
+        off += bytes;
+    };
+    area(w.state, align_up(sizeof(GroupState) * n, 256));
+    area(w.partial, align_up(sizeof(double) * kPartial * b * n, 256));
+    area(w.partial_all, align_up(sizeof(double) * kPartial * b * n, 256));
+    area(w.cand, align_up(sizeof(uint32_t) * cand_words(n_tiles, pixels), 256));
+    area(w.block_hist, align_up(sizeof(uint32_t) * 512 * b * n, 256));
+    area(w.sample_od, align_up(sizeof(float) * 3 * kSample * n, 256));
+    area(w.pool, align_up(sizeof(PoolState), 256));
+    l.end[kWsBase] = off;
+    {      // (the codes overlay the areas behind the level of the call's form: that form uses none of them)
+        size_t c = codes_at ? codes_at : off;
+        w.code_bad = reinterpret_cast<uint32_t*>(at + c);
+        w.codes = reinterpret_cast<uint8_t*>(at + c + align_up(sizeof(uint32_t) * n, 256));
     }
-    w.prior = reinterpret_cast<PriorRecord*>(p);
-    p += align_up(kPriorRecordBytes * n, 256);
-    w.fsched = reinterpret_cast<FusedSched*>(p);
-    p += kFusedSchedBytes;
-    w.ftile = reinterpret_cast<FusedTile*>(p);
-    p += align_up(kFusedTileBytes * n, 256);
-    w.cand_rec = reinterpret_cast<uint4*>(p);
-    if (fused_size(pixels)) p += align_up(sizeof(uint4) * kSlots * (size_t)record_cap_for(pixels) * n, 256);
-    w.dense_spill = reinterpret_cast<uint32_t*>(p);
-    if (fused_size(pixels)) p += align_up(sizeof(uint32_t) * kSlots * dense_spill_words(pixels) * n, 256);
-    w.cand_od = reinterpret_cast<float*>(p);
-    p += align_up(sizeof(float) * 3 * kSlots * (size_t)cap2_for(pixels) * n, 256);
-    w.seg_count = reinterpret_cast<uint32_t*>(p);
-    p += align_up(sizeof(uint32_t) * kSlots * 256 * n, 256);
-    w.key_spill = reinterpret_cast<uint32_t*>(p);
-    return w;
+    // (behind the base level: only tile sizes the two-pass form takes have these areas -- the rules that size them are defined for those
+    // sizes only -- and only the forms whose level includes an area use its pointer; for other sizes every level ends with the base)
+    l.end[kWsFused] = l.end[kWsTwoPass] = off;
+    if (!two_pass_size(pixels)) return l;
+    const bool dense = fused_size(pixels);
+    area(w.prior, align_up(kPriorRecordBytes * n, 256));
+    area(w.fsched, kFusedSchedBytes);
+    area(w.ftile, align_up(kFusedTileBytes * n, 256));
+    area(w.cand_rec, dense ? align_up(sizeof(uint4) * kSlots * (size_t)record_cap_for(pixels) * n, 256) : 0);
+    area(w.dense_spill, dense ? align_up(sizeof(uint32_t) * kSlots * dense_spill_words(pixels) * n, 256) : 0);
+    l.end[kWsFused] = off;
+    area(w.cand_od, align_up(sizeof(float) * 3 * kSlots * (size_t)cap2_for(pixels) * n, 256));
+    area(w.seg_count, align_up(sizeof(uint32_t) * kSlots * 256 * n, 256));
+    area(w.key_spill, align_up(sizeof(uint32_t) * kSlots * key_spill_words(pixels) * n, 256));
+    l.end[kWsTwoPass] = off;
+    return l;
 }
+static size_t workspace_bytes(int64_t n_tiles, int64_t pixels, int level = kWsTwoPass) { return workspace_layout(nullptr, n_tiles, pixels).end[level]; }
+static Workspace carve(void* base, int64_t n_tiles, int64_t pixels, size_t codes_at = 0) { return workspace_layout(base, n_tiles, pixels, codes_at).ws; }
 
 // ------------------------------------------------------------------------------------------------
 // data handed from one stage to the next: every stage is its own launch, so a kernel boundary publishes it and
@@ -3878,9 +3863,27 @@ static int run_fused(const T* images, O* out, const Geometry& g, const Workspace
 
 #endif
 
+// The grid of the passes that write images behind a per-tile estimate (reconstruct, separate): the geometry they run with and their work
+// items.  Big batches: ONE pack set (vr pixels) per thread and work item (no loop: 16384 small workgroups for config 2 instead of 1024
+// of sixteen sweeps -- the pass has no per-item state, and with 1024 workgroups only half the waves a CU can hold were resident: call
+// 159.2 -> 156.1 us, tools/ab_recon_chunk.py).  Small batches keep their own split (fine_chunk), and so does a reconstruct work-item
+// size set from outside (recon_chunk: the SX_RECON_CHUNK knob of the diagnostic builds, transform only).
+struct ReconGrid {
+    Geometry g;
+    unsigned items;
+};
+static ReconGrid recon_grid(const Geometry& g, int vr) {
+    ReconGrid r{g, (unsigned)(g.n_tiles * (g.recon_chunk ? g.recon_blocks : (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile)))};
+    if (!g.recon_chunk && !g.fine_chunk && vr > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {
+        r.g.recon_chunk = kStreamThreads * vr;
+        r.g.recon_blocks = (int)((g.pixels + r.g.recon_chunk - 1) / r.g.recon_chunk);
+        r.items = (unsigned)(g.n_tiles * r.g.recon_blocks);
+    }
+    return r;
+}
+
 template <typename T, typename O, int V, bool kInter = false>
 static int run_transform(const T* images, O* out, const Geometry& g, const Workspace& ws, const float* sm, const float* tmc, bool unit, hipStream_t stream) {
-    const unsigned items = (unsigned)(g.n_tiles * (g.recon_chunk ? g.recon_blocks : (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile)));      // reconstruct work items
     int rc = SX_OK;
     if (g.fast) {
         hipLaunchKernelGGL((stats_kernel<T, V, kInter>), dim3((unsigned)(g.n_tiles * g.blocks_per_tile)), dim3(kStreamThreads), 0, stream, images, g, ws);
@@ -3896,21 +3899,10 @@ static int run_transform(const T* images, O* out, const Geometry& g, const Works
         rc = run_estimate<T, V, kInter>(images, g, ws, (int)g.n_tiles, 1, tmc, nullptr, nullptr, stream);
     }
     if (rc != SX_OK) return rc;
-    // The reconstruct pass is paced by its stores: its pack is 16 bytes of OUTPUT per lane and plane, so that one store
-    // instruction of a wave writes 1 KB of consecutive bytes.  With the input's pack (16 pixels per lane for uint8) a wider output
-    // type leaves every lane 64-192 bytes of its own and every store instruction 64 different lines: uint8 -> float32 (/255)
-    // took 172 us planar and 569 us NHWC for the config-2 batch where the same-width uint8 output takes 24 us.
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
-    // Big batches: ONE pack set per thread and work item (no loop: 16384 small workgroups for config 2 instead of 1024 of sixteen
-    // sweeps -- the pass has no per-item state, and with 1024 workgroups only half the waves a CU can hold were resident: call
-    // 159.2 -> 156.1 us, tools/ab_recon_chunk.py).  Small batches keep their own split (fine_chunk).
-    Geometry gr = g;
-    unsigned items_r = items;
-    if (!g.recon_chunk && !g.fine_chunk && V > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {
-        gr.recon_chunk = kStreamThreads * VR;
-        gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
-        items_r = (unsigned)(g.n_tiles * gr.recon_blocks);
-    }
+    constexpr int VR = pack_for<O, V>();      // (16 bytes of output per lane and plane: dispatch.hpp)
+    const ReconGrid rg = recon_grid(g, VR);
+    const Geometry& gr = rg.g;
+    const unsigned items_r = rg.items;
     if (g.aug_alpha) {      // (sx_macenko_augment: the per-tile factors folded in; its own instantiations)
         if (unit)
             hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, true, kInter, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm);
@@ -3939,7 +3931,6 @@ static int device_cus() {
     }
     return cached[dev];
 }
-static int elem_bytes(int dtype) { return dtype == SX_U8 ? 1 : (dtype == SX_F16 || dtype == SX_BF16) ? 2 : dtype == SX_F32 ? 4 : 8; }
 // Whether a call can take the resident form at all: planar tiles of whole 16-byte packs, one to sixteen workgroups per tile,
 // the output of the input's type (uint8 with normalize_to_0_1: float32).
 static bool resident_able(int dtype, int64_t n, int64_t pixels, unsigned flags) {
@@ -4019,15 +4010,12 @@ static void set_fine_chunk(Geometry& g, int lane_px) {
 template <typename T>
 static int transform_typed(const void* images, void* out, const Geometry& g0, const Workspace& ws, const float* sm, const float* tmc, bool unit, hipStream_t stream) {
     Geometry g = g0;
-    const bool u8_half = sizeof(T) == 1 && g.out_code != 0;      // uint8 in, bf16 / f16 out (an extension: SURVEY.md 8f-2)
-    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
     constexpr int W = PackOf<T>::n;
-    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem_bytes(sizeof(T), g.out_code, unit) * W);
     g.vec = vec ? 1 : 0;
     g.vec_width = W;
     set_sampling(g, true);
-    if (g.fused && !(vec && !g.interleaved && !u8_half && std::is_same<T, float>::value)) {      // (unaligned pointers: the four-pass form serves them; its workspace is a prefix of the fused one)
+    if (g.fused && !(vec && !g.interleaved && std::is_same<T, float>::value)) {      // (unaligned pointers: the four-pass form serves them; its workspace is a prefix of the fused one)
         g.fused = 0;
         g.two_pass = 0;
     }
@@ -4075,44 +4063,18 @@ static int transform_typed(const void* images, void* out, const Geometry& g0, co
     }
 #endif
     const T* in = static_cast<const T*>(images);
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half) {
-#define SX_RUN_HALF(O)                                                                                                                                          \
-    return g.interleaved ? (vec ? run_transform<T, O, W, true>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, stream)                                          \
-                                : run_transform<T, O, 1, true>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, stream))                                         \
-                         : (vec ? run_transform<T, O, W>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, stream)                                                \
-                                : run_transform<T, O, 1>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, stream));
-            if (g.out_code == SX_BF16) {
-                SX_RUN_HALF(__hip_bfloat16)
-            } else {
-                SX_RUN_HALF(__half)
-            }
-#undef SX_RUN_HALF
-        }
-    }
-    if (g.interleaved) {      // (N,H,W,3): its own instantiations, so the planar kernels carry no trace of it
-        if constexpr (sizeof(T) == 1) {
-            if (u8_unit) {
-                return vec ? run_transform<T, float, W, true>(in, static_cast<float*>(out), g, ws, sm, tmc, true, stream)
-                           : run_transform<T, float, 1, true>(in, static_cast<float*>(out), g, ws, sm, tmc, true, stream);
-            }
-        }
-        return vec ? run_transform<T, T, W, true>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream)
-                   : run_transform<T, T, 1, true>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream);
-    }
-    if constexpr (sizeof(T) == 1) {
-        if (u8_unit) {
-            return vec ? run_transform<T, float, W>(in, static_cast<float*>(out), g, ws, sm, tmc, true, stream)
-                       : run_transform<T, float, 1>(in, static_cast<float*>(out), g, ws, sm, tmc, true, stream);
-        }
-    }
 #ifdef SX_DIAG
-    if constexpr (std::is_same<T, float>::value) {
+    if constexpr (std::is_same<T, float>::value) {      // (g.fused: planar tiles in 16-byte packs, see above)
         if (g.fused) return run_fused<T, T, W>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream);
     }
 #endif
-    return vec ? run_transform<T, T, W>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream)
-               : run_transform<T, T, 1>(in, static_cast<T*>(out), g, ws, sm, tmc, unit, stream);
+    // ((N,H,W,3) has its own instantiations, so the planar kernels carry no trace of it)
+    return with_out<T>(g.out_code, unit, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W>(vec, g.interleaved != 0, [&](auto v, auto inter) {
+            return run_transform<T, O, decltype(v)::value, decltype(inter)::value>(in, static_cast<O*>(out), g, ws, sm, tmc, decltype(u)::value, stream);
+        });
+    });
 }
 
 // sx_macenko_separate: the four-pass estimate (own basis without maxC: stats, plane, angle bracket and stain stage only), then one
@@ -4122,15 +4084,9 @@ template <typename T, typename O, int V, bool kUnit, bool kInter>
 static int run_separate(const T* images, const Geometry& g, const Workspace& ws, const SeparateOut& so, const float* tmc, hipStream_t stream) {
     int rc = run_estimate<T, V, kInter>(images, g, ws, (int)g.n_tiles, 1, tmc, nullptr, nullptr, stream);
     if (rc != SX_OK) return rc;
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
-    Geometry gr = g;
-    unsigned items = (unsigned)(g.n_tiles * (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile));
-    if (!g.fine_chunk && V > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {      // (big batches: one pack set per thread and work item, as run_transform)
-        gr.recon_chunk = kStreamThreads * VR;
-        gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
-        items = (unsigned)(g.n_tiles * gr.recon_blocks);
-    }
-    hipLaunchKernelGGL((separate_kernel<T, O, VR, kUnit, kInter>), dim3(items), dim3(kStreamThreads), 0, stream, images, gr, ws, so);
+    constexpr int VR = pack_for<O, V>();
+    const ReconGrid rg = recon_grid(g, VR);
+    hipLaunchKernelGGL((separate_kernel<T, O, VR, kUnit, kInter>), dim3(rg.items), dim3(kStreamThreads), 0, stream, images, rg.g, ws, so);
     return check_launch("macenko separate");
 }
 
@@ -4138,12 +4094,9 @@ template <typename T>
 static int separate_typed(const void* images, const Geometry& g0, const Workspace& ws, const SeparateOut& so, const float* tmc, bool unit, hipStream_t stream) {
     Geometry g = g0;
     const bool stains = so.stains != nullptr;
-    const bool u8_half = stains && sizeof(T) == 1 && g.out_code != 0;
-    const bool u8_unit = stains && unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = !stains ? sizeof(float) : (u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T)));
     constexpr int W = PackOf<T>::n;
     // (16-byte packs where every pointer allows them, as transform_typed decides; the scalar path otherwise)
-    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(so.stains, out_elem * W)) && (!so.conc || aligned_for(so.conc, 16));
+    const bool vec = (g.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(so.stains, out_elem_bytes(sizeof(T), g.out_code, unit) * W)) && (!so.conc || aligned_for(so.conc, 16));
     g.vec = vec ? 1 : 0;
     g.vec_width = W;
     set_sampling(g, true);
@@ -4151,27 +4104,12 @@ static int separate_typed(const void* images, const Geometry& g0, const Workspac
     set_fine_chunk(g, vec ? W : 1);
     const T* in = static_cast<const T*>(images);
     // (O: the images' element -- float for a call without images --, U: the fused /255; NHWC tiles have their own instantiations)
-#define SX_RUN_SEP(O, U)                                                                                                                 \
-    return g.interleaved ? (vec ? run_separate<T, O, W, U, true>(in, g, ws, so, tmc, stream) : run_separate<T, O, 1, U, true>(in, g, ws, so, tmc, stream)) \
-                         : (vec ? run_separate<T, O, W, U, false>(in, g, ws, so, tmc, stream) : run_separate<T, O, 1, U, false>(in, g, ws, so, tmc, stream));
-    if (!stains) {
-        SX_RUN_SEP(float, false)
-    }
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && g.out_code == SX_BF16) {
-            if (unit) { SX_RUN_SEP(__hip_bfloat16, true) } else { SX_RUN_SEP(__hip_bfloat16, false) }
-        }
-        if (u8_half) {
-            if (unit) { SX_RUN_SEP(__half, true) } else { SX_RUN_SEP(__half, false) }
-        }
-        if (u8_unit) {
-            SX_RUN_SEP(float, true)
-        }
-        SX_RUN_SEP(T, false)
-    } else {
-        if (unit) { SX_RUN_SEP(T, true) } else { SX_RUN_SEP(T, false) }
-    }
-#undef SX_RUN_SEP
+    return with_out<T>(g.out_code, unit, stains, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W>(vec, g.interleaved != 0, [&](auto v, auto inter) {
+            return run_separate<T, O, decltype(v)::value, decltype(u)::value, decltype(inter)::value>(in, g, ws, so, tmc, stream);
+        });
+    });
 }
 
 // sx_macenko_apply: ONE launch.  The pack is 16 bytes of output per lane and plane (run_transform's VR rule).  A work item is ONE pack
@@ -4182,7 +4120,7 @@ static int separate_typed(const void* images, const Geometry& g0, const Workspac
 template <typename O> constexpr int apply_sets() { return sizeof(O) == 1 ? 4 : 1; }
 template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
 static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    constexpr int VR = pack_for<O, V>();
     int sets = V == 1 ? 16 : apply_sets<O>();
 #ifdef SX_STAMPS      // diagnostic builds: pack sets per work item from the environment (tools/bench_apply.py --sets: A/B of the grid)
     if (const char* e = std::getenv("SX_APPLY_SETS")) {
@@ -4199,35 +4137,17 @@ static int run_apply(const T* images, O* out, int64_t n_tiles, ApplyArgs a, hipS
 // (kMask: sx_macenko_apply_masked -- planar tiles only; the mask's packs are as wide as the pixels', so its pointer has a say in `vec`)
 template <typename T, bool kMask = false>
 static int apply_typed(const void* images, void* out, int64_t n_tiles, const ApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    const bool u8_half = sizeof(T) == 1 && out_code != 0;
-    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
     constexpr int W = PackOf<T>::n;
     // (16-byte packs where both pointers allow them, as transform_typed decides; the scalar path otherwise)
-    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem * W);
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && aligned_for(out, out_elem_bytes(sizeof(T), out_code, unit) * W);
     if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
     const T* in = static_cast<const T*>(images);
-#define SX_RUN_APPLY(O, U)                                                                                                                                     \
-    if constexpr (kMask)                                                                                                                                       \
-        return vec ? run_apply<T, O, W, U, false, true>(in, static_cast<O*>(out), n_tiles, a, stream, mk) : run_apply<T, O, 1, U, false, true>(in, static_cast<O*>(out), n_tiles, a, stream, mk); \
-    else                                                                                                                                                       \
-    return interleaved ? (vec ? run_apply<T, O, W, U, true>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, true>(in, static_cast<O*>(out), n_tiles, a, stream)) \
-                       : (vec ? run_apply<T, O, W, U, false>(in, static_cast<O*>(out), n_tiles, a, stream) : run_apply<T, O, 1, U, false>(in, static_cast<O*>(out), n_tiles, a, stream));
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && out_code == SX_BF16) {
-            if (unit) { SX_RUN_APPLY(__hip_bfloat16, true) } else { SX_RUN_APPLY(__hip_bfloat16, false) }
-        }
-        if (u8_half) {
-            if (unit) { SX_RUN_APPLY(__half, true) } else { SX_RUN_APPLY(__half, false) }
-        }
-        if (u8_unit) {
-            SX_RUN_APPLY(float, true)
-        }
-        SX_RUN_APPLY(T, false)
-    } else {
-        if (unit) { SX_RUN_APPLY(T, true) } else { SX_RUN_APPLY(T, false) }
-    }
-#undef SX_RUN_APPLY
+    return with_out<T>(out_code, unit, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) {
+            return run_apply<T, O, decltype(v)::value, decltype(u)::value, decltype(inter)::value, kMask>(in, static_cast<O*>(out), n_tiles, a, stream, mk);
+        });
+    });
 }
 
 // sx_macenko_separate_apply: ONE launch.  The pack is run_separate's (16 bytes of output per lane and plane, sized by the images' element
@@ -4236,7 +4156,7 @@ static int apply_typed(const void* images, void* out, int64_t n_tiles, const App
 static int64_t separate_apply_chunk(int vr) { return (int64_t)kStreamThreads * vr * (vr == 1 ? 16 : 1); }
 template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
 static int run_separate_apply(const T* images, SeparateApplyArgs a, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
+    constexpr int VR = pack_for<O, V>();
     a.chunk = (int)separate_apply_chunk(VR);
     a.blocks = (int)((a.pixels + a.chunk - 1) / a.chunk);
     hipLaunchKernelGGL((separate_apply_kernel<T, O, VR, kUnit, kInter, kMask>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, images, a, mk);
@@ -4247,38 +4167,17 @@ static int run_separate_apply(const T* images, SeparateApplyArgs a, hipStream_t 
 template <typename T, bool kMask = false>
 static int separate_apply_typed(const void* images, const SeparateApplyArgs& a, int out_code, bool interleaved, bool unit, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
     const bool stains = a.stains != nullptr;
-    const bool u8_half = stains && sizeof(T) == 1 && out_code != 0;
-    const bool u8_unit = stains && unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = !stains ? sizeof(float) : (u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T)));
     constexpr int W = PackOf<T>::n;
     // (16-byte packs where every pointer allows them, as separate_typed decides; the scalar path otherwise)
-    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(a.stains, out_elem * W)) && (!a.conc || aligned_for(a.conc, 16));
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16) && (!stains || aligned_for(a.stains, out_elem_bytes(sizeof(T), out_code, unit) * W)) && (!a.conc || aligned_for(a.conc, 16));
     if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
     const T* in = static_cast<const T*>(images);
-#define SX_RUN_SEPA(O, U)                                                                                                                \
-    if constexpr (kMask)                                                                                                                 \
-        return vec ? run_separate_apply<T, O, W, U, false, true>(in, a, stream, mk) : run_separate_apply<T, O, 1, U, false, true>(in, a, stream, mk); \
-    else                                                                                                                                 \
-    return interleaved ? (vec ? run_separate_apply<T, O, W, U, true>(in, a, stream) : run_separate_apply<T, O, 1, U, true>(in, a, stream)) \
-                       : (vec ? run_separate_apply<T, O, W, U, false>(in, a, stream) : run_separate_apply<T, O, 1, U, false>(in, a, stream));
-    if (!stains) {
-        SX_RUN_SEPA(float, false)
-    }
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && out_code == SX_BF16) {
-            if (unit) { SX_RUN_SEPA(__hip_bfloat16, true) } else { SX_RUN_SEPA(__hip_bfloat16, false) }
-        }
-        if (u8_half) {
-            if (unit) { SX_RUN_SEPA(__half, true) } else { SX_RUN_SEPA(__half, false) }
-        }
-        if (u8_unit) {
-            SX_RUN_SEPA(float, true)
-        }
-        SX_RUN_SEPA(T, false)
-    } else {
-        if (unit) { SX_RUN_SEPA(T, true) } else { SX_RUN_SEPA(T, false) }
-    }
-#undef SX_RUN_SEPA
+    return with_out<T>(out_code, unit, stains, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) {
+            return run_separate_apply<T, O, decltype(v)::value, decltype(u)::value, decltype(inter)::value, kMask>(in, a, stream, mk);
+        });
+    });
 }
 
 // Where the masked separation and augmentation keep the source rows between their estimate and their one streaming launch: the head of
@@ -4299,10 +4198,9 @@ static int estimate_typed(const void* images, const Geometry& g0, const Workspac
     set_fine_chunk(g, vec ? W : 1);
     const T* in = static_cast<const T*>(images);
     // (no target: the scale stage leaves maxC in the tile's state and forms no scale)
-    const int rc = g.interleaved ? (vec ? run_estimate<T, W, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream)
-                                        : run_estimate<T, 1, true>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream))
-                                 : (vec ? run_estimate<T, W, false>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream)
-                                        : run_estimate<T, 1, false>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream));
+    const int rc = with_layout<W>(vec, g.interleaved != 0, [&](auto v, auto inter) {
+        return run_estimate<T, decltype(v)::value, decltype(inter)::value>(in, g, ws, (int)g.n_tiles, 1, nullptr, nullptr, nullptr, stream);
+    });
     if (rc != SX_OK) return rc;
     hipLaunchKernelGGL(export_estimate_kernel, dim3((unsigned)((g.n_tiles + 63) / 64)), dim3(64), 0, stream, ws.state, g.n_tiles, he_out, max_c_out, tissue_out);
     return check_launch("macenko export_estimate");
@@ -4357,14 +4255,10 @@ static int run_transform_masked(const T* images, O* out, const Geometry& g, cons
     const int rc = run_estimate<T, V, false, true>(images, g, ws, (int)g.n_tiles, 1, tmc, nullptr, nullptr, stream, mk);
     if (rc != SX_OK) return rc;
     // (run_transform's reconstruct grid: 16 bytes of output per lane and plane, one pack set per work item for big batches)
-    constexpr int VR = V == 1 ? 1 : ((int)(16 / sizeof(O)) < V ? (int)(16 / sizeof(O)) : V);
-    Geometry gr = g;
-    unsigned items_r = (unsigned)(g.n_tiles * (g.fine_chunk ? g.fine_blocks : g.blocks_per_tile));
-    if (!g.fine_chunk && V > 1 && g.n_tiles * g.pixels >= (1ll << 22)) {
-        gr.recon_chunk = kStreamThreads * VR;
-        gr.recon_blocks = (int)((g.pixels + gr.recon_chunk - 1) / gr.recon_chunk);
-        items_r = (unsigned)(g.n_tiles * gr.recon_blocks);
-    }
+    constexpr int VR = pack_for<O, V>();
+    const ReconGrid rg = recon_grid(g, VR);
+    const Geometry& gr = rg.g;
+    const unsigned items_r = rg.items;
     if (unit)
         hipLaunchKernelGGL((reconstruct_kernel<T, O, VR, true, false, false, true>), dim3(items_r), dim3(kStreamThreads), 0, stream, images, out, gr, ws, sm, mk);
     else
@@ -4375,22 +4269,16 @@ static int run_transform_masked(const T* images, O* out, const Geometry& g, cons
 template <typename T>
 static int transform_masked_typed(const void* images, void* out, const Geometry& g0, const Workspace& ws, const uint8_t* mask, const float* sm, const float* tmc, bool unit, hipStream_t stream) {
     Geometry g = g0;
-    const bool u8_half = sizeof(T) == 1 && g.out_code != 0;
-    const bool u8_unit = unit && sizeof(T) == 1 && !u8_half;
-    const size_t out_elem = u8_half ? 2 : (u8_unit ? sizeof(float) : sizeof(T));
     constexpr int W = PackOf<T>::n;
-    masked_geometry<T>(g, images, out, out_elem, mask, true);
+    masked_geometry<T>(g, images, out, out_elem_bytes(sizeof(T), g.out_code, unit), mask, true);
     const T* in = static_cast<const T*>(images);
     const MaskArgs<true> mk{mask};
-#define SX_RUN_MASKED(O) \
-    return g.vec ? run_transform_masked<T, O, W>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, mk, stream) : run_transform_masked<T, O, 1>(in, static_cast<O*>(out), g, ws, sm, tmc, unit, mk, stream);
-    if constexpr (sizeof(T) == 1) {
-        if (u8_half && g.out_code == SX_BF16) { SX_RUN_MASKED(__hip_bfloat16) }
-        if (u8_half) { SX_RUN_MASKED(__half) }
-        if (u8_unit) { SX_RUN_MASKED(float) }
-    }
-    SX_RUN_MASKED(T)
-#undef SX_RUN_MASKED
+    return with_out<T>(g.out_code, unit, [&](auto o, auto u) {
+        using O = typename decltype(o)::type;
+        return with_layout<W, true>(g.vec != 0, false, [&](auto v, auto) {
+            return run_transform_masked<T, O, decltype(v)::value>(in, static_cast<O*>(out), g, ws, sm, tmc, decltype(u)::value, mk, stream);
+        });
+    });
 }
 
 // sx_macenko_separate_masked / sx_macenko_augment_masked: the masked per-tile estimate (sx_macenko_estimate_masked's launches, with the
@@ -4701,8 +4589,7 @@ using namespace sx::macenko;
 
 static int validate_images(const void* images, int64_t n, int64_t h, int64_t w, const void* ws, size_t ws_bytes, size_t need) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    if (const int rc = check_tiles(n, h, w); rc != SX_OK) return rc;
     if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
     if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     return SX_OK;
@@ -4723,6 +4610,17 @@ static uint32_t next_code_epoch() {
     uint32_t e = counter.fetch_add(1u, std::memory_order_relaxed) + 1u;
     if (e == 0u) e = counter.fetch_add(1u, std::memory_order_relaxed) + 1u;
     return e;
+}
+// The workspace of a call that may run coded: where the call is a coded one and the buffer has the room (a workspace sized by an older
+// rule just runs without), the call gets its number and the codes lie behind the level of its form -- the four passes (0) or the
+// four-launch two-pass form (1), whose one pass over the input leaves them and whose reconstruct pass reads them; the fused launch never.
+static Workspace coded_setup(Geometry& g, int dtype, unsigned flags, void* ws_ptr, size_t ws_bytes, int form = 0) {
+    size_t codes_at = 0;
+    if ((form == 0 || form == 1) && coded_call(dtype, g.n_tiles, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(g.n_tiles, g.pixels, form)) {
+        g.code_epoch = next_code_epoch();
+        codes_at = macenko::workspace_bytes(g.n_tiles, g.pixels, form_level(form, g.pixels));
+    }
+    return carve(ws_ptr, g.n_tiles, g.pixels, codes_at);
 }
 
 extern "C" size_t sx_macenko_workspace_bytes(int64_t n_tiles, int64_t height, int64_t width) {
@@ -4792,8 +4690,7 @@ extern "C" int sx_macenko_transform(const void* images, void* out, int dtype, in
     int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, flags));
     if (rc != SX_OK) return rc;
     if (!out || !sm || !tmc) return fail(SX_ERR_BAD_ARG, "out / stain_matrix / target_max_conc pointer is null");
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    if ((rc = out_flags_ok(flags, dtype)) != SX_OK) return rc;
     Geometry g = make_geometry(n, h * w, 0);
     g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
     g.fast = (flags & SX_MACENKO_SAMPLED) ? 1 : 0;
@@ -4804,7 +4701,7 @@ extern "C" int sx_macenko_transform(const void* images, void* out, int dtype, in
     if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_SAMPLED | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
         return fail(SX_ERR_BAD_ARG, "flags 0x%x: bits outside the public set (the diagnostic flags need the diagnostic build, -DSX_DIAG)", flags);
 #endif
-    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    g.out_code = out_code_of(flags);
     int form = sx_macenko_form(dtype, n, h, w, flags);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
@@ -4816,25 +4713,12 @@ extern "C" int sx_macenko_transform(const void* images, void* out, int dtype, in
 #endif
     g.two_pass = form != 0 ? 1 : 0;
     g.fused = form == 2 ? 1 : 0;
-    // the four passes over a batch of float32 tiles: 8-bit codes behind the first pass (a workspace sized by an older rule just runs without)
-    // (the two-pass form: its one pass over the input leaves them, its reconstruct pass reads them)
-    size_t codes_at = 0;
-    if ((form == 0 || form == 1) && coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, form)) {
-        g.code_epoch = next_code_epoch();
-        codes_at = macenko::workspace_bytes(n, g.pixels, form_level(form, g.pixels));
-    }
+    // (the four passes over a batch of float32 tiles, and the four-launch two-pass form: 8-bit codes behind the first pass)
+    const Workspace ws = coded_setup(g, dtype, flags, ws_ptr, ws_bytes, form);
 #ifdef SX_DIAG
     if (flags & SX_MACENKO_NO_CODES) g.code_epoch = 0u;
 #endif
-    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
-    switch (dtype) {
-        case SX_U8: return transform_typed<uint8_t>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F16: return transform_typed<__half>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_BF16: return transform_typed<__hip_bfloat16>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F32: return transform_typed<float>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F64: return transform_typed<double>(images, out, g, ws, sm, tmc, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return transform_typed<typename decltype(t)::type>(images, out, g, ws, sm, tmc, unit, stream); });
 }
 
 // Stain augmentation: the four passes of the transform (own basis: stats, plane, angle bracket and stain stage only), the per-tile factors
@@ -4847,31 +4731,17 @@ extern "C" int sx_macenko_augment(const void* images, void* out, int dtype, int6
     if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise and jitter) or both null (own basis)");
     if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
         return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_augment takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    if ((rc = out_flags_ok(flags, dtype)) != SX_OK) return rc;
     Geometry g = make_geometry(n, h * w, 0);
     g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
-    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    g.out_code = out_code_of(flags);
     g.aug_alpha = alpha;
     g.aug_beta = beta;
     g.own_basis = sm == nullptr ? 1 : 0;
-    // (the codes of a float32 batch as in the transform's four passes)
-    size_t codes_at = 0;
-    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
-        g.code_epoch = next_code_epoch();
-        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
-    }
-    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    const Workspace ws = coded_setup(g, dtype, flags, ws_ptr, ws_bytes);      // (the codes of a float32 batch as in the transform's four passes)
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    switch (dtype) {
-        case SX_U8: return transform_typed<uint8_t>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F16: return transform_typed<__half>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_BF16: return transform_typed<__hip_bfloat16>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F32: return transform_typed<float>(images, out, g, ws, sm, tmc, unit, stream);
-        case SX_F64: return transform_typed<double>(images, out, g, ws, sm, tmc, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return transform_typed<typename decltype(t)::type>(images, out, g, ws, sm, tmc, unit, stream); });
 }
 
 // Stain separation: the four passes' per-tile estimate (own basis without maxC: stats, plane, angle bracket and stain stage only), then
@@ -4884,29 +4754,16 @@ extern "C" int sx_macenko_separate(const void* images, void* stains_out, float* 
     if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalised) or both null (own basis)");
     if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
         return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_separate takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    if ((rc = out_flags_ok(flags, dtype)) != SX_OK) return rc;
     Geometry g = make_geometry(n, h * w, 0);
     g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
-    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    g.out_code = out_code_of(flags);
     g.own_basis = (sm == nullptr && tile_max_c_out == nullptr) ? 1 : 0;      // (maxC asked for in own basis: the concentration bracket and the scale stage run, without a target)
-    size_t codes_at = 0;
-    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
-        g.code_epoch = next_code_epoch();
-        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
-    }
-    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    const Workspace ws = coded_setup(g, dtype, flags, ws_ptr, ws_bytes);
     const SeparateOut so{stains_out, conc_out, tile_he_out, tile_max_c_out, sm};
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    switch (dtype) {
-        case SX_U8: return separate_typed<uint8_t>(images, g, ws, so, tmc, unit, stream);
-        case SX_F16: return separate_typed<__half>(images, g, ws, so, tmc, unit, stream);
-        case SX_BF16: return separate_typed<__hip_bfloat16>(images, g, ws, so, tmc, unit, stream);
-        case SX_F32: return separate_typed<float>(images, g, ws, so, tmc, unit, stream);
-        case SX_F64: return separate_typed<double>(images, g, ws, so, tmc, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return separate_typed<typename decltype(t)::type>(images, g, ws, so, tmc, unit, stream); });
 }
 
 // The transform's per-tile estimate as a call of its own: the four passes' estimate (existing kernels), then HE_source, maxC and the
@@ -4920,40 +4777,29 @@ extern "C" int sx_macenko_estimate(const void* images, int dtype, int64_t n, int
     if (!tile_he_out || !tile_max_c_out) return fail(SX_ERR_BAD_ARG, "tile_he_out / tile_max_c_out pointer is null");
     Geometry g = make_geometry(n, h * w, 0);
     g.interleaved = (flags & SX_MACENKO_CHANNELS_LAST) ? 1 : 0;
-    // (the codes of a float32 batch as in the transform's four passes)
-    size_t codes_at = 0;
-    if (coded_call(dtype, n, g.pixels, flags) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
-        g.code_epoch = next_code_epoch();
-        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
-    }
-    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    const Workspace ws = coded_setup(g, dtype, flags, ws_ptr, ws_bytes);      // (the codes of a float32 batch as in the transform's four passes)
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return estimate_typed<uint8_t>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
-        case SX_F16: return estimate_typed<__half>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
-        case SX_BF16: return estimate_typed<__hip_bfloat16>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
-        case SX_F32: return estimate_typed<float>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
-        case SX_F64: return estimate_typed<double>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return estimate_typed<typename decltype(t)::type>(images, g, ws, tile_he_out, tile_max_c_out, tile_tissue_out, stream); });
 }
 
-// Normalise (and optionally jitter) with a GIVEN source basis: apply_kernel, one launch on `stream`, nothing else enqueued, no workspace.
-extern "C" int sx_macenko_apply(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c,
-                                int64_t n_sources, const float* alpha, const float* beta, const float* sm, const float* tmc, unsigned flags, void* stream_ptr) {
+// The argument checks sx_macenko_apply and its masked form share (everything but the flags; the mask: null in the unmasked call).
+static int apply_args_ok(const void* images, const void* out, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources, const float* alpha,
+                         const float* beta, const float* sm, const float* tmc, const unsigned char* mask_dev, bool masked) {
     if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    int rc = check_tiles(n, h, w);
+    if (rc != SX_OK) return rc;
+    if (masked && (rc = check_mask(mask_dev)) != SX_OK) return rc;
     if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
     if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
     if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise) or both null (own basis)");
     if ((alpha == nullptr) != (beta == nullptr)) return fail(SX_ERR_BAD_ARG, "alpha and beta: both given or both null");
     if (!sm && !alpha) return fail(SX_ERR_BAD_ARG, "own basis (no stain_matrix / target_max_conc) needs the factors alpha and beta: without them the call would rebuild its input");
     if (sm && !source_max_c) return fail(SX_ERR_BAD_ARG, "source_max_c pointer is null (it may be null in own-basis mode only)");
-    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
-        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_apply takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    return SX_OK;
+}
+
+static ApplyArgs apply_args(int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources, const float* alpha, const float* beta, const float* sm,
+                            const float* tmc) {
     ApplyArgs a{};
     a.he = source_he;
     a.max_c = source_max_c;
@@ -4963,18 +4809,26 @@ extern "C" int sx_macenko_apply(const void* images, void* out, int dtype, int64_
     a.tmc = tmc;
     a.pixels = h * w;
     a.per_tile = n_sources == n && n != 1 ? 1 : 0;
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    return a;
+}
+
+template <bool kMask>
+static int apply_dispatch(const void* images, void* out, int dtype, int64_t n, const ApplyArgs& a, unsigned flags, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    const int out_code = out_code_of(flags);
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return apply_typed<uint8_t>(images, out, n, a, out_code, inter, unit, stream);
-        case SX_F16: return apply_typed<__half>(images, out, n, a, out_code, inter, unit, stream);
-        case SX_BF16: return apply_typed<__hip_bfloat16>(images, out, n, a, out_code, inter, unit, stream);
-        case SX_F32: return apply_typed<float>(images, out, n, a, out_code, inter, unit, stream);
-        case SX_F64: return apply_typed<double>(images, out, n, a, out_code, inter, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return apply_typed<typename decltype(t)::type, kMask>(images, out, n, a, out_code, inter, unit, stream, mk); });
+}
+
+// Normalise (and optionally jitter) with a GIVEN source basis: apply_kernel, one launch on `stream`, nothing else enqueued, no workspace.
+extern "C" int sx_macenko_apply(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c,
+                                int64_t n_sources, const float* alpha, const float* beta, const float* sm, const float* tmc, unsigned flags, void* stream_ptr) {
+    int rc = apply_args_ok(images, out, n, h, w, source_he, source_max_c, n_sources, alpha, beta, sm, tmc, nullptr, false);
+    if (rc != SX_OK) return rc;
+    if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
+        return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_apply takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
+    if ((rc = out_flags_ok(flags, dtype)) != SX_OK) return rc;
+    return apply_dispatch<false>(images, out, dtype, n, apply_args(n, h, w, source_he, source_max_c, n_sources, alpha, beta, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr));
 }
 
 extern "C" int sx_macenko_fit(const void* images, int dtype, int64_t n, int64_t h, int64_t w, float* he_out, float* max_c_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
@@ -4983,21 +4837,9 @@ extern "C" int sx_macenko_fit(const void* images, int dtype, int64_t n, int64_t 
     if (!he_out || !max_c_out) return fail(SX_ERR_BAD_ARG, "he_out / max_c_out pointer is null");
     Geometry g = make_geometry(n, h * w, 1);
     // (a float32 batch: the moments pass leaves the tiles' 8-bit codes, the two bracket passes read them -- as in the transform's four passes)
-    size_t codes_at = 0;
-    if (coded_call(dtype, n, g.pixels, 0u) && ws_bytes >= coded_workspace_bytes(n, g.pixels, 0)) {
-        g.code_epoch = next_code_epoch();
-        codes_at = macenko::workspace_bytes(n, g.pixels, kWsBase);
-    }
-    const Workspace ws = carve(ws_ptr, n, g.pixels, codes_at);
+    const Workspace ws = coded_setup(g, dtype, 0u, ws_ptr, ws_bytes);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return fit_typed<uint8_t>(images, g, ws, he_out, max_c_out, stream);
-        case SX_F16: return fit_typed<__half>(images, g, ws, he_out, max_c_out, stream);
-        case SX_BF16: return fit_typed<__hip_bfloat16>(images, g, ws, he_out, max_c_out, stream);
-        case SX_F32: return fit_typed<float>(images, g, ws, he_out, max_c_out, stream);
-        case SX_F64: return fit_typed<double>(images, g, ws, he_out, max_c_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return fit_typed<typename decltype(t)::type>(images, g, ws, he_out, max_c_out, stream); });
 }
 
 // ---- tissue masks: the reference's algorithm on the masked-in pixels only, masked-out pixels copied (include/stainx_hip.h) ----
@@ -5007,96 +4849,59 @@ static int masked_flags_ok(unsigned flags, unsigned allowed, int dtype, const ch
     if (selects) allowed |= SX_MACENKO_NO_TIE_SHORTCUT;      // (the diagnostic build: the calls that select may be sent down their slow exact paths)
 #endif
     if (flags & ~allowed) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s runs the four passes over planar tiles (no SX_MACENKO_SAMPLED, no SX_MACENKO_CHANNELS_LAST) and takes the flags 0x%x only", flags, who, allowed);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
-    return SX_OK;
+    return out_flags_ok(flags, dtype);
+}
+constexpr unsigned kMaskedImageFlags = SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16;      // (the masked calls that write images)
+
+// What the masked calls with a workspace check first, in this order: flags, images / sizes / workspace, mask.
+static int masked_call_ok(unsigned flags, unsigned allowed, const char* who, const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, void* ws_ptr, size_t ws_bytes) {
+    int rc = masked_flags_ok(flags, allowed, dtype, who);
+    if (rc != SX_OK) return rc;
+    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
+    if (rc != SX_OK) return rc;
+    return check_mask(mask_dev);
+}
+// (their geometry: per tile or pooled, never coded)
+static Geometry masked_call_geometry(int64_t n, int64_t pixels, int pooled, unsigned flags) {
+    Geometry g = make_geometry(n, pixels, pooled);
+#ifdef SX_DIAG
+    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
+#endif
+    return g;
 }
 
 extern "C" int sx_macenko_estimate_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, int pooled, float* he_out, float* max_c_out, float* kept_out,
                                           unsigned long long* mask_counts_out, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
-    int rc = masked_flags_ok(flags, SX_MACENKO_CLASSIC, dtype, "sx_macenko_estimate_masked");
+    const int rc = masked_call_ok(flags, SX_MACENKO_CLASSIC, "sx_macenko_estimate_masked", images, dtype, n, h, w, mask_dev, ws_ptr, ws_bytes);
     if (rc != SX_OK) return rc;
-    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
-    if (rc != SX_OK) return rc;
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
     if (!he_out || !max_c_out) return fail(SX_ERR_BAD_ARG, "he_out / max_c_out pointer is null");
-    Geometry g = make_geometry(n, h * w, pooled ? 1 : 0);
-#ifdef SX_DIAG
-    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
-#endif
+    const Geometry g = masked_call_geometry(n, h * w, pooled ? 1 : 0, flags);
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return estimate_masked_typed<uint8_t>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
-        case SX_F16: return estimate_masked_typed<__half>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
-        case SX_BF16: return estimate_masked_typed<__hip_bfloat16>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
-        case SX_F32: return estimate_masked_typed<float>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
-        case SX_F64: return estimate_masked_typed<double>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return estimate_masked_typed<typename decltype(t)::type>(images, g, ws, mask_dev, he_out, max_c_out, kept_out, mask_counts_out, stream); });
 }
 
 extern "C" int sx_macenko_transform_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* sm, const float* tmc, unsigned flags,
                                            void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
-    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_transform_masked");
+    const int rc = masked_call_ok(flags, kMaskedImageFlags, "sx_macenko_transform_masked", images, dtype, n, h, w, mask_dev, ws_ptr, ws_bytes);
     if (rc != SX_OK) return rc;
-    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
-    if (rc != SX_OK) return rc;
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
     if (!out || !sm || !tmc) return fail(SX_ERR_BAD_ARG, "out / stain_matrix / target_max_conc pointer is null");
-    Geometry g = make_geometry(n, h * w, 0);
-#ifdef SX_DIAG
-    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
-#endif
-    g.out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    Geometry g = masked_call_geometry(n, h * w, 0, flags);
+    g.out_code = out_code_of(flags);
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    switch (dtype) {
-        case SX_U8: return transform_masked_typed<uint8_t>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
-        case SX_F16: return transform_masked_typed<__half>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
-        case SX_BF16: return transform_masked_typed<__hip_bfloat16>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
-        case SX_F32: return transform_masked_typed<float>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
-        case SX_F64: return transform_masked_typed<double>(images, out, g, ws, mask_dev, sm, tmc, unit, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return transform_masked_typed<typename decltype(t)::type>(images, out, g, ws, mask_dev, sm, tmc, unit, stream); });
 }
 
 extern "C" int sx_macenko_apply_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources,
                                        const float* alpha, const float* beta, const float* sm, const float* tmc, const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
-    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
-    if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
-    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
-    if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise) or both null (own basis)");
-    if ((alpha == nullptr) != (beta == nullptr)) return fail(SX_ERR_BAD_ARG, "alpha and beta: both given or both null");
-    if (!sm && !alpha) return fail(SX_ERR_BAD_ARG, "own basis (no stain_matrix / target_max_conc) needs the factors alpha and beta: without them the call would rebuild its input");
-    if (sm && !source_max_c) return fail(SX_ERR_BAD_ARG, "source_max_c pointer is null (it may be null in own-basis mode only)");
-    const int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_apply_masked", false);
+    int rc = apply_args_ok(images, out, n, h, w, source_he, source_max_c, n_sources, alpha, beta, sm, tmc, mask_dev, true);
     if (rc != SX_OK) return rc;
-    ApplyArgs a{};
-    a.he = source_he;
-    a.max_c = source_max_c;
-    a.alpha = alpha;
-    a.beta = beta;
-    a.sm = sm;
-    a.tmc = tmc;
-    a.pixels = h * w;
-    a.per_tile = n_sources == n && n != 1 ? 1 : 0;
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
-    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const MaskArgs<true> mk{mask_dev};
-    switch (dtype) {
-        case SX_U8: return apply_typed<uint8_t, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_F16: return apply_typed<__half, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_BF16: return apply_typed<__hip_bfloat16, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_F32: return apply_typed<float, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_F64: return apply_typed<double, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    rc = masked_flags_ok(flags, kMaskedImageFlags, dtype, "sx_macenko_apply_masked", false);
+    if (rc != SX_OK) return rc;
+    return apply_dispatch<true>(images, out, dtype, n, apply_args(n, h, w, source_he, source_max_c, n_sources, alpha, beta, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr),
+                                MaskArgs<true>{mask_dev});
 }
 
 // ---- separation and augmentation: given source basis, tissue masks ----
@@ -5104,8 +4909,7 @@ extern "C" int sx_macenko_apply_masked(const void* images, void* out, int dtype,
 static int separate_apply_args_ok(const void* images, const void* stains_out, const float* conc_out, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c,
                                   int64_t n_sources, const float* sm, const float* tmc) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    if (const int rc = check_tiles(n, h, w); rc != SX_OK) return rc;
     if (!stains_out && !conc_out) return fail(SX_ERR_BAD_ARG, "stains_out and conc_out are both null: nothing to separate into");
     if (!source_he) return fail(SX_ERR_BAD_ARG, "source_he pointer is null");
     if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 (one basis for the batch) or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
@@ -5116,17 +4920,10 @@ static int separate_apply_args_ok(const void* images, const void* stains_out, co
 
 template <bool kMask>
 static int separate_apply_dispatch(const void* images, int dtype, const SeparateApplyArgs& a, unsigned flags, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
+    const int out_code = out_code_of(flags);
     const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
     const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    switch (dtype) {
-        case SX_U8: return separate_apply_typed<uint8_t, kMask>(images, a, out_code, inter, unit, stream, mk);
-        case SX_F16: return separate_apply_typed<__half, kMask>(images, a, out_code, inter, unit, stream, mk);
-        case SX_BF16: return separate_apply_typed<__hip_bfloat16, kMask>(images, a, out_code, inter, unit, stream, mk);
-        case SX_F32: return separate_apply_typed<float, kMask>(images, a, out_code, inter, unit, stream, mk);
-        case SX_F64: return separate_apply_typed<double, kMask>(images, a, out_code, inter, unit, stream, mk);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return separate_apply_typed<typename decltype(t)::type, kMask>(images, a, out_code, inter, unit, stream, mk); });
 }
 
 static SeparateApplyArgs separate_apply_args(void* stains_out, float* conc_out, int64_t n, int64_t h, int64_t w, const float* source_he, const float* source_max_c, int64_t n_sources,
@@ -5147,12 +4944,11 @@ static SeparateApplyArgs separate_apply_args(void* stains_out, float* conc_out, 
 // Separate with a GIVEN source basis: separate_apply_kernel, one launch on `stream`, nothing else enqueued, no workspace.
 extern "C" int sx_macenko_separate_apply(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_he,
                                          const float* source_max_c, int64_t n_sources, const float* sm, const float* tmc, unsigned flags, void* stream_ptr) {
-    const int rc = separate_apply_args_ok(images, stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc);
+    int rc = separate_apply_args_ok(images, stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc);
     if (rc != SX_OK) return rc;
     if (flags & ~(SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16))
         return fail(SX_ERR_BAD_ARG, "flags 0x%x: sx_macenko_separate_apply takes SX_MACENKO_NORMALIZE_0_1, _CHANNELS_LAST, _CLASSIC, _OUT_BF16 and _OUT_F16 only", flags);
-    if ((flags & (SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16)) != 0 && (dtype != SX_U8 || (flags & SX_MACENKO_OUT_BF16 && flags & SX_MACENKO_OUT_F16)))
-        return fail(SX_ERR_BAD_ARG, "SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16: uint8 input only, one of the two");
+    if ((rc = out_flags_ok(flags, dtype)) != SX_OK) return rc;
     return separate_apply_dispatch<false>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr));
 }
 
@@ -5161,45 +4957,35 @@ extern "C" int sx_macenko_separate_apply_masked(const void* images, void* stains
                                                 void* stream_ptr) {
     int rc = separate_apply_args_ok(images, stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc);
     if (rc != SX_OK) return rc;
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
-    rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_separate_apply_masked", false);
+    if ((rc = check_mask(mask_dev)) != SX_OK) return rc;
+    rc = masked_flags_ok(flags, kMaskedImageFlags, dtype, "sx_macenko_separate_apply_masked", false);
     if (rc != SX_OK) return rc;
     return separate_apply_dispatch<true>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, source_he, source_max_c, n_sources, sm, tmc), flags, static_cast<hipStream_t>(stream_ptr),
                                          MaskArgs<true>{mask_dev});
+}
+
+// The masked per-tile estimate of sx_macenko_separate_masked / sx_macenko_augment_masked, with the estimate's packs as the output pass's:
+// 16-byte packs where every pointer of the call allows them (outs_ok: the call's output pointers).
+static int estimate_rows_masked_call(const void* images, int dtype, const Geometry& g, const Workspace& ws, const unsigned char* mask_dev, bool outs_ok, float* he_b, float* max_c_b, hipStream_t stream) {
+    return with_dtype(dtype, [&](auto t) { return estimate_rows_masked<typename decltype(t)::type>(images, g, ws, mask_dev, outs_ok, he_b, max_c_b, stream); });
 }
 
 // sx_macenko_separate with a tissue mask: the masked per-tile estimate, its rows exported (to the caller's tile_he_out / tile_max_c_out as
 // well), then separate_apply_kernel<kMask> over them: what sx_macenko_estimate_masked followed by sx_macenko_separate_apply_masked runs.
 extern "C" int sx_macenko_separate_masked(const void* images, void* stains_out, float* conc_out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* sm,
                                           const float* tmc, float* tile_he_out, float* tile_max_c_out, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
-    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_separate_masked");
+    int rc = masked_call_ok(flags, kMaskedImageFlags, "sx_macenko_separate_masked", images, dtype, n, h, w, mask_dev, ws_ptr, ws_bytes);
     if (rc != SX_OK) return rc;
-    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
-    if (rc != SX_OK) return rc;
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
     if (!stains_out && !conc_out) return fail(SX_ERR_BAD_ARG, "stains_out and conc_out are both null: nothing to separate into");
     if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalised) or both null (own basis)");
-    Geometry g = make_geometry(n, h * w, 0);
-#ifdef SX_DIAG
-    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
-#endif
+    Geometry g = masked_call_geometry(n, h * w, 0, flags);
     g.own_basis = (sm == nullptr && tile_max_c_out == nullptr) ? 1 : 0;      // (as sx_macenko_separate: maxC asked for in own basis runs the whole estimate)
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    // (the estimate's packs as the separation's: 16-byte packs where every pointer of the call allows them)
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
-    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    const int in_elem = dtype == SX_U8 ? 1 : (dtype == SX_F16 || dtype == SX_BF16) ? 2 : dtype == SX_F32 ? 4 : 8;
-    const size_t out_elem = (dtype == SX_U8 && out_code != 0) ? 2 : ((dtype == SX_U8 && unit) ? sizeof(float) : (size_t)in_elem);
+    const int in_elem = elem_bytes(dtype);
+    const size_t out_elem = out_elem_bytes(in_elem, out_code_of(flags), (flags & SX_MACENKO_NORMALIZE_0_1) != 0);
     const bool outs_ok = (!stains_out || aligned_for(stains_out, out_elem * (16 / in_elem))) && (!conc_out || aligned_for(conc_out, 16));
-    switch (dtype) {
-        case SX_U8: rc = estimate_rows_masked<uint8_t>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
-        case SX_F16: rc = estimate_rows_masked<__half>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
-        case SX_BF16: rc = estimate_rows_masked<__hip_bfloat16>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
-        case SX_F32: rc = estimate_rows_masked<float>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
-        case SX_F64: rc = estimate_rows_masked<double>(images, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream); break;
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    rc = estimate_rows_masked_call(images, dtype, g, ws, mask_dev, outs_ok, tile_he_out, tile_max_c_out, stream);
     if (rc != SX_OK) return rc;
     const float* rows = workspace_rows(ws);
     return separate_apply_dispatch<true>(images, dtype, separate_apply_args(stains_out, conc_out, n, h, w, rows, rows + 6 * n, n, sm, tmc), flags & ~SX_MACENKO_CLASSIC, stream, MaskArgs<true>{mask_dev});
@@ -5210,52 +4996,21 @@ extern "C" int sx_macenko_separate_masked(const void* images, void* stains_out, 
 // copied by sx_macenko_transform_masked's background rule.
 extern "C" int sx_macenko_augment_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask_dev, const float* alpha, const float* beta,
                                          const float* sm, const float* tmc, unsigned flags, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
-    int rc = masked_flags_ok(flags, SX_MACENKO_NORMALIZE_0_1 | SX_MACENKO_CLASSIC | SX_MACENKO_OUT_BF16 | SX_MACENKO_OUT_F16, dtype, "sx_macenko_augment_masked");
+    int rc = masked_call_ok(flags, kMaskedImageFlags, "sx_macenko_augment_masked", images, dtype, n, h, w, mask_dev, ws_ptr, ws_bytes);
     if (rc != SX_OK) return rc;
-    rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, sx_macenko_workspace_bytes_for(dtype, n, h, w, SX_MACENKO_CLASSIC));
-    if (rc != SX_OK) return rc;
-    if (!mask_dev) return fail(SX_ERR_BAD_ARG, "mask pointer is null (the masked calls take explicit masks: one byte per pixel, (N, H, W))");
     if (!out || !alpha || !beta) return fail(SX_ERR_BAD_ARG, "out / alpha / beta pointer is null");
     if ((sm == nullptr) != (tmc == nullptr)) return fail(SX_ERR_BAD_ARG, "stain_matrix and target_max_conc: both given (normalise and jitter) or both null (own basis)");
-    Geometry g = make_geometry(n, h * w, 0);
-#ifdef SX_DIAG
-    g.no_tie = (flags & SX_MACENKO_NO_TIE_SHORTCUT) ? 1 : 0;
-#endif
+    Geometry g = masked_call_geometry(n, h * w, 0, flags);
     g.own_basis = sm == nullptr ? 1 : 0;
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const int out_code = (flags & SX_MACENKO_OUT_BF16) ? SX_BF16 : ((flags & SX_MACENKO_OUT_F16) ? SX_F16 : 0);
-    const bool unit = (flags & SX_MACENKO_NORMALIZE_0_1) != 0;
-    const int in_elem = dtype == SX_U8 ? 1 : (dtype == SX_F16 || dtype == SX_BF16) ? 2 : dtype == SX_F32 ? 4 : 8;
-    const size_t out_elem = (dtype == SX_U8 && out_code != 0) ? 2 : ((dtype == SX_U8 && unit) ? sizeof(float) : (size_t)in_elem);
+    const int in_elem = elem_bytes(dtype);
+    const size_t out_elem = out_elem_bytes(in_elem, out_code_of(flags), (flags & SX_MACENKO_NORMALIZE_0_1) != 0);
     const bool outs_ok = aligned_for(out, out_elem * (16 / in_elem));      // (the estimate's packs as sx_macenko_transform_masked decides them)
-    switch (dtype) {
-        case SX_U8: rc = estimate_rows_masked<uint8_t>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
-        case SX_F16: rc = estimate_rows_masked<__half>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
-        case SX_BF16: rc = estimate_rows_masked<__hip_bfloat16>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
-        case SX_F32: rc = estimate_rows_masked<float>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
-        case SX_F64: rc = estimate_rows_masked<double>(images, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream); break;
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    rc = estimate_rows_masked_call(images, dtype, g, ws, mask_dev, outs_ok, nullptr, nullptr, stream);      // (refuses a dtype code outside the five)
     if (rc != SX_OK) return rc;
     const float* rows = workspace_rows(ws);
-    ApplyArgs a{};
-    a.he = rows;
-    a.max_c = rows + 6 * n;
-    a.alpha = alpha;
-    a.beta = beta;
-    a.sm = sm;
-    a.tmc = tmc;
-    a.pixels = h * w;
-    a.per_tile = n != 1 ? 1 : 0;
-    const MaskArgs<true> mk{mask_dev};
-    switch (dtype) {
-        case SX_U8: return apply_typed<uint8_t, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_F16: return apply_typed<__half, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_BF16: return apply_typed<__hip_bfloat16, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        case SX_F32: return apply_typed<float, true>(images, out, n, a, out_code, false, unit, stream, mk);
-        default: return apply_typed<double, true>(images, out, n, a, out_code, false, unit, stream, mk);
-    }
+    return apply_dispatch<true>(images, out, dtype, n, apply_args(n, h, w, rows, rows + 6 * n, n, alpha, beta, sm, tmc), flags, stream, MaskArgs<true>{mask_dev});
 }
 
 extern "C" int sx_macenko_tile_params(const void* ws_ptr, int64_t n_groups, float* params_out, void* stream_ptr) {
@@ -5285,14 +5040,7 @@ extern "C" int sx_macenko_dfit_moments(const void* images, int dtype, int64_t n,
     Geometry g = make_geometry(n, h * w, 1);
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return dfit_moments_typed<uint8_t>(images, g, ws, moments_out, stream);
-        case SX_F16: return dfit_moments_typed<__half>(images, g, ws, moments_out, stream);
-        case SX_BF16: return dfit_moments_typed<__hip_bfloat16>(images, g, ws, moments_out, stream);
-        case SX_F32: return dfit_moments_typed<float>(images, g, ws, moments_out, stream);
-        case SX_F64: return dfit_moments_typed<double>(images, g, ws, moments_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return dfit_moments_typed<typename decltype(t)::type>(images, g, ws, moments_out, stream); });
 }
 
 extern "C" int sx_macenko_dfit_begin(const double* moments, void* state, void* stream_ptr) {
@@ -5307,14 +5055,7 @@ extern "C" int sx_macenko_dfit_histogram(const void* images, int dtype, int64_t 
     Geometry g = make_geometry(n, h * w, 1);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const DFitState* st = static_cast<const DFitState*>(state);
-    switch (dtype) {
-        case SX_U8: return dfit_histogram_typed<uint8_t>(images, g, st, stage, hist_out, stream);
-        case SX_F16: return dfit_histogram_typed<__half>(images, g, st, stage, hist_out, stream);
-        case SX_BF16: return dfit_histogram_typed<__hip_bfloat16>(images, g, st, stage, hist_out, stream);
-        case SX_F32: return dfit_histogram_typed<float>(images, g, st, stage, hist_out, stream);
-        case SX_F64: return dfit_histogram_typed<double>(images, g, st, stage, hist_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return dfit_histogram_typed<typename decltype(t)::type>(images, g, st, stage, hist_out, stream); });
 }
 
 extern "C" int sx_macenko_dfit_advance(void* state, int stage, const unsigned long long* hist, void* stream_ptr) {
@@ -5351,24 +5092,24 @@ extern "C" int sx_macenko_pfit_sample_count(int64_t n, int64_t h, int64_t w) {
     return g.sample_count;
 }
 
-extern "C" int sx_macenko_pfit_stats(const void* images, int dtype, int64_t n, int64_t h, int64_t w, double* moments_out, float* sample_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
-    int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, macenko::workspace_bytes(n, h * w, kWsBase));
-    if (rc != SX_OK) return rc;
-    if (!moments_out || !sample_out) return fail(SX_ERR_BAD_ARG, "moments_out / sample_out pointer is null");
+// sx_macenko_pfit_stats and its packed form: the stats pass, then the moments and the sample copied out (tiles_out: the packed record's
+// leading tile count, null for the unpacked call).
+static int pfit_stats_call(const void* images, int dtype, int64_t n, int64_t h, int64_t w, double* moments_out, float* sample_out, long long* tiles_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr,
+                           const char* what) {
     const Geometry g = pfit_geometry(n, h, w, 0, -1);
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: rc = pfit_pass_typed<uint8_t>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F16: rc = pfit_pass_typed<__half>(images, g, ws, -1, nullptr, stream); break;
-        case SX_BF16: rc = pfit_pass_typed<__hip_bfloat16>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F32: rc = pfit_pass_typed<float>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F64: rc = pfit_pass_typed<double>(images, g, ws, -1, nullptr, stream); break;
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    const int rc = with_dtype(dtype, [&](auto t) { return pfit_pass_typed<typename decltype(t)::type>(images, g, ws, -1, nullptr, stream); });
     if (rc != SX_OK) return rc;
-    hipLaunchKernelGGL(pfit_export_stats_kernel, dim3(13), dim3(256), 0, stream, ws, (int64_t)(g.n_tiles * g.blocks_per_tile), moments_out, sample_out);
-    return check_launch("macenko pfit stats export");
+    hipLaunchKernelGGL(pfit_export_stats_kernel, dim3(13), dim3(256), 0, stream, ws, (int64_t)(g.n_tiles * g.blocks_per_tile), moments_out, sample_out, tiles_out, tiles_out ? (long long)n : 0ll);
+    return check_launch(what);
+}
+
+extern "C" int sx_macenko_pfit_stats(const void* images, int dtype, int64_t n, int64_t h, int64_t w, double* moments_out, float* sample_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
+    const int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, macenko::workspace_bytes(n, h * w, kWsBase));
+    if (rc != SX_OK) return rc;
+    if (!moments_out || !sample_out) return fail(SX_ERR_BAD_ARG, "moments_out / sample_out pointer is null");
+    return pfit_stats_call(images, dtype, n, h, w, moments_out, sample_out, nullptr, ws_ptr, ws_bytes, stream_ptr, "macenko pfit stats export");
 }
 
 extern "C" int sx_macenko_pfit_plane(const double* moments, long long n_all, const float* sample_union, int sample_count, int64_t n, int64_t h, int64_t w, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
@@ -5386,23 +5127,10 @@ extern "C" int sx_macenko_pfit_plane(const double* moments, long long n_all, con
 extern "C" int sx_macenko_pfit_stats_packed(const void* images, int dtype, int64_t n, int64_t h, int64_t w, void* record_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {
     if (!record_out || reinterpret_cast<uintptr_t>(record_out) % 8 != 0) return fail(SX_ERR_BAD_ARG, "record_out is null or not 8-byte aligned");
     unsigned char* rec = static_cast<unsigned char*>(record_out);
-    int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, macenko::workspace_bytes(n, h * w, kWsBase));
+    const int rc = validate_images(images, n, h, w, ws_ptr, ws_bytes, macenko::workspace_bytes(n, h * w, kWsBase));
     if (rc != SX_OK) return rc;
-    const Geometry g = pfit_geometry(n, h, w, 0, -1);
-    const Workspace ws = carve(ws_ptr, n, g.pixels);
-    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: rc = pfit_pass_typed<uint8_t>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F16: rc = pfit_pass_typed<__half>(images, g, ws, -1, nullptr, stream); break;
-        case SX_BF16: rc = pfit_pass_typed<__hip_bfloat16>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F32: rc = pfit_pass_typed<float>(images, g, ws, -1, nullptr, stream); break;
-        case SX_F64: rc = pfit_pass_typed<double>(images, g, ws, -1, nullptr, stream); break;
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
-    if (rc != SX_OK) return rc;
-    hipLaunchKernelGGL(pfit_export_stats_kernel, dim3(13), dim3(256), 0, stream, ws, (int64_t)(g.n_tiles * g.blocks_per_tile), reinterpret_cast<double*>(rec + 8),
-                       reinterpret_cast<float*>(rec + 8 + 8 * kPartial), reinterpret_cast<long long*>(rec), (long long)n);
-    return check_launch("macenko pfit stats export (packed)");
+    return pfit_stats_call(images, dtype, n, h, w, reinterpret_cast<double*>(rec + 8), reinterpret_cast<float*>(rec + 8 + 8 * kPartial), reinterpret_cast<long long*>(rec), ws_ptr, ws_bytes, stream_ptr,
+                           "macenko pfit stats export (packed)");
 }
 
 extern "C" int sx_macenko_pfit_plane_packed(const void* gathered, int world, const int* sample_counts_host, const long long* expected_tiles, int* stale_out, long long n_all, int sample_count, int64_t n, int64_t h,
@@ -5461,14 +5189,7 @@ extern "C" int sx_macenko_pfit_pass(const void* images, int dtype, int64_t n, in
     const Geometry g = pfit_geometry(n, h, w, n_all, sample_count);
     const Workspace ws = carve(ws_ptr, n, g.pixels);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return pfit_pass_typed<uint8_t>(images, g, ws, stage, sums_out, stream);
-        case SX_F16: return pfit_pass_typed<__half>(images, g, ws, stage, sums_out, stream);
-        case SX_BF16: return pfit_pass_typed<__hip_bfloat16>(images, g, ws, stage, sums_out, stream);
-        case SX_F32: return pfit_pass_typed<float>(images, g, ws, stage, sums_out, stream);
-        case SX_F64: return pfit_pass_typed<double>(images, g, ws, stage, sums_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return pfit_pass_typed<typename decltype(t)::type>(images, g, ws, stage, sums_out, stream); });
 }
 
 extern "C" int sx_macenko_pfit_gather(const long long* sums_global, int stage, long long n_all, int sample_count, int64_t n, int64_t h, int64_t w, int share, unsigned* compact_out, int* counts_out, void* ws_ptr, size_t ws_bytes, void* stream_ptr) {

@@ -9,6 +9,7 @@
 // LAB is recomputed in pass 2 instead of being stored: 24 VALU-cheap transcendentals per pixel are
 // cheaper than a 12 B/px round trip through HBM.
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "tissue.hpp"
 #include <algorithm>
 #include <atomic>
@@ -653,14 +654,7 @@ static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t
     if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
     if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return run<uint8_t>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready);
-        case SX_F16: return run<__half>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready);
-        case SX_BF16: return run<__hip_bfloat16>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready);
-        case SX_F32: return run<float>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready);
-        case SX_F64: return run<double>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return run<typename decltype(t)::type>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready); });
 }
 
 // ---- per-tile statistics, given statistics ------------------------------------------------------------------------------------------
@@ -965,14 +959,7 @@ extern "C" int sx_reinhard_apply_stats(const void* images, void* out, int dtype,
     if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const int per_tile = n_sources == n && n != 1 ? 1 : 0;
-    switch (dtype) {
-        case SX_U8: return reinhard::run_apply_stats<uint8_t>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
-        case SX_F16: return reinhard::run_apply_stats<__half>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
-        case SX_BF16: return reinhard::run_apply_stats<__hip_bfloat16>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
-        case SX_F32: return reinhard::run_apply_stats<float>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
-        case SX_F64: return reinhard::run_apply_stats<double>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_stats<typename decltype(t)::type>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream); });
 }
 
 // ---- tissue masks (an extension: HistomicsTK's reinhard(mask_out=), staintools' LuminosityThresholdTissueLocator) ------------------------------
@@ -984,14 +971,7 @@ extern "C" int sx_tissue_mask(const void* images, int dtype, int64_t n, int64_t 
     if (!tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const float y_cut = tissue::y_cut_of(luminosity_threshold);
-    switch (dtype) {
-        case SX_U8: return reinhard::run_tissue_mask<uint8_t>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
-        case SX_F16: return reinhard::run_tissue_mask<__half>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
-        case SX_BF16: return reinhard::run_tissue_mask<__hip_bfloat16>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
-        case SX_F32: return reinhard::run_tissue_mask<float>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
-        case SX_F64: return reinhard::run_tissue_mask<double>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return reinhard::run_tissue_mask<typename decltype(t)::type>(images, n, h, w, channels_last, y_cut, mask_out, tile_counts_out, stream); });
 }
 
 extern "C" size_t sx_reinhard_masked_workspace_bytes(int dtype, int64_t n, int64_t h, int64_t w) {
@@ -1020,14 +1000,7 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     const int per_tile = n_sources == n && n != 1 ? 1 : 0;
     const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(luminosity_threshold)};
-    switch (dtype) {
-        case SX_U8: return reinhard::run_apply_stats_masked<uint8_t>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
-        case SX_F16: return reinhard::run_apply_stats_masked<__half>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
-        case SX_BF16: return reinhard::run_apply_stats_masked<__hip_bfloat16>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
-        case SX_F32: return reinhard::run_apply_stats_masked<float>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
-        case SX_F64: return reinhard::run_apply_stats_masked<double>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_stats_masked<typename decltype(t)::type>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream); });
 }
 
 // ---- tissue detection: luminosity histograms (for Otsu thresholds), per-tile cuts, binary morphology on masks ------------------------------

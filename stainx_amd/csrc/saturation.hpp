@@ -257,14 +257,7 @@ extern "C" int sx_saturation_map(const void* images, int dtype, int64_t n, int64
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes");
     if (n > 0x7fffffffll / detect::kBlocksPerTile) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return saturation::run_saturation_map<uint8_t>(images, n, h, w, channels_last, levels_out, stream);
-        case SX_F16: return saturation::run_saturation_map<__half>(images, n, h, w, channels_last, levels_out, stream);
-        case SX_BF16: return saturation::run_saturation_map<__hip_bfloat16>(images, n, h, w, channels_last, levels_out, stream);
-        case SX_F32: return saturation::run_saturation_map<float>(images, n, h, w, channels_last, levels_out, stream);
-        case SX_F64: return saturation::run_saturation_map<double>(images, n, h, w, channels_last, levels_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return saturation::run_saturation_map<typename decltype(t)::type>(images, n, h, w, channels_last, levels_out, stream); });
 }
 
 extern "C" int sx_median_filter_u8(const uint8_t* levels_in, uint8_t* levels_out, int64_t n, int64_t h, int64_t w, int size, void* stream_ptr) {

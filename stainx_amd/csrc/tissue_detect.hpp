@@ -287,14 +287,7 @@ extern "C" int sx_luminosity_histogram(const void* images, int dtype, int64_t n,
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes");
     if (n > 0x7fffffffll / detect::kBlocksPerTile) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return detect::run_histogram<uint8_t>(images, n, h, w, channels_last, pooled != 0, counts_out, stream);
-        case SX_F16: return detect::run_histogram<__half>(images, n, h, w, channels_last, pooled != 0, counts_out, stream);
-        case SX_BF16: return detect::run_histogram<__hip_bfloat16>(images, n, h, w, channels_last, pooled != 0, counts_out, stream);
-        case SX_F32: return detect::run_histogram<float>(images, n, h, w, channels_last, pooled != 0, counts_out, stream);
-        case SX_F64: return detect::run_histogram<double>(images, n, h, w, channels_last, pooled != 0, counts_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return detect::run_histogram<typename decltype(t)::type>(images, n, h, w, channels_last, pooled != 0, counts_out, stream); });
 }
 
 extern "C" int sx_tissue_mask_tiles(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* tile_y_cut, uint8_t* mask_out, unsigned long long* tile_counts_out, void* stream_ptr) {
@@ -305,14 +298,7 @@ extern "C" int sx_tissue_mask_tiles(const void* images, int dtype, int64_t n, in
     if (n > 0x7fffffffll / detect::kBlocksPerTile) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
     if (!tile_y_cut) return fail(SX_ERR_BAD_ARG, "tile_y_cut pointer is null");
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return detect::run_mask_tiles<uint8_t>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream);
-        case SX_F16: return detect::run_mask_tiles<__half>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream);
-        case SX_BF16: return detect::run_mask_tiles<__hip_bfloat16>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream);
-        case SX_F32: return detect::run_mask_tiles<float>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream);
-        case SX_F64: return detect::run_mask_tiles<double>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream);
-        default: return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    }
+    return with_dtype(dtype, [&](auto t) { return detect::run_mask_tiles<typename decltype(t)::type>(images, n, h, w, channels_last, tile_y_cut, mask_out, tile_counts_out, stream); });
 }
 
 extern "C" int sx_mask_morphology(const uint8_t* mask_in, uint8_t* mask_out, int64_t n, int64_t h, int64_t w, int op, int element, int radius, uint8_t* scratch, unsigned long long* tile_counts_out, void* stream_ptr) {

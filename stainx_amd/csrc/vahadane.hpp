@@ -423,14 +423,7 @@ static void maxc_typed(const Call& c, const MaxcArgs& a, float* max_c_out, unsig
     }
 }
 
-static int pack_width(int dtype) {
-    switch (dtype) {
-        case SX_U8: return 16;
-        case SX_F16: case SX_BF16: return 8;
-        case SX_F32: return 4;
-        default: return 2;
-    }
-}
+static int pack_width(int dtype) { return 16 / elem_bytes(dtype); }
 
 // What both entry points check about the images, the mask, the flags and the workspace; fills `c`.  Nothing is enqueued.
 static int prepare(const char* who, const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned char* mask, int pooled, unsigned flags, const void* ws, size_t ws_bytes, void* stream,
@@ -471,13 +464,7 @@ static int enqueue_maxc(const Call& c, const Layout& l, void* ws, const float* h
     a.pooled = c.pooled;
     a.per_row = per_row;
     if (hipMemsetAsync(a.hist, 0, sizeof(unsigned long long) * 2 * kBinsAll * rows, c.stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
-    switch (c.dtype) {
-        case SX_U8: maxc_typed<uint8_t>(c, a, max_c_out, pixels_out); break;
-        case SX_F16: maxc_typed<__half>(c, a, max_c_out, pixels_out); break;
-        case SX_BF16: maxc_typed<__hip_bfloat16>(c, a, max_c_out, pixels_out); break;
-        case SX_F32: maxc_typed<float>(c, a, max_c_out, pixels_out); break;
-        default: maxc_typed<double>(c, a, max_c_out, pixels_out); break;
-    }
+    with_dtype(c.dtype, [&](auto t) { return maxc_typed<typename decltype(t)::type>(c, a, max_c_out, pixels_out), (int)SX_OK; });      // (prepare() has checked the code)
     return check_launch("stain max concentrations");
 }
 
@@ -514,13 +501,7 @@ extern "C" int sx_vahadane_estimate(const void* images, int dtype, int64_t n, in
     a.pooled = c.pooled;
     a.init_per_row = n_init != 1 ? 1 : 0;
     a.lambda = (float)lambda;
-    switch (dtype) {
-        case SX_U8: rounds_typed<uint8_t>(c, a, iterations, he_out, pixels_out); break;
-        case SX_F16: rounds_typed<__half>(c, a, iterations, he_out, pixels_out); break;
-        case SX_BF16: rounds_typed<__hip_bfloat16>(c, a, iterations, he_out, pixels_out); break;
-        case SX_F32: rounds_typed<float>(c, a, iterations, he_out, pixels_out); break;
-        default: rounds_typed<double>(c, a, iterations, he_out, pixels_out); break;
-    }
+    with_dtype(dtype, [&](auto t) { return rounds_typed<typename decltype(t)::type>(c, a, iterations, he_out, pixels_out), (int)SX_OK; });      // (prepare() has checked the code)
     rc = check_launch("vahadane estimate");
     if (rc != SX_OK || !max_c_out) return rc;
     return enqueue_maxc(c, l, ws_ptr, he_out, 1, max_c_out, nullptr);
