@@ -872,7 +872,9 @@ int sx_stain_max_concentrations(const void* images_dev, int dtype, int64_t n_til
  * 7.787 Y_p + 16/116, L_p = 116 f_p - 16, g = 100 / L_p.  Per pixel, in float32, with (f_x, f_y, f_z) of the LAB conversion:
  * f_y' = min(g f_y + (16/116)(1 - g), 1), f_x' = f_y' + (f_x - f_y), f_z' = f_y' - (f_y - f_z), and back to sRGB as
  * sx_reinhard_apply_stats goes: L*' = min(100 L* / L_p, 100), a* and b* unchanged, nothing quantised on the way.  A row that is NaN or
- * gives L_p <= 0 (a black tile) copies its tiles through bit for bit.  What a NaN pixel becomes is unspecified.  Not in place.
+ * gives L_p <= 0 (a black tile) copies its tiles through bit for bit; so does a row that is exactly 1 (L_p = 100: the gain is 1 and the
+ * map the identity on [0, 1], which the float32 round trip and the truncation to a level would not give back; members outside [0, 1]
+ * are then kept, not clipped).  What a NaN pixel becomes is unspecified.  Not in place.
  *
  * Argument errors (a NULL required pointer; n, h, w not positive or overflowing; a percentile outside (0, 100] or not finite;
  * n_sources other than 1 or n_tiles; out_dev == images_dev: SX_ERR_BAD_ARG; an unknown element type: SX_ERR_DTYPE; a workspace

@@ -147,8 +147,9 @@ __global__ __launch_bounds__(kSelectThreads) void percentile_select_kernel(Selec
     }
 }
 
-// The apply pass.  Row 0 of `luminance` for every tile (per_tile == 0) or row `tile`.  A row that is NaN (S was empty) or gives L_p <= 0 (a
-// black tile) copies its tiles through bit for bit: a workgroup-uniform branch.
+// The apply pass.  Row 0 of `luminance` for every tile (per_tile == 0) or row `tile`.  A row that is NaN (S was empty), gives L_p <= 0 (a
+// black tile) or is exactly 1 (the percentile is white already: gain 1, where the float32 round trip followed by the truncation to a level
+// would take one level off about half the elements of a uint8 tile) copies its tiles through bit for bit: a workgroup-uniform branch.
 template <typename T, int V>
 __global__ __launch_bounds__(kStreamThreads) void standardize_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, const float* __restrict__ luminance, int per_tile) {
     const int64_t tile = blockIdx.x / g.blocks_per_tile;
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(kStreamThreads) void standardize_kernel(const T* __
         const double y_p = (double)y_f;
         const double f_p = y_p > 0.008856 ? cbrt(y_p) : 7.787 * y_p + 16.0 / 116.0;
         const double l_p = 116.0 * f_p - 16.0;
-        const bool through = !(y_f == y_f) || !(l_p > 0.0);
+        const bool through = !(y_f == y_f) || !(l_p > 0.0) || y_f == 1.0f;      // (Y_p = 1: L_p = 100, the gain is 1 and the map the identity)
         const double gain = through ? 1.0 : 100.0 / l_p;
         map[0] = (float)gain;
         map[1] = (float)((16.0 / 116.0) * (1.0 - gain));

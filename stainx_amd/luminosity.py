@@ -39,7 +39,7 @@ class LuminosityStandardizer(nn.Module):
 
     ``mask``: an explicit uint8 / bool (N, H, W) tensor that says which pixels ENTER S (pen marks kept out, say); every pixel is mapped,
     because the point of the step is that glass becomes white.  The ``"luminosity"`` rule is not offered as a mask here.  A tile whose
-    set is empty, or whose percentile is black, is copied through.  Planar NCHW (or CHW) images of the five element types, on a ROCm
+    set is empty, or whose percentile is black or exactly white (Y_p = 1: the gain is 1), is copied through.  Planar NCHW (or CHW) images of the five element types, on a ROCm
     device; there is no CPU path.  Nothing synchronises: a call can be captured in a graph."""
 
     def __init__(self, percentile: float = 95.0, statistics: str = "tile", device: str | torch.device | None = None):

@@ -59,10 +59,10 @@ def lightness(y: np.ndarray | float) -> np.ndarray:
 
 
 def gain(y_p: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-    """(g, through) per row: g = 100 / L_p; through where Y_p is NaN or L_p <= 0 (the tile is copied)."""
+    """(g, through) per row: g = 100 / L_p; through where Y_p is NaN, L_p <= 0 or Y_p is exactly 1 (gain 1) (the tile is copied)."""
     y_p = np.asarray(y_p, dtype=np.float64).reshape(-1)
     l_p = lightness(y_p)
-    through = np.isnan(y_p) | ~(l_p > 0.0)
+    through = np.isnan(y_p) | ~(l_p > 0.0) | (y_p == 1.0)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(through, 1.0, 100.0 / l_p), through
 

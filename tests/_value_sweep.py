@@ -14,7 +14,17 @@ list, in float64, in slices of 2^20 pixels, and carried to a layout through its 
        sweeps and random triples; +-Inf, NaN and +-FLT_MAX as a group of their own (pixels with a member of it are out of every domain);
        and two tiles that hold lattice values only, so that tiles that pass the 8-bit code gates sit beside tiles that do not.
 
+    A_small  uint8 through the single-element path of the stain sweeps: every level in every channel and 2^16 seeded colours, odd layout only
+             (set A then runs its 2^24 colours once, in the pack layout: :func:`stain_layouts`);
+    K  float32 CONCENTRATIONS for ``ColorDeconvolution.combine`` (:func:`concentration_set`).
+
     gate_tiles()  float32 tiles for the 8-bit code gates, which mark WHOLE tiles: grey levels, every element one ulp off, one element off.
+
+The stain sweeps (tests/test_value_sweep_stains_gpu.py) add references from the project's restatements, float64 throughout: ``separation``
+(two-stain concentrations and H / E levels, own basis and normalised), ``jitter`` (macenko64 with C' = alpha C + beta, the fixed pairs
+JITTER dealt to the tiles in turn), ``deconv(name)`` (tests/_deconv_numpy.py: concentrations, apply with factors, apply with the other
+basis as target, three stain images), ``luminosity`` (tests/_luminosity_numpy.py's map for the rows LUMINOSITY_Y, with the way every
+branch went) and :func:`combine64`; ``luminosity_domain`` is every member in [0, 1].
 
 Masks per pixel: ``finite``; ``reinhard_domain`` (every member in [-1, 2]) and ``macenko_domain`` (every member in [-1/512, 2]: the optical
 density -log((255 x + 1) / 240) has its pole at -1/255), the domains on which the kernels are held to the float64 reference.
@@ -30,7 +40,10 @@ import numpy as np
 import torch
 
 from oracle import stain_oracle as so
-from stainx_amd import synth
+from stainx_amd import stain_basis, synth
+from tests import _deconv_numpy as dn
+from tests import _luminosity_numpy as ln
+from tests import _quantify_numpy as qn
 
 F32 = np.float32
 SLICE = 1 << 20
@@ -40,6 +53,18 @@ THRESHOLDS = (0.5, 0.8, 0.9)                       # luminosity thresholds of th
 REINHARD_TOL = 1e-4                                # the project's parity bound on [0, 1] (tests/test_siblings_gpu.py, test_per_tile_gpu.py)
 TRIPLE_DOMAIN = (-0.25, 1.25)                      # the Reinhard domain of set C's random triples (Sweep.reinhard_domain says why)
 MIN_BRANCH_PIXELS = 1000                           # coverage: in-domain pixels on either side of every branch, per float set
+CONC_TOL = qn.CONC_TOL                             # the project's bound on a float32 concentration against float64
+LUMINOSITY_TOL = 1e-4                              # the project's bound of the luminosity apply pass on [0, 1] (tests/test_luminosity_gpu.py)
+DECONV_NAMES = ("hed", "hdab")
+OTHER_BASIS = {"hed": "hdab", "hdab": "hed"}       # ColorDeconvolution(name, target=the other basis)
+# (alpha, beta) of the (H, E) concentrations, one pair per tile in turn: the identity, a mild pair, and a corner of what
+# MacenkoAugment.sample_factors draws with its defaults sigma1 = sigma2 = 0.2 (alpha in [0.8, 1.2], beta in [-0.2, 0.2])
+JITTER = (((1.0, 1.0), (0.0, 0.0)), ((1.1, 0.92), (0.03, -0.02)), ((1.2, 0.8), (0.2, -0.2)))
+# the luminance percentiles Y_p of the luminosity rows, as the float32 the kernel reads: L_p = 30, 75 and 100 (gains 3.33, 1.33 and 1)
+LUMINOSITY_Y = tuple(float(F32(((l_p + 16.0) / 116.0) ** 3)) for l_p in (30.0, 75.0, 100.0))
+QUANTIFY_BINNING = (5, 64)                         # bin_log2, zero_bin
+POLE_BAND = 1e-4                                   # quantify: a member whose float64 255 x + 1 lies within this of zero is not decided
+COMBINE_DOMAIN = 12.0                              # the concentration set: every member finite with |C| <= 12
 
 # ------------------------------------------------------------------------------------------------ the float64 reference
 _RGB2XYZ = np.array([[0.412453, 0.357580, 0.180423], [0.212671, 0.715160, 0.072169], [0.019334, 0.119193, 0.950227]])      # oracle/stain_oracle.py:232
@@ -90,17 +115,106 @@ def reinhard64(x: np.ndarray, mean, std, ref_mean, ref_std) -> dict:
     return {"out": back["rgb"], "raw": back["raw"], "lab": fwd["lab"], "gamma_in": fwd["gamma_in"], "f": fwd["f"], "f_inv": back["f_inv"], "gamma_out": back["gamma_out"]}
 
 
-def macenko64(x: np.ndarray, he, max_c, sm, tmc) -> dict:
+def optical_density64(x: np.ndarray) -> np.ndarray:
+    """OD = -log((255 x + 1) / 240) of (P, 3) unit pixels in float64 (oracle/stain_oracle.py:58)."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        return -np.log((np.asarray(x, dtype=np.float64) * 255.0 + 1.0) / 240.0)
+
+
+def concentrations64(x: np.ndarray, he) -> np.ndarray:
+    """(P, 2) float64: the least-squares concentrations of (P, 3) unit pixels in the basis ``he`` (oracle/stain_oracle.py:117)."""
+    he = np.asarray(he, dtype=np.float64).reshape(3, 2)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        return np.linalg.lstsq(he, optical_density64(x).T, rcond=None)[0].T
+
+
+def rebuild64(conc: np.ndarray, basis) -> np.ndarray:
+    """(P, S) concentrations -> (P, 3) un-clamped levels 240 exp(-basis C) with a (3, S) basis (oracle/stain_oracle.py:162-164)."""
+    basis = np.asarray(basis, dtype=np.float64).reshape(3, -1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return 240.0 * np.exp(-(conc @ basis.T))
+
+
+def macenko64(x: np.ndarray, he, max_c, sm, tmc, alpha=None, beta=None, own_basis: bool = False) -> dict:
     """The tail of the Macenko transform with a GIVEN (HE, maxC, SM, targetMaxC) (oracle/stain_oracle.py:58, 117, 162-164) in float64:
-    OD = -log((255 x + 1) / 240), least squares, rescale, 240 exp(-OD'), clipped to 0..255.  (P, 3) in; ``out`` (P, 3), ``raw`` before the clip."""
+    OD = -log((255 x + 1) / 240), least squares, rescale, 240 exp(-OD'), clipped to 0..255.  (P, 3) in; ``out`` (P, 3), ``raw`` before the clip.
+    ``alpha`` / ``beta`` ((2,) or (P, 2)): the jitter C' = alpha C + beta of the rescaled concentrations; ``own_basis``: no rescale, and
+    the tile is rebuilt with ``he`` itself."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        conc = concentrations64(x, he)
+        if not own_basis:
+            conc = conc * (np.asarray(tmc, dtype=np.float64).reshape(2) / np.asarray(max_c, dtype=np.float64).reshape(2))
+        if alpha is not None:
+            conc = np.asarray(alpha, dtype=np.float64) * conc + np.asarray(beta, dtype=np.float64)
+        raw = rebuild64(conc, he if own_basis else sm)
+    return {"out": np.clip(raw, 0.0, 255.0), "raw": raw}
+
+
+def separation64(x: np.ndarray, he, max_c, sm, tmc) -> dict:
+    """Stain separation with a given basis in float64: ``conc`` (P, 2) own-basis concentrations (normalised mode: times ``scale`` =
+    tmc / maxC), ``own`` and ``normalised`` (P, 2, 3): the un-clamped H and E levels, stain i rebuilt from C_i alone with ``he`` / from
+    C_i scale_i with ``sm``."""
+    conc = concentrations64(x, he)
     he, sm = np.asarray(he, dtype=np.float64).reshape(3, 2), np.asarray(sm, dtype=np.float64).reshape(3, 2)
     scale = np.asarray(tmc, dtype=np.float64).reshape(2) / np.asarray(max_c, dtype=np.float64).reshape(2)
+    own = np.stack([rebuild64(conc[:, s:s + 1], he[:, s:s + 1]) for s in range(2)], axis=1)
+    normalised = np.stack([rebuild64(conc[:, s:s + 1] * scale[s], sm[:, s:s + 1]) for s in range(2)], axis=1)
+    return {"conc": conc, "own": own, "normalised": normalised}
+
+
+def _as_tile(x: np.ndarray) -> np.ndarray:
+    """(P, 3) pixels as one (1, 3, 1, P) tile, what the restatements of tests/_deconv_numpy.py and tests/_luminosity_numpy.py take."""
+    return np.ascontiguousarray(np.asarray(x).T).reshape(1, 3, 1, -1)
+
+
+def _as_pixels(tile: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(tile.reshape(3, -1).T)
+
+
+def basis_of(name: str) -> np.ndarray:
+    """The (3, 3) float32 basis ``ColorDeconvolution(name)`` uses."""
+    return stain_basis(name).numpy()
+
+
+def deconv64(x32: np.ndarray, name: str) -> dict:
+    """tests/_deconv_numpy.py on (P, 3) float32 unit pixels, float64 throughout: ``conc`` (P, 3); the un-clamped levels of apply with
+    dn.ALPHA / dn.BETA (``apply``) and of apply rebuilt with the other basis (``target``); ``stains`` (P, 3 images, 3 channels)."""
+    tile, basis = _as_tile(np.asarray(x32, dtype=F32)), basis_of(name)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        od = -np.log((np.asarray(x, dtype=np.float64) * 255.0 + 1.0) / 240.0)
-        conc = np.linalg.lstsq(he, od.T, rcond=None)[0]      # (2, P)
-        od_new = (sm @ (conc * scale[:, None])).T
-        raw = 240.0 * np.exp(-od_new)
-    return {"out": np.clip(raw, 0.0, 255.0), "raw": raw}
+        out = {"conc": _as_pixels(dn.concentrations(tile, basis)),
+               "apply": _as_pixels(dn.apply(tile, basis, alpha=[dn.ALPHA], beta=[dn.BETA], dtype=np.float64)),
+               "target": _as_pixels(dn.apply(tile, basis, target=basis_of(OTHER_BASIS[name]), dtype=np.float64)),
+               "stains": np.stack([_as_pixels(img) for img in dn.stain_images(tile, basis, dtype=np.float64)], axis=1)}
+    return out
+
+
+def luminosity64(x32: np.ndarray) -> dict:
+    """tests/_luminosity_numpy.py's map on (P, 3) float32 unit pixels for the rows LUMINOSITY_Y, in float64, from its own functions (the
+    CPU file holds clip(raw) to ln.standardize_unit bit for bit): ``raw`` (P, rows, 3) unit values BEFORE the clamp to [0, 1]; and which
+    way every branch went: ``gamma_in`` (P, 3), ``f`` (P, 3), ``f_inv`` and ``gamma_out`` (P, rows, 3), ``clamp`` (P, rows): the
+    min(100 L* / L_p, 100) took 100."""
+    tile = _as_tile(np.asarray(x32, dtype=F32))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        u = ln.unit(tile)
+        gamma_in = u > 0.04045
+        xyz = np.einsum("ij,njhw->nihw", ln.RGB2XYZ, ln.linear(u)) / ln.WHITE
+        cube = xyz > 0.008856
+        f = ln.f_values(tile)
+        fx, fy, fz = f[:, 0], f[:, 1], f[:, 2]
+        raw, f_inv, gamma_out, clamp = [], [], [], []
+        for y_p in LUMINOSITY_Y:
+            g = ln.gain(np.array([y_p]))[0][0]
+            lifted = g * fy + (16.0 / 116.0) * (1.0 - g)
+            fy2 = np.minimum(lifted, 1.0)
+            f2 = np.stack([fy2 + (fx - fy), fy2, fy2 - (fy - fz)], axis=1)
+            lin = np.einsum("ij,njhw->nihw", ln.XYZ2RGB, ln.f_inv(f2) * ln.WHITE)
+            curve = lin > 0.0031308
+            raw.append(_as_pixels(np.where(curve, 1.055 * _pow(curve, lin, 1.0 / 2.4) - 0.055, 12.92 * lin)))
+            f_inv.append(_as_pixels(f2 > 0.2068966))
+            gamma_out.append(_as_pixels(curve))
+            clamp.append((lifted >= 1.0).reshape(-1))
+    return {"raw": np.stack(raw, axis=1), "gamma_in": _as_pixels(gamma_in), "f": _as_pixels(cube), "f_inv": np.stack(f_inv, axis=1), "gamma_out": np.stack(gamma_out, axis=1),
+            "clamp": np.stack(clamp, axis=1)}
 
 
 def grey_levels(x32: np.ndarray) -> np.ndarray:
@@ -187,6 +301,8 @@ class Sweep:
     def __init__(self, name: str, pixels: torch.Tensor, layouts: dict[str, Layout], triples: np.ndarray | None = None):
         self.name, self.pixels, self.dtype, self.layouts = name, pixels, pixels.dtype, layouts
         self.triples = np.zeros(len(pixels), dtype=bool) if triples is None else triples      # (P,): the random triples of set C
+        self._jitter: dict = {}
+        self._deconv: dict = {}
 
     def __repr__(self) -> str:
         return f"Sweep({self.name}, {len(self.pixels)} pixels)"
@@ -229,6 +345,43 @@ class Sweep:
         return _in_slices(lambda x: macenko64(x, st["he"], st["max_c"], st["sm"], st["tmc"]), self.x32)
 
     @cached_property
+    def luminosity_domain(self) -> np.ndarray:
+        """Every member in [0, 1], where the float32 oracle's round trip is within a quarter of the bound of float64 at the three gains
+        (tests/test_value_sweep_cpu.py prints the figures).  Not widened: nothing outside [0, 1] has been measured at the gain 3.33."""
+        return self._within(0.0, 1.0)
+
+    @cached_property
+    def separation(self) -> dict:
+        st = statistics()
+        return _in_slices(lambda x: separation64(x, st["he"], st["max_c"], st["sm"], st["tmc"]), self.x32)
+
+    def jitter(self, layout: "Layout", own_basis: bool, shift: int = 0) -> dict:
+        """macenko64 with C' = alpha C + beta over the LAYOUT's pixels (the factors are per tile: tile t takes JITTER[(t + shift) % 3];
+        :func:`row_shifts` gives a layout of fewer tiles than pairs one call per pair), normalised or in the source's own basis: ``raw``
+        (N, 3, H, W) float64 before the clip, ``alpha`` / ``beta`` (N, 2) float32, ``pair`` (N,) the index into JITTER.  Once per layout."""
+        key = (layout.name, bool(own_basis), shift)
+        if key not in self._jitter:
+            st = statistics()
+            which = (np.arange(layout.n) + shift) % len(JITTER)
+            pairs = np.asarray(JITTER, dtype=np.float64)[which]      # (N, 2 (alpha, beta), 2 (H, E))
+            per_pixel = np.repeat(pairs, layout.h * layout.w, axis=0)
+            x = self.x32[layout.index]
+            raw = np.concatenate([macenko64(x[s:s + SLICE], st["he"], st["max_c"], st["sm"], st["tmc"], alpha=per_pixel[s:s + SLICE, 0], beta=per_pixel[s:s + SLICE, 1],
+                                            own_basis=own_basis)["raw"] for s in range(0, len(x), SLICE)])
+            raw = np.ascontiguousarray(raw.reshape(layout.n, layout.h, layout.w, 3).transpose(0, 3, 1, 2))
+            self._jitter[key] = {"raw": raw, "alpha": pairs[:, 0].astype(F32), "beta": pairs[:, 1].astype(F32), "pair": which}
+        return self._jitter[key]
+
+    def deconv(self, name: str) -> dict:
+        if name not in self._deconv:
+            self._deconv[name] = _in_slices(lambda x: deconv64(x, name), self.x32)
+        return self._deconv[name]
+
+    @cached_property
+    def luminosity(self) -> dict:
+        return _in_slices(luminosity64, self.x32)
+
+    @cached_property
     def levels(self) -> np.ndarray:
         """(P, 3) uint8: the grey level of every member (:func:`grey_levels`)."""
         return grey_levels(self.x32)
@@ -259,11 +412,11 @@ class Sweep:
         return nhwc.contiguous() if channels_last else nhwc.permute(0, 3, 1, 2).contiguous()
 
     def spread(self, layout: Layout, per_pixel: np.ndarray, replace: np.ndarray | None = None) -> np.ndarray:
-        """A per-pixel array (P,) or (P, 3) carried to the layout: (N, H, W) or (N, 3, H, W)."""
+        """A per-pixel array (P,) or (P, K) carried to the layout: (N, H, W) or (N, K, H, W)."""
         got = per_pixel[self.index(layout, replace)]
         if got.ndim == 1:
             return got.reshape(layout.n, layout.h, layout.w)
-        return np.ascontiguousarray(got.reshape(layout.n, layout.h, layout.w, 3).transpose(0, 3, 1, 2))
+        return np.ascontiguousarray(got.reshape(layout.n, layout.h, layout.w, got.shape[1]).transpose(0, 3, 1, 2))
 
 
 def _both_layouts(blocks: list[np.ndarray], pad: int, packs: tuple[int, int], odd: tuple[int, int], seed: int) -> dict[str, Layout]:
@@ -278,6 +431,25 @@ def set_a() -> Sweep:
     colours = torch.stack([(i >> 16) & 255, (i >> 8) & 255, i & 255], dim=1).to(torch.uint8)
     pixels = torch.cat([colours, torch.tensor([[128, 128, 128]], dtype=torch.uint8)])
     return Sweep("A_u8_all_colours", pixels, _both_layouts([np.arange(1 << 24)], 1 << 24, (4096, 4096), (4099, 4095), 11))
+
+
+@lru_cache(maxsize=None)
+def set_a_small() -> Sweep:
+    """uint8 through the single-element path: every level in every channel -- the grey axis and the six channel sweeps of
+    :func:`_axis_and_sweeps`, the fixed members as levels -- and 2^16 seeded colours, in an odd layout ONLY (255 x 257 tiles: odd W, odd
+    H * W, four work items of 16 384 pixels each).  Set A then needs its 2^24 colours in the pack layout alone."""
+    levels = torch.arange(256, dtype=torch.uint8)
+    parts = [levels[:, None].expand(-1, 3)]
+    for fixed in FIXED:
+        for c in range(3):
+            px = torch.tensor([round(255 * v) for v in fixed], dtype=torch.uint8).repeat(256, 1)
+            px[:, c] = levels
+            parts.append(px)
+    colours = torch.from_numpy(np.random.default_rng(2031).integers(0, 256, size=(1 << 16, 3), dtype=np.uint8))
+    pixels = torch.cat(parts + [colours, torch.tensor([[128, 128, 128]], dtype=torch.uint8)])
+    h, w = 255, 257
+    assert w % 2 == 1 and (h * w) % 2 == 1 and h * w >= 2 * 16384
+    return Sweep("A_small_u8", pixels, {"odd": _layout("odd", h, w, [np.arange(len(pixels) - 1)], len(pixels) - 1, 12)})
 
 
 def _axis_and_sweeps(values: torch.Tensor) -> torch.Tensor:
@@ -353,6 +525,63 @@ def set_c() -> Sweep:
     first = len(lattice_px) + 7 * len(finite)
     triples[first:first + (1 << 20)] = True
     return Sweep("C_f32", pixels, _both_layouts(blocks, len(pixels) - 1, (512, 512), (511, 513), 37), triples)
+
+
+def stain_layouts(sweep: Sweep) -> list[Layout]:
+    """The layouts of the stain sweeps: set A's 2^24 colours run ONCE, in the pack layout (A_small covers the single-element path)."""
+    return [sweep.layouts["packs"]] if sweep.name.startswith("A_u8") else list(sweep.layouts.values())
+
+
+def row_shifts(layout: Layout, rows: int) -> range:
+    """Per-tile rows are dealt in turn, tile t taking row (t + shift) % rows: one shift where the layout has a tile for every row, every
+    shift where it has not (set A's pack layout is ONE tile)."""
+    return range(1) if layout.n >= rows else range(rows)
+
+
+@lru_cache(maxsize=None)
+def concentration_set() -> Sweep:
+    """float32 (P, 3) CONCENTRATIONS for ColorDeconvolution.combine, which need not come out of a separation: the concentrations of set
+    C's in-domain pixels under ``hed`` (rounded to float32) -- without C's two lattice-only tiles: combine(separate(k / 255)) is the
+    integer k + 1, and with those 2^19 pixels 15.3 % of the uint8 reference of ``hed`` lies within the bound of an integer, over the cap
+    of tests/test_value_sweep_cpu.py; the lattice and its neighbours stay, in the axis and the sweeps of set C --; the grey axis and one-stain sweeps over [-4, 12] (the other two fixed at
+    (0.5, 0.2, 0.1) and at (1.5, 1.0, 0.3)); 2^18 uniform triples in [-2, 6)^3; and +-Inf, NaN, +-FLT_MAX, +-1e30 as a block of its
+    own.  The pad is (0.5, 0.5, 0.5).  ``combine_domain``: every member finite with |C| <= 12."""
+    c = set_c()
+    rng = np.random.default_rng(2032)
+    beside_lattice = np.arange(len(c.pixels)) >= LATTICE_TILES * 512 * 512      # (not the lattice tiles: see the docstring)
+    with np.errstate(over="ignore", invalid="ignore"):
+        separated = c.deconv("hed")["conc"][c.macenko_domain & beside_lattice].astype(F32)
+    line = np.concatenate([np.linspace(-4.0, 12.0, 1 << 14, dtype=np.float64).astype(F32), _neighbours(np.array([0.0, -0.0, 12.0, -4.0], dtype=F32), 2)])
+    swept = [np.repeat(line[:, None], 3, axis=1)]
+    for fixed in ((0.5, 0.2, 0.1), (1.5, 1.0, 0.3)):
+        for s in range(3):
+            px = np.tile(np.asarray(fixed, dtype=F32), (len(line), 1))
+            px[:, s] = line
+            swept.append(px)
+    uniform = (rng.random((1 << 18, 3), dtype=F32) * F32(8.0) - F32(2.0)).astype(F32)
+    tiny = np.finfo(F32)
+    group = np.array([np.inf, -np.inf, np.nan, tiny.max, -tiny.max, 1e30, -1e30], dtype=F32)
+    wild = uniform[: 1 << 12].copy()
+    wild[np.arange(len(wild)), rng.integers(0, 3, size=len(wild))] = group[rng.integers(0, len(group), size=len(wild))]
+    wild = np.concatenate([np.repeat(group[:, None], 3, axis=1), wild])
+    finite = np.concatenate([separated] + swept + [uniform])
+    pixels = torch.from_numpy(np.concatenate([finite, wild, np.full((1, 3), 0.5, dtype=F32)]).astype(F32))
+    blocks = [np.arange(len(finite)), len(finite) + np.arange(len(wild))]
+    return Sweep("K_f32_concentrations", pixels, _both_layouts(blocks, len(pixels) - 1, (512, 512), (511, 513), 41))
+
+
+def combine_domain(sweep: Sweep) -> np.ndarray:
+    c = sweep.pixels.numpy()
+    with np.errstate(invalid="ignore"):
+        return (np.isfinite(c) & (np.abs(c) <= F32(COMBINE_DOMAIN))).all(axis=1)
+
+
+@lru_cache(maxsize=None)
+def combine64(name: str) -> np.ndarray:
+    """(P, 3) float64: dn.combine of the concentration set with the basis ``name``, un-clamped levels."""
+    c = concentration_set().pixels.numpy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        return _in_slices(lambda part: _as_pixels(dn.combine(_as_tile(part), basis_of(name), dtype=np.float64)), c)["out"]
 
 
 def float_sets() -> list[Sweep]:

@@ -11,7 +11,9 @@ ill-posed stands between a value and its result.
   within the bound of an integer, where one level is allowed.  Outside the domain -- finite or not -- every output is finite and in range,
   and replacing those pixels by 0.5 grey changes no bit of any other pixel (no NaN through a pack, a ballot or an MFMA block).
 * The 8-bit code gates mark whole tiles: tiles of k / 255 beside tiles whose every element, or whose one element, is k / 255 +- 1 ulp (or
-  -0.0) -- the transform (which codes the tiles that pass) gives the bits of estimate + apply (which never codes).
+  -0.0) -- the transform (which codes the tiles that pass) gives the bits of estimate + apply (which never codes); so do separation and
+  augmentation with the tile's own estimate against the same call with that estimate given.
+* The stain kernels (separation, jitter, deconvolution, quantify, luminosity apply): tests/test_value_sweep_stains_gpu.py.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-from stainx_amd import HistogramMatching, Macenko, Reinhard, StainEstimate, synth, tissue_mask
+from stainx_amd import HistogramMatching, Macenko, MacenkoAugment, Reinhard, StainEstimate, synth, tissue_mask
 from tests import _hm_slide_numpy as sn
 from tests import _masked_numpy as mn
 from tests import _value_sweep as vs
@@ -230,7 +232,9 @@ def test_code_gates_take_no_neighbour_of_a_grey_level_for_a_code(dev):
     down, -0.0 for 0; first pack, last pack, a lane in the middle of a wave).  The gates mark a whole tile, so only such tiles can show
     what they make of a neighbour: a gate that took k / 255 +- 1 ulp for level k would code the tile and return table[k] where estimate +
     apply (given statistics, no gate, never coded) evaluates f(k / 255 +- 1 ulp).  The transform equals estimate + apply bit for bit on
-    every tile.
+    every tile.  So do ``Macenko.separate(x)`` (its last pass reads the codes of the tiles the first pass coded) against
+    ``separate(x, source=estimate(x))`` and the ``MacenkoAugment`` forward (the transform's passes in front of its own reconstruct pass)
+    against estimate + apply with the same factors, both in their own basis and normalised: one launch with a given basis has no gate.
 
     Measured with the bit comparison of both gates replaced by |x - k / 255| <= 3e-7 in a scratch build: the test fails -- Reinhard with
     batch statistics differs on all 16 tiles (the pooled statistics move), Reinhard with tile statistics and Macenko on 6 each: the three
@@ -246,8 +250,22 @@ def test_code_gates_take_no_neighbour_of_a_grey_level_for_a_code(dev):
     for statistics in ("batch", "tile"):
         reinhard.statistics = statistics
         cases[f"Reinhard, {statistics} statistics"] = (reinhard.transform(x), reinhard.apply(x, reinhard.estimate(x, pooled=statistics == "batch")))
-    cases["Macenko"] = (macenko.transform(x), macenko.apply(x, macenko.estimate(x)))
-    differ = {what: sorted(name for name, t in tiles.items() if not same_bits(got[t], want[t])) for what, (got, want) in cases.items()}
+    estimate = macenko.estimate(x)
+    cases["Macenko"] = (macenko.transform(x), macenko.apply(x, estimate))
+    # separation and augmentation with each tile's OWN estimate (the forms that may code a tile) against the same call with that estimate
+    # GIVEN (one launch, no gate, never coded).  Whether or not a form has a coded path, the comparison holds and costs one call.
+    for own_basis in (True, False):
+        mode = "own basis" if own_basis else "normalised"
+        own = macenko.separate(x, own_basis=own_basis, stains=True, concentrations=True)
+        given = macenko.separate(x, source=estimate, own_basis=own_basis, stains=True, concentrations=True)
+        for part in ("hematoxylin", "eosin", "concentrations"):
+            cases[f"Macenko.separate, {mode}, {part}"] = (getattr(own, part), getattr(given, part))
+    pairs = torch.tensor(vs.JITTER, dtype=torch.float32)[torch.arange(n) % len(vs.JITTER)].to(dev)      # (N, 2 (alpha, beta), 2)
+    alpha, beta = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+    augment = MacenkoAugment(normalizer=macenko, device=dev, normalize_to_0_1=False)
+    cases["MacenkoAugment, normalised"] = (augment(x, alpha, beta), macenko.apply(x, estimate, alpha=alpha, beta=beta))
+    cases["MacenkoAugment, own basis"] = (MacenkoAugment(device=dev, normalize_to_0_1=False)(x, alpha, beta), macenko.apply(x, estimate, alpha=alpha, beta=beta, own_basis=True))
+    differ ={what: sorted(name for name, t in tiles.items() if not same_bits(got[t], want[t])) for what, (got, want) in cases.items()}
     for what, names in differ.items():
         print(f"code gates, {what}: transform != estimate + apply on {len(names)} of {n} tiles {names}")
     assert not any(differ.values()), differ
