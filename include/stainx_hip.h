@@ -193,7 +193,13 @@ int sx_macenko_estimate(const void* images_dev, int dtype, int64_t n_tiles, int6
  * The pseudo-inverse is a function of the six given floats (fp64, the rank rule of lstsq(rcond=None): a rank-1 basis drops its second
  * singular value), the scale a float32 division, so a tile's own estimate fed back -- sx_macenko_estimate's outputs, n_sources =
  * n_tiles -- gives the bits of sx_macenko_transform(..., SX_MACENKO_CLASSIC) without factors and of sx_macenko_augment with them,
- * wherever the tile's maxC is finite and non-zero. */
+ * wherever the tile's maxC is finite and non-zero.
+ * Verified parameter domain (tests/_param_sweep.py): the parity bound of 2.55e-2 on the 0-255 scale against the float64
+ * arithmetic is verified for finite bases with cond(HE) = sigma_max / sigma_min <= 25 (a stain angle of about 0.08 rad; the estimates of
+ * H&E tiles measured lie at 3.3 ... 11.4) whose column sums are positive, a finite positive maxC with target_max_conc / maxC / |column|
+ * in [0.05, 2.5], and finite factors with alpha in [-1.2, 1.2] and |beta| <= 3.  The float32 fold itself leaves the quarter of the bound
+ * it is allowed near cond 100 and the bound near cond 500: a narrower angle is a caller's error, not caught here.  Outside the domain
+ * every output element is still finite and inside the output range, and a tile's result depends on its own row alone. */
 int sx_macenko_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                      const float* source_he_dev, const float* source_max_c_dev, int64_t n_sources,
                      const float* alpha_dev, const float* beta_dev,
@@ -503,7 +509,10 @@ int sx_reinhard_apply(const void* images_dev, void* out_dev, int dtype, int64_t 
  *   The statistics and the reference are DEVICE memory read by the kernel (a captured graph replayed after new values were written
  *   into the same buffers uses the new values).  The arithmetic per pixel is the pooled apply pass's, a function of the float32
  *   statistics: sx_reinhard_fit's outputs with n_sources = 1 give the bits of sx_reinhard_transform, sx_reinhard_tile_stats' outputs
- *   with n_sources = n_tiles those of sx_reinhard_transform_tiles. */
+ *   with n_sources = n_tiles those of sx_reinhard_transform_tiles.
+ *   Verified parameter domain (tests/_param_sweep.py): the bound of 1e-4 on [0, 1] against float64 is verified for finite
+ *   statistics with ref_std / source_std in [0.1, 2.5] for L, a and b and a source mean in [-64, 320]; at a ratio of 5 the float32
+ *   arithmetic of the reference itself is 6.5e-5 from float64.  Outside it every output element is finite and inside [0, 1]. */
 size_t sx_reinhard_tiles_workspace_bytes(int dtype, int64_t n_tiles, int64_t height, int64_t width);
 int sx_reinhard_tile_stats(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                            float* tile_mean_out_dev, float* tile_std_out_dev, void* workspace_dev, size_t workspace_bytes,
@@ -786,7 +795,10 @@ int sx_hm_transform_masked(const void* images_dev, void* out_dev, int dtype, int
  *   graph replayed after new tables (or mask bytes) were written into the same buffers uses the new values.  n_sources is 1 (one
  *   table set for the batch) or n_tiles (set t serves tile t); anything else is SX_ERR_BAD_ARG.  Every workgroup converts its source's
  *   tables to the output element on the way into LDS.  Masked: a tissue pixel gets exactly the bits of the unmasked call, a
- *   background pixel the bits of its input (floats are not quantised). */
+ *   background pixel the bits of its input (floats are not quantised).
+ *   Table entries need not lie inside 0..255 (given tables may be blended or edited ones): for EVERY output type an entry is clamped to
+ *   [0, 255] first and a NaN entry is 0 -- uint8: trunc(clamp(v, 0, 255)), so 255.5, 256, 1e9 and +Inf give 255, -0.5, -1 and -Inf give 0;
+ *   floats: clamp(v / 255, 0, 1).  Tables inside 0..255 (all that sx_hm_tables writes) give the bits they always gave. */
 int sx_hm_estimate(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last, int per_tile,
                    unsigned long long* counts_out_dev, unsigned long long* pixels_out_dev, void* workspace_dev,
                    size_t workspace_bytes, void* stream);
@@ -875,6 +887,12 @@ int sx_stain_max_concentrations(const void* images_dev, int dtype, int64_t n_til
  * gives L_p <= 0 (a black tile) copies its tiles through bit for bit; so does a row that is exactly 1 (L_p = 100: the gain is 1 and the
  * map the identity on [0, 1], which the float32 round trip and the truncation to a level would not give back; members outside [0, 1]
  * are then kept, not clipped).  What a NaN pixel becomes is unspecified.  Not in place.
+ * L_p is formed in fp64 as written above, so a positive Y_p below 1.8e-18 (every denormal) is absorbed by the 16/116 and gives L_p = 0
+ * exactly: a black row, copied.  The smallest positive L_p is 3.6e-15 and the largest gain 2.8e16, a finite float32: g f_y + (16/116)(1 - g)
+ * never meets Inf - Inf.  Verified parameter domain (tests/_param_sweep.py): the bound of 1e-4 on [0, 1] against float64 is
+ * verified for finite rows with L_p >= 0.25 (a gain of 400; the cancellation in g f_y + (16/116)(1 - g) costs about g * 1e-8 on a dark
+ * pixel) and |g - 1| >= 1e-3, or Y_p exactly 1: a row within a few float32 steps of 1 is NOT copied, runs the map at a gain that is 1 to
+ * rounding, and on uint8 tiles may then come out one level off anywhere (every element lies within the bound of its own level).
  *
  * Argument errors (a NULL required pointer; n, h, w not positive or overflowing; a percentile outside (0, 100] or not finite;
  * n_sources other than 1 or n_tiles; out_dev == images_dev: SX_ERR_BAD_ARG; an unknown element type: SX_ERR_DTYPE; a workspace

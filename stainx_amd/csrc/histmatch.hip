@@ -233,7 +233,8 @@ __device__ __forceinline__ float lut_value(float s, const float* ref_cdf) {
 template <typename T>
 __device__ __forceinline__ T typed_value(float v) {
     if constexpr (sizeof(T) == 1) {
-        return (uint8_t)v;                                                            // stays 0..255, truncated
+        return (uint8_t)fminf(fmaxf(v, 0.0f), 255.0f);                                // clamped like the float outputs, then truncated; a NaN is 0.
+                                                                                      // (lut_value is inside 0..255 already; a GIVEN table -- sx_hm_apply_tables -- need not be, and the bare cast of 256, -1 or NaN is undefined)
     } else {
         const float unit = fminf(fmaxf(v / 255.0f, 0.0f), 1.0f);                      // :291, :296
         if constexpr (sizeof(T) == 8) return (double)unit; else return Elem<T>::store(unit);

@@ -27,7 +27,11 @@ def tables(counts: np.ndarray, pixels: np.ndarray, ref_hists) -> np.ndarray:
 
 
 def lookup(images: np.ndarray, luts: np.ndarray, channel_axis: int = 1) -> np.ndarray:
-    """``so.hm_transform`` from its gather on, with GIVEN tables ``luts`` (1, 3, 256) or (N, 3, 256): tile t takes row t (or row 0)."""
+    """``so.hm_transform`` from its gather on, with GIVEN tables ``luts`` (1, 3, 256) or (N, 3, 256): tile t takes row t (or row 0).
+    A table entry outside 0..255 is clamped before the cast of EVERY output type, uint8 included, and a NaN entry is 0 (the library's
+    rule, include/stainx_hip.h: sx_hm_apply_tables; the reference builds its own tables and never meets such an entry); an entry of
+    -0.0 comes out as +0.0, as the device's max(v, 0) returns it (numpy's clip would keep the sign)."""
+    luts = np.where(np.isnan(luts) | (luts == 0), F32(0), luts).astype(F32)
     chw, permuted = so._channels_first(images, channel_axis)
     dtype = chw.dtype
     u8, scaled_back = so.images_to_uint8(np.ascontiguousarray(chw))
