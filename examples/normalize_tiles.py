@@ -155,6 +155,20 @@ def main() -> None:
     out = torch.cat([mk.apply(b, slide) for b in batches])
     print(f"[rank {rank}] Macenko on sampled tissue   {tuple(out.shape)} in {len(batches)} batches  sampled {sample.taken.tolist()} of {sample.population.tolist()} tissue pixels  "
           f"maxC = {[round(v, 4) for v in slide.max_concentrations[0].tolist()]}")
+    # 13. statistics-space augmentation (RandStainNA): fit the cohort's distribution of per-tile statistics ONCE -- in LAB from
+    #     Reinhard.estimate, in HED from ColorDeconvolution.estimate (exact integer moments, no map) --, then every tile of a training batch
+    #     is moved from its OWN statistics to a target drawn from it: estimate + one apply launch, nothing returns to the host.
+    from stainx_amd import ColorDeconvolution, StatisticsAugment, StatisticsDistribution
+
+    lab_cohort = StatisticsDistribution.fit(*[Reinhard(device=dev, mask="luminosity").estimate(b) for b in batches])      # rows of tiles without tissue are skipped
+    hed_cohort = StatisticsDistribution.fit(*[ColorDeconvolution("hed", device=dev, mask="luminosity").estimate(b) for b in batches])
+    lab_aug = StatisticsAugment(lab_cohort, "lab", kind="normal", p=0.8, mask="luminosity", generator=torch.Generator().manual_seed(rank))
+    hed_aug = StatisticsAugment(hed_cohort, "hed", kind="laplace", mask="luminosity", generator=torch.Generator().manual_seed(rank))
+    out_lab, out_hed = lab_aug(edge), hed_aug(edge)
+    glass = (tissue_mask(edge)[0] == 0).unsqueeze(1).expand_as(edge)
+    assert torch.equal(out_lab[glass], edge[glass])                  # LAB: glass keeps the bits of the input
+    print(f"[rank {rank}] StatisticsAugment           {tuple(out_lab.shape)} {out_lab.dtype} (lab) + {tuple(out_hed.shape)} {out_hed.dtype} (hed)  "
+          f"cohort L* mean {lab_cohort.mean_center[0].item():.1f} +- {lab_cohort.mean_spread[0].item():.1f}")
     if world > 1:
         torch.distributed.destroy_process_group()
 

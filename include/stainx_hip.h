@@ -359,6 +359,32 @@ int sx_deconv_quantify(const void* images_dev, int dtype, int64_t n_tiles, int64
 int sx_deconv_quantify_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                               const float* basis_dev, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
                               long long* out_dev, const unsigned char* mask_dev, unsigned flags, void* stream);
+/* sx_deconv_moments: the statistics pass of the stain space -- exact integer first and second moments of the three concentrations, in one
+ * streaming pass that reads a pixel once and writes no map (mean / standard deviation matching of concentrations, statistics-space
+ * augmentation).  The concentrations are, bit for bit, the float32 values sx_deconv_separate writes and sx_deconv_quantify bins, and
+ * a pixel counts under sx_deconv_quantify's rule: three finite concentrations (and, masked, its mask byte set); a tile whose basis row
+ * holds a NaN counts nothing.  Per counted pixel and stain:
+ *   t_s = C_s * 2^16 converted to int32 (round to nearest even, saturating) -- sx_deconv_quantify's term;   sums_s    += t_s
+ *   u_s = clamp(t_s, -2^22, 2^22);                                                                          squares_s += (u_s * u_s) >> 8
+ * so `sums` has the unit 2^-16 and `squares` the unit 2^-24 (floored; a concentration beyond +-64 enters the squares as 64).
+ *   out_dev   S x 7 int64, S = n_tiles (per_tile != 0) or 1 (one set pooled over the batch); row s is [sums: 3][squares: 3][pixels: 1].
+ *             Caller-owned; the call zeroes it in-stream (one hipMemsetAsync) and enqueues ONE kernel: every word is written.  No workspace.
+ *             On a stream that is being captured the zeroes come from a small clearing launch instead of the memset: with HIP 7.0 /
+ *             ROCm 7.2 a memset node's replay depends on what was launched since the previous replay (tools/probe_graph_memset.py,
+ *             profiles/graph_memset_probe.txt: a graph of one hipMemsetAsync writes wrong bytes on every replay that follows a
+ *             reduction and its read-back), a kernel node replays its own arguments.
+ * Integers throughout: the result does not depend on the order of the adds -- identical run to run, and rows add up exactly over tiles,
+ * batches, slides and ranks.  No overflow below 2^27 counted pixels per row even if every term is clamped (2^63 / 2^36; the sums: 2^63 /
+ * 2^31 pixels).  The floor biases a pixel's C^2 by less than 2^-24, downwards.
+ * Arguments, layouts (SX_MACENKO_CHANNELS_LAST: unmasked call only), the five element types, per-tile bases (n_bases = 1 or n_tiles) and
+ * flags (SX_MACENKO_CHANNELS_LAST, SX_MACENKO_CLASSIC as a no-op; every other bit is SX_ERR_BAD_ARG) are sx_deconv_quantify's. */
+int sx_deconv_moments(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                      const float* basis_dev, int64_t n_bases, int per_tile, long long* out_dev, unsigned flags, void* stream);
+/* sx_deconv_moments_masked: the same over the masked-in pixels of an explicit mask (N, H, W), one byte per pixel, non-zero = in; planar
+ * tiles only.  Values under masked-out pixels never matter. */
+int sx_deconv_moments_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                             const float* basis_dev, int64_t n_bases, int per_tile, long long* out_dev,
+                             const unsigned char* mask_dev, unsigned flags, void* stream);
 
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
@@ -751,6 +777,28 @@ int sx_reinhard_apply_stats_masked(const void* images_dev, void* out_dev, int dt
                                    int64_t width, const float* source_mean_dev, const float* source_std_dev, int64_t n_sources,
                                    const float* ref_mean_dev, const float* ref_std_dev, const uint8_t* mask_dev,
                                    double luminosity_threshold, void* stream);
+
+/* A TARGET PER TILE (an extension: statistics-space augmentation -- RandStainNA, Shen et al. 2022 --, Reinhard to per-tile or per-slide
+ * targets without a fit).
+ * sx_reinhard_apply_targets: sx_reinhard_apply_stats with n_targets rows of target statistics -- ONE kernel launch on `stream`, nothing
+ *   else enqueued, no workspace.
+ *   source_mean_dev, source_std_dev   n_sources x 3 floats each, n_sources = 1 or n_tiles (row t serves tile t)
+ *   target_mean_dev, target_std_dev   n_targets x 3 floats each, n_targets = 1 or n_tiles (row t serves tile t)
+ *   Any other n_sources / n_targets is SX_ERR_BAD_ARG.  All four arrays are DEVICE memory read by the kernel (a captured graph replayed
+ *   after new values were written into the same buffers uses the new values).  The arithmetic is the one body of the apply pass: with
+ *   n_targets = 1 and finite rows the output is bit for bit sx_reinhard_apply_stats', and tile t of a batched call is the one-tile call
+ *   with rows t.  If any of a tile's source or target rows holds a NaN the tile is copied with the bits of its input (tiles of fewer than
+ *   two pixels or tissue pixels, explicit "leave this tile" rows); sx_reinhard_apply_stats(_masked) keep their behaviour on such rows.
+ * sx_reinhard_apply_targets_masked: the same with a mask, with the semantics of sx_reinhard_apply_stats_masked (mask_dev: (N, H, W)
+ *   bytes, or NULL for the luminosity rule with luminosity_threshold in (0, 1)): a tissue pixel gets the bits of the unmasked call, a
+ *   background pixel the bits of its input. */
+int sx_reinhard_apply_targets(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                              int64_t width, const float* source_mean_dev, const float* source_std_dev, int64_t n_sources,
+                              const float* target_mean_dev, const float* target_std_dev, int64_t n_targets, void* stream);
+int sx_reinhard_apply_targets_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height,
+                                     int64_t width, const float* source_mean_dev, const float* source_std_dev, int64_t n_sources,
+                                     const float* target_mean_dev, const float* target_std_dev, int64_t n_targets,
+                                     const uint8_t* mask_dev, double luminosity_threshold, void* stream);
 
 /* Histogram matching, NCHW and NHWC.  The three 256-bin histograms count tissue pixels only, and the LUT arithmetic takes the TISSUE count
  * as its number of pixels (the sum of a channel's histogram); a tissue pixel gets its LUT value, a background pixel the bits of its

@@ -78,6 +78,9 @@ SIGNATURES = {
     # stain quantification: integer histograms of the three concentrations, fixed-point sums, counted pixels -- a memset and one launch
     "sx_deconv_quantify": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _int, _int, _vp, _uint, _vp]),
     "sx_deconv_quantify_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _int, _int, _vp, _vp, _uint, _vp]),
+    # statistics of the stain space: integer sums, sums of squares and counted pixels of the three concentrations -- a memset and one launch
+    "sx_deconv_moments": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _uint, _vp]),
+    "sx_deconv_moments_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),
@@ -142,6 +145,9 @@ SIGNATURES = {
     "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_apply_stats_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _c.c_double, _vp]),
+    # a target per tile: one launch, rows of source and target statistics read on the device, NaN rows copy their tile
+    "sx_reinhard_apply_targets": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sx_reinhard_apply_targets_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _c.c_double, _vp]),
     "sx_hm_masked_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "sx_hm_fit_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
     "sx_hm_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

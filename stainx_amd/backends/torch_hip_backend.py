@@ -1393,6 +1393,45 @@ class DeconvHIP(TorchHIPBackendBase):
                     _native.check(rc, "sx_deconv_quantify", self._lib)
         return out[:, :768].view(sets, 3, 256), out[:, 768:771], out[:, 771]
 
+    MOMENT_WORDS = 7      # a row of sx_deconv_moments' output: [sums 3][squares 3][pixels 1]
+
+    def moments(self, images: torch.Tensor, basis: torch.Tensor, *, per_tile: bool = True, channels_last: bool = False,
+                masking: tuple | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(sums (S, 3), squares (S, 3), pixels (S,))``, int64 views of ONE (S, 7) tensor; S = N (``per_tile``) or 1.  Fixed-point sums
+        (2^-16) and sums of squares (2^-24) of the three concentrations ``separate`` would write, and the counted pixels: a memset and one
+        launch, no map.  ``masking`` as in ``apply``."""
+        images = images.to(self.device)
+        n, h, w = self._dims(images, channels_last, "moments")
+        code = _dtype_code(images)
+        if masking is not None and channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
+        b, n_bases = self._bases(basis, n, "basis")
+        mask = None
+        if masking is not None and masking[0] is not None:
+            mask = _mask_bytes(masking[0], self.device)
+            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
+                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+        sets = n if per_tile else 1
+        if n == 0 or h * w == 0:
+            out = torch.zeros((sets, self.MOMENT_WORDS), dtype=torch.int64, device=self.device)
+        else:
+            images = images.contiguous()
+            out = torch.empty((sets, self.MOMENT_WORDS), dtype=torch.int64, device=self.device)
+            flags = _native.MACENKO_CHANNELS_LAST if channels_last else 0
+            stream = _native.stream_ptr(self.device)
+            with _native.on_device(self.device):
+                if masking is not None:
+                    if mask is None:
+                        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+                        rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
+                        _native.check(rc, "sx_tissue_mask", self._lib)
+                    rc = self._lib.sx_deconv_moments_masked(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, int(bool(per_tile)), out.data_ptr(), mask.data_ptr(), flags, stream)
+                    _native.check(rc, "sx_deconv_moments_masked", self._lib)
+                else:
+                    rc = self._lib.sx_deconv_moments(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, int(bool(per_tile)), out.data_ptr(), flags, stream)
+                    _native.check(rc, "sx_deconv_moments", self._lib)
+        return out[:, 0:3], out[:, 3:6], out[:, 6]
+
 
 class ReinhardHIP(TorchHIPBackendBase):
     """Reinhard LAB statistics matching on the GPU (numerics of ReinhardTorch, torch_backend.py:304-355)."""
@@ -1623,6 +1662,56 @@ class ReinhardHIP(TorchHIPBackendBase):
                                                           int(src_mean.shape[0]), mean.data_ptr(), std.data_ptr(), None if mask is None else mask.data_ptr(),
                                                           float(luminosity_threshold), _native.stream_ptr(self.device))
         _native.check(rc, "sx_reinhard_apply_stats_masked")
+        return out
+
+    # ---- a target per tile (include/stainx_hip.h: sx_reinhard_apply_targets ...) --------------------------
+    @staticmethod
+    def _rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str) -> tuple[torch.Tensor, torch.Tensor]:
+        if mean.dim() == 1:
+            mean = mean.unsqueeze(0)
+        if std.dim() == 1:
+            std = std.unsqueeze(0)
+        for name, t in ((f"{what}_mean", mean), (f"{what}_std", std)):
+            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
+                raise ValueError(f"{name} must be (3,), (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
+        if mean.shape[0] != std.shape[0]:
+            raise ValueError(f"{what}_mean and {what}_std must have the same number of rows, got {mean.shape[0]} and {std.shape[0]}")
+        return mean, std
+
+    def apply_targets(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, target_mean: torch.Tensor, target_std: torch.Tensor) -> torch.Tensor:
+        """``apply_statistics`` with a row of TARGET statistics per tile as well -- (1, 3) or (N, 3) each: one launch, no workspace.  A
+        tile any of whose rows holds a NaN is copied bit for bit."""
+        return self._apply_targets(images, source_mean, source_std, target_mean, target_std, None)
+
+    def apply_targets_masked(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, target_mean: torch.Tensor, target_std: torch.Tensor,
+                             mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
+        """``apply_targets`` with a tissue mask (None: the luminosity rule): one launch; background pixels are copied."""
+        return self._apply_targets(images, source_mean, source_std, target_mean, target_std, (mask, luminosity_threshold))
+
+    def _apply_targets(self, images, source_mean, source_std, target_mean, target_std, masking):
+        images = images.to(self.device)
+        self._check(images)
+        n, _, h, w = images.shape
+        source_mean, source_std = self._rows(source_mean, source_std, n, "source")
+        target_mean, target_std = self._rows(target_mean, target_std, n, "target")
+        code = _dtype_code(images)
+        images = images.contiguous()
+        sm, ss, tm, ts = self._f32(source_mean), self._f32(source_std), self._f32(target_mean), self._f32(target_std)
+        out = torch.empty_like(images)
+        if images.numel() == 0:
+            return out
+        stream = _native.stream_ptr(self.device)
+        with _native.on_device(self.device):
+            if masking is None:
+                rc = self._lib.sx_reinhard_apply_targets(images.data_ptr(), out.data_ptr(), code, n, h, w, sm.data_ptr(), ss.data_ptr(), int(sm.shape[0]),
+                                                         tm.data_ptr(), ts.data_ptr(), int(tm.shape[0]), stream)
+                _native.check(rc, "sx_reinhard_apply_targets")
+            else:
+                mask = _mask_bytes(masking[0], self.device)
+                rc = self._lib.sx_reinhard_apply_targets_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, sm.data_ptr(), ss.data_ptr(), int(sm.shape[0]),
+                                                                tm.data_ptr(), ts.data_ptr(), int(tm.shape[0]), None if mask is None else mask.data_ptr(),
+                                                                float(masking[1]), stream)
+                _native.check(rc, "sx_reinhard_apply_targets_masked")
         return out
 
     # ---- batch statistics pooled across ranks (see stainx_amd/distributed.py) --------------------------

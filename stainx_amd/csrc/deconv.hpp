@@ -506,6 +506,123 @@ __global__ __launch_bounds__(kStreamThreads) void deconv_quantify_kernel(const T
     }
 }
 
+// sx_deconv_moments / sx_deconv_moments_masked: first and second moments of the three concentrations as integers -- quantify's loop and
+// counting rule without the histogram.  DESIGN.md 4q.
+//   t_s = quantify's term (C_s 2^16, round to nearest even, saturating to int32)      sums_s    += t_s
+//   u_s = clamp(t_s, -2^22, 2^22)                                                     squares_s += (u_s u_s) >> 8      (unit 2^-24, floored)
+// Seven int64 accumulators per lane, one shuffle reduction per wave and word, the waves' totals through 4 x 7 LDS words, then seven
+// 64-bit global adds per WORKGROUP (non-zero totals only).  No LDS atomics, no table but the level tables.
+constexpr int kMomentWords = 7;      // a row of the output: [sums 3][squares 3][pixels 1]
+constexpr int kMomentClamp = 1 << 22;
+
+struct MomentArgs {
+    const float* basis;             // n_bases x 9
+    unsigned long long* out;        // S x kMomentWords, zero when the kernel starts
+    int64_t pixels, n_tiles;        // P = H*W, N
+    int blocks;                     // work items per tile
+    int per_basis, per_tile;        // 1: row `tile` of the bases / of the output, 0: row 0
+};
+
+template <typename T, int V, bool kInter, bool kMask = false>
+__global__ __launch_bounds__(kStreamThreads) void deconv_moments_kernel(const T* __restrict__ images, MomentArgs a, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    static_assert(!(kInter && kMask), "the masked forms are planar");
+    static_assert(kQuantPixels % (kStreamThreads * V) == 0, "a work item is a whole number of pack sets");
+    constexpr int TPB = kStreamThreads;
+    constexpr int kWaves = kStreamThreads / kWave;
+    __shared__ LevelTables<T> tb;
+    __shared__ float fold[13];      // (the last word: the tile's basis row holds a NaN)
+    __shared__ long long red[kWaves][kMomentWords];
+    const int64_t tile = blockIdx.x / (unsigned)a.blocks;
+    const int chunk_id = (int)(blockIdx.x % (unsigned)a.blocks);
+    const uint8_t* msk = tile_mask(mk, tile, a.pixels);
+    const int64_t p_begin = (int64_t)chunk_id * kQuantPixels;
+    const int64_t p_end = min(p_begin + (int64_t)kQuantPixels, a.pixels);
+    const T* img = images + tile * 3 * a.pixels;
+
+    int64_t p = p_begin + (int64_t)threadIdx.x * V;
+    float u[3][V];
+    MaskPack<V> mp;
+    mp.clear();
+    if (p < p_end) {
+        deconv_load<T, V, kInter>(img, a.pixels, p, u);
+        if constexpr (kMask) mp.load(msk + p);
+    }
+
+    if (threadIdx.x == 0) {
+        const float* b_src = a.basis + (a.per_basis ? tile * 9 : 0);
+        double inv[9];
+        deconv_inverse(b_src, inv);
+        ConcFold::fill(inv, fold);
+        fold[12] = deconv_row_has_nan(b_src) ? 1.0f : 0.0f;
+    }
+    tb.fill();
+    __syncthreads();
+    if (fold[12] != 0.0f) return;      // (uniform over the workgroup; the output is zero already)
+    ConcFold cf;
+    cf.read(fold);
+
+    long long acc[kMomentWords] = {0ll, 0ll, 0ll, 0ll, 0ll, 0ll, 0ll};
+    while (p < p_end) {
+        const int64_t p_next = p + (int64_t)TPB * V;
+        const bool more = p_next < p_end;
+        float un[3][V];
+        MaskPack<V> mn;
+        mn.clear();
+        if (more) {      // (the next pack set is on its way while this one is summed)
+            deconv_load<T, V, kInter>(img, a.pixels, p_next, un);
+            if constexpr (kMask) mn.load(msk + p_next);
+        }
+        uint32_t in_bits = ~0u;
+        if constexpr (kMask) in_bits = mp.bits();
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            float l[3], c[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) l[k] = l2_of<T>(u[k][i], tb);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) c[s] = cf.of(s, l[0], l[1], l[2]);
+            constexpr float kInf = __builtin_huge_valf();
+            const bool ok = in_mask(in_bits, i) && fabsf(c[0]) < kInf && fabsf(c[1]) < kInf && fabsf(c[2]) < kInf;
+            if (ok) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const float t = rintf(c[s] * 65536.0f);
+                    const int term = t >= 2147483648.0f ? 2147483647 : (t <= -2147483648.0f ? (-2147483647 - 1) : (int)t);      // v_cvt_i32_f32's saturation, spelled out
+                    const long long uu = (long long)min(max(term, -kMomentClamp), kMomentClamp);
+                    acc[s] += (long long)term;
+                    acc[3 + s] += (uu * uu) >> 8;      // (at most 2^44 >> 8: non-negative, the shift is the floor)
+                }
+                acc[6] += 1ll;
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int i = 0; i < V; ++i) u[k][i] = un[k][i];
+            mp = mn;
+        }
+        p = p_next;
+    }
+    // (every thread arrives here: a thread without a pack holds zeros)
+    // wave_sum_i64: 64-bit shuffles, two LDS round trips a step.  The DPP reductions of common.hpp are 32-bit; a 64-bit sum on them needs the
+    // carry between the halves at every step.  Seven reductions per wave and WORK ITEM (8192 pixels), independent of each other; not timed on their own.
+    const int wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int k = 0; k < kMomentWords; ++k) {
+        const long long total = wave_sum_i64(acc[k]);
+        if (lane_id() == 0) red[wave][k] = total;
+    }
+    __syncthreads();
+    if (threadIdx.x < kMomentWords) {
+        long long total = 0ll;
+#pragma unroll
+        for (int wv = 0; wv < kWaves; ++wv) total += red[wv][threadIdx.x];
+        unsigned long long* row = a.out + (a.per_tile ? tile : 0) * kMomentWords;
+        if (total != 0ll) atomicAdd(&row[threadIdx.x], (unsigned long long)total);      // (two's complement: the 64-bit add is the signed add)
+    }
+}
+
 // ---- host side: the parents' pack rules (16 bytes of output per lane and plane: VR; one pack set per work item on the vector paths,
 // four for one-byte output, sixteen sweeps on the scalar path) ----
 template <typename T, typename O, int V, bool kUnit, bool kInter, bool kMask = false>
@@ -585,6 +702,28 @@ static int deconv_quantify_typed(const void* images, const QuantArgs& a, bool in
     const T* in = static_cast<const T*>(images);
     if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
     return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) { return run_deconv_quantify<T, decltype(v)::value, decltype(inter)::value, kMask>(in, a, stream, mk); });
+}
+
+// The zeroes of a call on a stream that is being CAPTURED: a clearing launch instead of the memset.  (What a memset node of a captured
+// graph writes on replay depends, with HIP 7.0 / ROCm 7.2 on gfx950, on what was launched since the previous replay: tools/probe_graph_memset.py,
+// profiles/graph_memset_probe.txt.  A kernel node replays its own arguments.  DESIGN.md 4q.)
+__global__ void moments_clear_kernel(unsigned long long* __restrict__ out, int64_t words) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < words) out[i] = 0ull;
+}
+
+// (quantify's work items and pack rule)
+template <typename T, bool kMask = false>
+static int deconv_moments_typed(const void* images, MomentArgs a, bool interleaved, hipStream_t stream, MaskArgs<kMask> mk = MaskArgs<kMask>{}) {
+    constexpr int W = PackOf<T>::n;
+    bool vec = (a.pixels % W == 0) && aligned_for(images, 16);
+    const T* in = static_cast<const T*>(images);
+    if constexpr (kMask) vec = vec && aligned_for(mk.mask, W);
+    a.blocks = (int)((a.pixels + kQuantPixels - 1) / kQuantPixels);
+    return with_layout<W, kMask>(vec, interleaved, [&](auto v, auto inter) {
+        hipLaunchKernelGGL((deconv_moments_kernel<T, decltype(v)::value, decltype(inter)::value, kMask>), dim3((unsigned)(a.n_tiles * a.blocks)), dim3(kStreamThreads), 0, stream, in, a, mk);
+        return check_launch("deconv moments");
+    });
 }
 
 }  // namespace macenko
@@ -730,4 +869,48 @@ extern "C" int sx_deconv_quantify(const void* images, int dtype, int64_t n, int6
 extern "C" int sx_deconv_quantify_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int bin_log2, int zero_bin, int per_tile,
                                          long long* out, const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
     return deconv_quantify_call<true>(images, dtype, n, h, w, basis, n_bases, bin_log2, zero_bin, per_tile, out, mask_dev, flags, stream_ptr);
+}
+
+template <bool kMask>
+static int deconv_moments_call(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int per_tile, long long* out,
+                               const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
+    const char* who = kMask ? "sx_deconv_moments_masked" : "sx_deconv_moments";
+    int rc = deconv_common_ok(images, n, h, w, basis, n_bases, "images");
+    if (rc != SX_OK) return rc;
+    if (!out) return fail(SX_ERR_BAD_ARG, "out pointer is null");
+    if (kMask && (rc = check_mask(mask_dev)) != SX_OK) return rc;
+    if (kMask && (flags & SX_MACENKO_CHANNELS_LAST)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes planar (N,3,H,W) tiles only (no SX_MACENKO_CHANNELS_LAST)", flags, who);
+    if (flags & ~(SX_MACENKO_CHANNELS_LAST | SX_MACENKO_CLASSIC)) return fail(SX_ERR_BAD_ARG, "flags 0x%x: %s takes SX_MACENKO_CHANNELS_LAST and SX_MACENKO_CLASSIC only (there is no output image)", flags, who);
+    MomentArgs a{};
+    a.basis = basis;
+    a.out = reinterpret_cast<unsigned long long*>(out);
+    a.pixels = h * w;
+    a.n_tiles = n;
+    a.per_basis = n_bases == n && n != 1 ? 1 : 0;
+    a.per_tile = per_tile ? 1 : 0;
+    const bool inter = (flags & SX_MACENKO_CHANNELS_LAST) != 0;
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    if ((rc = dtype_ok(dtype)) != SX_OK) return rc;      // (before anything is enqueued)
+    const int64_t words = (per_tile ? n : 1) * (int64_t)kMomentWords;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capture) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipStreamIsCapturing failed");
+    if (capture == hipStreamCaptureStatusNone) {
+        if (hipMemsetAsync(out, 0, (size_t)words * sizeof(unsigned long long), stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    } else {      // (see moments_clear_kernel)
+        hipLaunchKernelGGL(moments_clear_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, a.out, words);
+        if ((rc = check_launch("deconv moments (clear)")) != SX_OK) return rc;
+    }
+    MaskArgs<kMask> mk{};
+    if constexpr (kMask) mk.mask = mask_dev;
+    return with_dtype(dtype, [&](auto t) { return deconv_moments_typed<typename decltype(t)::type, kMask>(images, a, inter, stream, mk); });
+}
+
+extern "C" int sx_deconv_moments(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int per_tile, long long* out, unsigned flags,
+                                 void* stream_ptr) {
+    return deconv_moments_call<false>(images, dtype, n, h, w, basis, n_bases, per_tile, out, nullptr, flags, stream_ptr);
+}
+
+extern "C" int sx_deconv_moments_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const float* basis, int64_t n_bases, int per_tile, long long* out,
+                                        const unsigned char* mask_dev, unsigned flags, void* stream_ptr) {
+    return deconv_moments_call<true>(images, dtype, n, h, w, basis, n_bases, per_tile, out, mask_dev, flags, stream_ptr);
 }

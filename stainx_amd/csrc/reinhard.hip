@@ -559,6 +559,47 @@ __global__ __launch_bounds__(kStreamThreads) void apply_stats_masked_kernel(cons
     apply_chunk<T, V, true>(images, out, g, src_mean + row * 3, src_std + row * 3, ref_mean, ref_std, Codes{nullptr, nullptr, 0u}, [] {}, tis);
 }
 
+// sx_reinhard_apply_targets / _targets_masked: a TARGET row per tile as well (per_target == 1: row `tile`, 0: row 0), and a tile any of
+// whose four rows holds a NaN is copied with the bits of its input -- one workgroup-uniform branch in front of the first pixel, in the
+// unmasked form too.  Every other tile runs apply_chunk as the kernels above do: with one finite target row the bits are theirs.
+__device__ __forceinline__ bool rows_have_nan(const float* sm, const float* ss, const float* tm, const float* ts) {
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bad = bad || sm[c] != sm[c] || ss[c] != ss[c] || tm[c] != tm[c] || ts[c] != ts[c];
+    return bad;
+}
+template <typename T, int V>
+__device__ __forceinline__ void copy_chunk(const T* images, T* out, Geometry g) {
+    const int64_t tile = blockIdx.x / g.blocks_per_tile;
+    const int chunk_id = blockIdx.x % g.blocks_per_tile;
+    const int64_t p_begin = (int64_t)chunk_id * g.chunk, p_end = min(p_begin + g.chunk, g.pixels);
+    const T* img = images + tile * 3 * g.pixels;
+    T* dst = out + tile * 3 * g.pixels;
+    for (int64_t p = p_begin + (int64_t)threadIdx.x * V; p < p_end; p += (int64_t)kStreamThreads * V) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if constexpr (V == 1) {
+                dst[c * g.pixels + p] = img[c * g.pixels + p];
+            } else {
+                const Pack<T, V> pk = load_pack_stream<T, V>(img + c * g.pixels + p);
+                store_pack_stream<T, V>(dst + c * g.pixels + p, pk.v);
+            }
+        }
+    }
+}
+template <typename T, int V, bool kMasked>
+__global__ __launch_bounds__(kStreamThreads) void apply_targets_kernel(const T* __restrict__ images, T* __restrict__ out, Geometry g, const float* __restrict__ src_mean, const float* __restrict__ src_std, int per_tile, const float* __restrict__ tgt_mean, const float* __restrict__ tgt_std, int per_target, tissue::Source tis) {
+    const int64_t tile = blockIdx.x / g.blocks_per_tile;
+    const int64_t row = per_tile ? tile : 0, trow = per_target ? tile : 0;
+    const float *sm = src_mean + row * 3, *ss = src_std + row * 3, *tm = tgt_mean + trow * 3, *ts = tgt_std + trow * 3;
+    if (rows_have_nan(sm, ss, tm, ts)) {      // (uniform over the workgroup: the rows are the tile's)
+        copy_chunk<T, V>(images, out, g);
+        return;
+    }
+    if constexpr (kMasked) apply_chunk<T, V, true>(images, out, g, sm, ss, tm, ts, Codes{nullptr, nullptr, 0u}, [] {}, tis);
+    else apply_chunk<T, V>(images, out, g, sm, ss, tm, ts, Codes{nullptr, nullptr, 0u}, [] {});
+}
+
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // Sweeps of a workgroup per work item: eight on a batch that fills the chip (64 tiles of 512 x 512: 2048 work items), fewer on small
 // ones -- a single 512 x 512 tile is 32 work items at eight sweeps and two launches that last as long as ONE of them; at one sweep
@@ -817,6 +858,19 @@ static int run_apply_stats_masked(const void* images, void* out, int64_t n, int6
     return check_launch("reinhard (given statistics, tissue mask)");
 }
 
+// a target row per tile: the geometry and the pack rule of the two calls above, one launch
+template <typename T, bool kMasked>
+static int run_apply_targets(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* tgt_mean, const float* tgt_std, int per_target, tissue::Source tis, hipStream_t stream) {
+    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
+    const bool vec = kMasked ? masked_vector_path<T>(images, out, tis.mask, g.pixels) : vector_path<T>(images, out, g.pixels);
+    if (vec)
+        hipLaunchKernelGGL((apply_targets_kernel<T, 4, kMasked>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, tgt_mean, tgt_std, per_target, tis);
+    else
+        hipLaunchKernelGGL((apply_targets_kernel<T, 1, kMasked>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, tgt_mean, tgt_std, per_target, tis);
+    return check_launch(kMasked ? "reinhard (targets per tile, tissue mask)" : "reinhard (targets per tile)");
+}
+
 // sx_tissue_mask: the rule as a call of its own.  Workgroup b takes share b % blocks_per_tile of tile b / blocks_per_tile; a thread a pack
 // of four pixels (planar tiles of whole packs at aligned addresses) or single pixels; mask bytes 1 / 0 and the tile's tissue count.
 constexpr int kMaskBlocksPerTile = 64;
@@ -1001,6 +1055,29 @@ extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int
     const int per_tile = n_sources == n && n != 1 ? 1 : 0;
     const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(luminosity_threshold)};
     return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_stats_masked<typename decltype(t)::type>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream); });
+}
+
+// ---- a target per tile (statistics-space augmentation, Reinhard to per-tile / per-slide targets without a fit) ------------------------------
+template <bool kMasked>
+static int apply_targets_call(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* target_mean, const float* target_std, int64_t n_targets, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
+    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
+    if (!source_mean || !source_std || !target_mean || !target_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / target_mean / target_std pointer is null");
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
+    if (n_targets != 1 && n_targets != n) return fail(SX_ERR_BAD_ARG, "n_targets must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_targets);
+    if (kMasked && !mask && !tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
+    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
+    const int per_tile = n_sources == n && n != 1 ? 1 : 0, per_target = n_targets == n && n != 1 ? 1 : 0;
+    const tissue::Source tis{mask, kMasked && !mask ? tissue::y_cut_of(luminosity_threshold) : 0.0f};
+    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_targets<typename decltype(t)::type, kMasked>(images, out, n, h, w, source_mean, source_std, per_tile, target_mean, target_std, per_target, tis, stream); });
+}
+
+extern "C" int sx_reinhard_apply_targets(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* target_mean, const float* target_std, int64_t n_targets, void* stream_ptr) {
+    return apply_targets_call<false>(images, out, dtype, n, h, w, source_mean, source_std, n_sources, target_mean, target_std, n_targets, nullptr, 0.0, stream_ptr);
+}
+
+extern "C" int sx_reinhard_apply_targets_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* target_mean, const float* target_std, int64_t n_targets, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
+    return apply_targets_call<true>(images, out, dtype, n, h, w, source_mean, source_std, n_sources, target_mean, target_std, n_targets, mask, luminosity_threshold, stream_ptr);
 }
 
 // ---- tissue detection: luminosity histograms (for Otsu thresholds), per-tile cuts, binary morphology on masks ------------------------------

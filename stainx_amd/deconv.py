@@ -209,6 +209,99 @@ class StainHistograms(NamedTuple):
         return torch.where(self.pixels > 0, value, torch.full_like(value, float("nan")))
 
 
+class ConcentrationStatistics(NamedTuple):
+    """What ``ColorDeconvolution.estimate`` returns: exact integer moments of the three stain concentrations of a batch, taken in one
+    streaming launch -- no concentration map is written.  ``sums``: (S, 3) int64, the sum of the concentrations in fixed point (units of
+    2^-16, ``quantify``'s sums); ``squares``: (S, 3) int64, the sum of their squares (units of 2^-24, each pixel's term floored; a
+    concentration beyond +-64 enters as 64); ``pixels``: (S,) int64, the pixels counted (finite concentrations, and inside the mask if
+    there is one).  S = N for a set per tile, 1 for one set pooled over the batch.
+
+    Integers throughout: the same run to run, and sets of different tiles, batches, slides or ranks ADD UP EXACTLY (:meth:`pool`, or
+    ``all_reduce`` (SUM) on the three tensors).  :meth:`mean` and :meth:`std` are float64 torch ops where the tensors live (no
+    synchronisation)."""
+
+    sums: torch.Tensor
+    squares: torch.Tensor
+    pixels: torch.Tensor
+
+    @staticmethod
+    def pool(*items: "ConcentrationStatistics") -> "ConcentrationStatistics":
+        """One set, (1, 3), (1, 3) and (1,): the sum of every set of every argument (exact)."""
+        if not items:
+            raise ValueError("pool needs at least one ConcentrationStatistics")
+        sums = squares = pixels = None
+        for item in items:
+            if not isinstance(item, ConcentrationStatistics):
+                raise ValueError(f"pool takes ConcentrationStatistics, got {type(item).__name__}")
+            s, q, p = item.sums.sum(dim=0, keepdim=True), item.squares.sum(dim=0, keepdim=True), item.pixels.sum(dim=0, keepdim=True)
+            sums, squares, pixels = (s, q, p) if sums is None else (sums + s, squares + q, pixels + p)
+        return ConcentrationStatistics(sums, squares, pixels)
+
+    def _mean_std(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(mean(), std())`` in one go (the two share half of their operations)."""
+        p = self.pixels.to(torch.float64).unsqueeze(-1)
+        some = p.clamp(min=1.0)
+        s = self.sums.to(torch.float64) * (1.0 / 65536.0)      # (a power of two: the product is the quotient)
+        q = self.squares.to(torch.float64) * (1.0 / 16777216.0)
+        mean = s / some
+        var = (q - s * mean) / (some - 1.0).clamp(min=1.0)
+        sd = torch.sqrt(var.clamp(min=0.0))
+        none = p < 2.0
+        return mean.masked_fill(none, float("nan")), sd.masked_fill(none, float("nan"))
+
+    def mean(self) -> torch.Tensor:
+        """(S, 3) float64: the mean concentration of each stain over the counted pixels, ``sums / 2^16 / pixels``; NaN where fewer than
+        two pixels were counted (a set without statistics, as ``Reinhard.estimate``'s NaN rows)."""
+        return self._mean_std()[0]
+
+    def std(self) -> torch.Tensor:
+        """(S, 3) float64: the unbiased standard deviation, ``sqrt((squares / 2^24 - (sums / 2^16) mean) / (pixels - 1))`` (a negative
+        difference -- the floor of the squares on a constant tile -- counts as 0); NaN where fewer than two pixels were counted."""
+        return self._mean_std()[1]
+
+
+def _statistics_rows(value: Any, n: int, what: str) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(mean, std)`` of a ``ConcentrationStatistics`` or a given pair, each (3,), (1, 3) or (N, 3): checked by shape only (no GPU work)."""
+    if isinstance(value, ConcentrationStatistics):
+        rows = tuple(value.pixels.shape)
+        if len(rows) != 1 or rows[0] not in (1, n) or tuple(value.sums.shape) != (rows[0], 3) or tuple(value.squares.shape) != (rows[0], 3):
+            raise ValueError(f"{what} holds {rows} sets for a batch of {n} tiles (one set, or one per tile)")
+        return value._mean_std()
+    if not isinstance(value, (tuple, list)) or len(value) != 2:
+        raise ValueError(f"{what} must be a ConcentrationStatistics or a (mean, std) pair")
+    shapes = []
+    for name, t in (("mean", value[0]), ("std", value[1])):
+        shape = tuple(getattr(t, "shape", ()))
+        if not isinstance(t, torch.Tensor) or not (shape == (3,) or (len(shape) == 2 and shape[1] == 3 and shape[0] in (1, n))):
+            raise ValueError(f"{what} {name} must be a tensor of shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
+        shapes.append(1 if len(shape) == 1 else shape[0])
+    if shapes[0] != shapes[1]:
+        raise ValueError(f"{what} mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
+    return value[0], value[1]
+
+
+def check_gain_range(gain_range: Any) -> tuple[float, float]:
+    try:
+        lo, hi = (float(g) for g in gain_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"gain_range must be a pair (low, high) with 0 < low <= high, got {gain_range!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError(f"gain_range must be a pair (low, high) with 0 < low <= high, got {gain_range!r}")
+    return lo, hi
+
+
+def match_factors(source_mean: torch.Tensor, source_std: torch.Tensor, target_mean: torch.Tensor, target_std: torch.Tensor, n: int,
+                  gain_range: tuple[float, float]) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(alpha, beta)``, (n, 3) float32 each, where the statistics live: ``alpha = clamp(target_std / source_std, gain_range)``,
+    ``beta = target_mean - alpha * source_mean``, in float32.  A tile whose source row holds a NaN or a zero standard deviation -- or
+    whose target row holds a NaN -- gets ``alpha = 1, beta = 0`` for all three stains.  Plain torch ops, no synchronisation."""
+    sm, ss, tm, ts = (t.to(torch.float32).reshape(-1, 3).expand(n, 3) for t in (source_mean, source_std, target_mean, target_std))
+    alpha = torch.clamp(ts / ss, gain_range[0], gain_range[1])
+    beta = tm - alpha * sm
+    leave = (torch.isnan(torch.cat([sm, ss, tm, ts], dim=1)).any(dim=1, keepdim=True)) | (ss == 0).any(dim=1, keepdim=True)
+    return alpha.masked_fill(leave, 1.0), beta.masked_fill(leave, 0.0)
+
+
 def _cuda_device(device: Any, fallback: torch.device, who: str) -> torch.device:
     device = torch.device(device) if device is not None else fallback
     if device.type != "cuda":
@@ -346,6 +439,44 @@ class ColorDeconvolution:
         counts, sums, pixels = self._engine(device).quantify(batch, self._bases_on(device)[0], bin_log2=bin_log2, zero_bin=zero_bin, per_tile=not pooled,
                                                              channels_last=self.channels_last, masking=(explicit, self.luminosity_threshold) if masked else None)
         return StainHistograms(counts, sums, pixels, bin_log2, zero_bin)
+
+    def estimate(self, x: torch.Tensor, *, pooled: bool = False, mask: Any = None) -> ConcentrationStatistics:
+        """The statistics pass of the stain space: exact integer sums and sums of squares of the three concentrations
+        ``separate(x, concentrations=True)`` would write (bit for bit those values) and the counted pixels -- a set per tile, or one set
+        ``pooled`` over the batch -- in ONE streaming launch that reads a pixel once and writes no map (include/stainx_hip.h:
+        sx_deconv_moments).  ``mask``: as in ``apply`` -- only masked-in pixels count.  See ``ConcentrationStatistics``."""
+        batch, single = self._batch(x, "estimate")
+        n, h, w = self._dims(batch)
+        self._rows_ok(n)
+        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
+        if masked and self.channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        return ConcentrationStatistics(*self._engine(device).moments(batch, self._bases_on(device)[0], per_tile=not pooled, channels_last=self.channels_last,
+                                                                     masking=(explicit, self.luminosity_threshold) if masked else None))
+
+    def match(self, x: torch.Tensor, source: Any, target: Any, *, mask: Any = None, gain_range: tuple[float, float] = (0.1, 2.5)) -> torch.Tensor:
+        """Mean / standard deviation matching of the concentrations ("Reinhard in stain space"): ``C' = alpha * C + beta`` with
+        ``alpha = clamp(target_std / source_std, gain_range)`` and ``beta = target_mean - alpha * source_mean`` per tile and stain, then
+        ``apply``: one launch.  ``source`` / ``target``: a ``ConcentrationStatistics`` (``estimate``'s) or a ``(mean, std)`` pair of
+        (3,), (1, 3) or (N, 3) tensors.  The factors are computed in float32 on the device: no synchronisation, the call is capturable.  A
+        tile whose source row holds a NaN or a zero standard deviation (or whose target row holds a NaN) is mapped with ``alpha = 1,
+        beta = 0``."""
+        batch, single = self._batch(x, "match")
+        n, h, w = self._dims(batch)
+        gain_range = check_gain_range(gain_range)
+        self._rows_ok(n)
+        masked, _ = masks.resolve(self.mask, mask.unsqueeze(0) if single and isinstance(mask, torch.Tensor) and mask.dim() == 2 else mask, n, h, w,
+                                  self.device if self.device is not None else batch.device)
+        if masked and self.channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        sm, ss = _statistics_rows(source, n, "source")
+        tm, ts = _statistics_rows(target, n, "target")
+        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        alpha, beta = match_factors(sm.to(device), ss.to(device), tm.to(device), ts.to(device), n, gain_range)
+        return self.apply(x, alpha, beta, mask=mask)
 
     def combine(self, concentrations: torch.Tensor, out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
         """``separate``'s inverse: (N, 3, H, W) float32 concentrations -> tiles of ``out_dtype``, rebuilt with ``basis``."""

@@ -103,27 +103,42 @@ class Reinhard(NormalizerTemplate):
             return ColorStatistics(mean.reshape(1, 3), std.reshape(1, 3))
         return ColorStatistics(*engine.tile_statistics(images))
 
-    def apply(self, images: Any, source: Any, mask: Any = None) -> Any:
-        """Normalise ``images`` (NCHW) to the fitted reference with GIVEN source statistics: one kernel launch, a pixel read and a pixel
-        written (include/stainx_hip.h: sx_reinhard_apply_stats).  ``source``: a ``ColorStatistics`` or a ``(mean, std)`` pair -- (3,),
-        (1, 3) (one set for the batch) or (N, 3) (row t serves tile t).  With a mask (the normaliser's rule, or ``mask=`` for this call)
-        still one launch: tissue pixels get exactly the unmasked result, background pixels -- and tiles whose row holds a NaN -- are copied."""
-        if not self._is_fitted:
-            raise ValueError("Must call fit() before transform()")
-        n = self._check_images(images, "apply")[0]
-        masked, explicit = self._masking(images, mask, "apply")
-        if isinstance(source, (tuple, list)) and len(source) == 2:      # (a ColorStatistics is a tuple of two)
-            mean, std = source
+    @staticmethod
+    def _check_rows(pair: Any, n: int, what: str) -> tuple:
+        if isinstance(pair, (tuple, list)) and len(pair) == 2:      # (a ColorStatistics is a tuple of two)
+            mean, std = pair
         else:
-            raise ValueError("source must be a ColorStatistics or a (mean, std) pair")
+            raise ValueError(f"{what} must be a ColorStatistics or a (mean, std) pair")
         shapes = []
         for name, value in (("mean", mean), ("std", std)):
             shape = tuple(getattr(value, "shape", ()))
             if not (shape == (3,) or (len(shape) == 2 and shape[1] == 3 and shape[0] in (1, n))):
-                raise ValueError(f"source {name} must have shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
+                raise ValueError(f"{what} {name} must have shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
             shapes.append(1 if len(shape) == 1 else shape[0])
         if shapes[0] != shapes[1]:
-            raise ValueError(f"source mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
+            raise ValueError(f"{what} mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
+        return mean, std
+
+    def apply(self, images: Any, source: Any, mask: Any = None, *, target: Any = None) -> Any:
+        """Normalise ``images`` (NCHW) to the fitted reference with GIVEN source statistics: one kernel launch, a pixel read and a pixel
+        written (include/stainx_hip.h: sx_reinhard_apply_stats).  ``source``: a ``ColorStatistics`` or a ``(mean, std)`` pair -- (3,),
+        (1, 3) (one set for the batch) or (N, 3) (row t serves tile t).  With a mask (the normaliser's rule, or ``mask=`` for this call)
+        still one launch: tissue pixels get exactly the unmasked result, background pixels -- and tiles whose row holds a NaN -- are copied.
+
+        ``target`` (a ``ColorStatistics`` or ``(mean, std)`` pair of the same shapes): normalise to THESE statistics instead of the
+        fitted reference -- a target per tile or per slide, no ``fit()`` needed; still one launch (sx_reinhard_apply_targets).  With one
+        finite target row the bits are those of the fitted path with that reference; a tile whose source or target row holds a NaN is
+        copied bit for bit, masked or not."""
+        if target is None and not self._is_fitted:
+            raise ValueError("Must call fit() before transform()")
+        n = self._check_images(images, "apply")[0]
+        masked, explicit = self._masking(images, mask, "apply")
+        mean, std = self._check_rows(source, n, "source")
+        if target is not None:
+            t_mean, t_std = self._check_rows(target, n, "target")
+            if masked:
+                return self._get_backend_impl().apply_targets_masked(images, mean, std, t_mean, t_std, explicit, self.luminosity_threshold)
+            return self._get_backend_impl().apply_targets(images, mean, std, t_mean, t_std)
         if masked:
             return self._get_backend_impl().apply_statistics_masked(images, mean, std, *self.arguments(), explicit, self.luminosity_threshold)
         return self._get_backend_impl().apply_statistics(images, mean, std, *self.arguments())
