@@ -80,10 +80,38 @@ static int with_layout(bool vec, bool interleaved, F&& f) {
     return vec ? f(int_constant<W>{}, std::false_type{}) : f(int_constant<1>{}, std::false_type{});
 }
 
+// f(std::bool_constant<a>{}, std::bool_constant<b>{}): two flags of a kernel (packs x channels-last, packs x per tile), all four pairs;
+// what f returns (a launch: nothing).
+template <typename F>
+static auto with_flags(bool a, bool b, F&& f) {
+    if (a) return b ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return b ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+
 // ---- argument checks the entry points share ---------------------------------------------------------------------------------------
 static inline int check_tiles(int64_t n, int64_t h, int64_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
     if (n * h * w >= (1ll << 32)) return fail(SX_ERR_BAD_ARG, "N*H*W must be below 2^32 pixels");
+    return SX_OK;
+}
+// (the Reinhard and the histogram-matching calls: their own two texts, and no limit on the pixels of a call)
+static inline int check_sizes(int64_t n, int64_t h, int64_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
+    return SX_OK;
+}
+static inline int check_sizes_got(int64_t n, int64_t h, int64_t w) {
+    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    return SX_OK;
+}
+// rows given per call: one for the batch, or one per tile
+static inline int check_rows(const char* name, int64_t rows, int64_t n) {
+    if (rows != 1 && rows != n) return fail(SX_ERR_BAD_ARG, "%s must be 1 or n_tiles (%lld), got %lld", name, (long long)n, (long long)rows);
+    return SX_OK;
+}
+static inline int rows_per_tile(int64_t rows, int64_t n) { return rows == n && n != 1 ? 1 : 0; }
+static inline int check_workspace(const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
     return SX_OK;
 }
 static inline int check_mask(const void* mask) {

@@ -74,34 +74,16 @@ __device__ __forceinline__ uint32_t grey_level(T v) {
 
 template <typename T> struct VecOf { static constexpr int n = 16 / sizeof(T); };   // elements per 16-byte load
 
-template <typename T, bool kVec>
+// single elements (the calls that take packs count with histogram_planar_kernel / histogram_last_kernel)
+template <typename T>
 __global__ __launch_bounds__(kThreads) void histogram_kernel(const T* __restrict__ images, Layout lay, uint32_t* __restrict__ counts) {
     __shared__ uint32_t hist[kWaves][3][kBins];
     for (int i = threadIdx.x; i < kWaves * 3 * kBins; i += kThreads) (&hist[0][0][0])[i] = 0;
     __syncthreads();
     uint32_t(*mine)[kBins] = hist[threadIdx.x / kWave];
     const int64_t total = lay.elements();
-    constexpr int V = kVec ? VecOf<T>::n : 1;
-    const int64_t stride = (int64_t)gridDim.x * kThreads * V;
-    for (int64_t e = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * V; e < total; e += stride) {
-        if constexpr (kVec) {
-            const Pack<T, V> pk = *reinterpret_cast<const Pack<T, V>*>(images + e);
-            if (lay.channels_last) {
-                int c = (int)(e % 3);
-#pragma unroll
-                for (int i = 0; i < V; ++i) {
-                    atomicAdd(&mine[c][grey_level<T>(pk.v[i])], 1u);
-                    c = c == 2 ? 0 : c + 1;
-                }
-            } else {
-                const int c = lay.channel_of(e);          // pixels % V == 0: a pack never straddles planes
-#pragma unroll
-                for (int i = 0; i < V; ++i) atomicAdd(&mine[c][grey_level<T>(pk.v[i])], 1u);
-            }
-        } else {
-            atomicAdd(&mine[lay.channel_of(e)][grey_level<T>(images[e])], 1u);
-        }
-    }
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += stride) atomicAdd(&mine[lay.channel_of(e)][grey_level<T>(images[e])], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < 3 * kBins; i += kThreads) {
         uint32_t s = 0;
@@ -839,21 +821,62 @@ static bool run_resident(const uint8_t* images, uint8_t* out, int64_t n, int64_t
 }
 #endif
 
+// The per-tile calls (and sx_hm_estimate, pooled or not): the per-tile areas behind the Tables.  The masked calls: behind the Tables one
+// tissue counter per set, then the per-tile areas of `sets` sets (a pooled call: one set).  One clear covers the pooled live counters, the
+// status word, (masked) the tissue counters and the sets' live counters: any contents in, READY out.
+static size_t tiles_workspace_bytes(int64_t n) { return workspace_bytes() + tile_area_bytes(n); }
+static size_t masked_tissue_bytes(int64_t n) { return (sizeof(uint32_t) * (size_t)n + 255) / 256 * 256; }
+static size_t masked_workspace_bytes(int64_t n) { return workspace_bytes() + masked_tissue_bytes(n) + tile_area_bytes(n); }
+static int clear_counters(Tables* tab, size_t behind_tables, hipStream_t stream) {
+    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + behind_tables, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    return SX_OK;
+}
+
+// 16-byte packs: the images and (where there is one) the output at 16-byte aligned addresses, and whole packs in what a pack must not
+// leave -- a channel plane of a planar tile; of channels-last tiles the batch, or the tile where the call keeps tiles apart
+// (within_tile); with a mask the pixels of a tile in both layouts, and a pack's mask bytes aligned.  Single elements otherwise.
+template <typename T>
+static bool vector_path(const Layout& lay, const void* images, const void* out, bool within_tile, bool masked = false, const uint8_t* mask = nullptr) {
+    constexpr int V = VecOf<T>::n;
+    const auto aligned = [](const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; };      // (a null pointer: no such operand)
+    const int64_t whole = (masked || !lay.channels_last) ? lay.pixels : (within_tile ? 3 * lay.pixels : lay.elements());
+    return aligned(images, 16) && aligned(out, 16) && whole % V == 0 && aligned(mask, V);
+}
+
+// The histogram pass of the unmasked calls: planar packs, channels-last packs or single elements, into the pooled counters or (kPerTile)
+// the tiles' own.
+template <typename T, bool kPerTile>
+static void histogram_pass(const T* in, const Layout& lay, bool vec, uint32_t* counts, hipStream_t stream) {
+    const int64_t n = lay.n_tiles, per_tile = 3 * lay.pixels, total = lay.elements();
+    if (vec && !lay.channels_last) {
+        const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
+        hipLaunchKernelGGL((histogram_planar_kernel<T, kPerTile>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, counts);
+    } else if (vec) {
+        const int chunks_per_tile = kPerTile ? (int)((per_tile + kLastChunk - 1) / kLastChunk) : 1;
+        const unsigned grid = kPerTile ? (unsigned)(n * chunks_per_tile) : (unsigned)((total + kLastChunk - 1) / kLastChunk);
+        hipLaunchKernelGGL((histogram_last_kernel<T, kPerTile>), dim3(grid), dim3(kThreads), 0, stream, in, kPerTile ? per_tile : total, counts, chunks_per_tile);
+    } else if constexpr (kPerTile) {
+        const int blocks_per_tile = (int)std::min<int64_t>((per_tile + kThreads * 4 - 1) / (kThreads * 4), 64);
+        hipLaunchKernelGGL((histogram_tile_kernel<T>), dim3((unsigned)(n * blocks_per_tile)), dim3(kThreads), 0, stream, in, lay, blocks_per_tile, counts);
+    } else {
+        const unsigned grid = (unsigned)std::min<int64_t>((total + kThreads * 4 - 1) / (kThreads * 4), 256 * 8);
+        hipLaunchKernelGGL((histogram_kernel<T>), dim3(grid), dim3(kThreads), 0, stream, in, lay, counts);
+    }
+}
+
 template <typename T>
 static int run(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, unsigned long long* counts_out, const unsigned long long* counts_in, double n_total, void* ws, hipStream_t stream, bool ready) {
-    Layout lay{n, h * w, channels_last};
+    const Layout lay{n, h * w, channels_last};
     Tables* tab = static_cast<Tables*>(ws);
     const T* in = static_cast<const T*>(images);
-    constexpr int V = VecOf<T>::n;
-    const int64_t total = lay.elements();
-    // vector path: 16-byte aligned base, and a pack never crosses a channel plane
-    const bool vec = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (!out || reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
-                     (channels_last ? (total % V == 0) : (lay.pixels % V == 0));
-    const int64_t per_block = (int64_t)kThreads * (vec ? V : 1) * 4;
-    const unsigned grid = (unsigned)std::min<int64_t>((total + per_block - 1) / per_block, 256 * 8);
+    const bool vec = vector_path<T>(lay, images, out, /*within_tile=*/false);
+    const int64_t per_block = (int64_t)kThreads * (vec ? VecOf<T>::n : 1) * 4;
+    const unsigned grid = (unsigned)std::min<int64_t>((lay.elements() + per_block - 1) / per_block, 256 * 8);
     double lut_pixels = n_total;
     if (!counts_in) {
-        if (!ready && hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts), stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+        if (!ready) {
+            if (const int rc = clear_counters(tab, 0, stream)) return rc;
+        }
 #ifdef SX_DIAG
         if constexpr (std::is_same<T, uint8_t>::value) {
             static const int mode = [] { const char* e = std::getenv("SX_HM_RESIDENT"); return e ? std::atoi(e) : 1; }();
@@ -862,15 +885,7 @@ static int run(const void* images, void* out, int64_t n, int64_t h, int64_t w, i
             }
         }
 #endif
-        if (vec && !channels_last) {
-            const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
-            hipLaunchKernelGGL((histogram_planar_kernel<T>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, &tab->counts[0][0]);
-        } else if (vec && channels_last) {
-            hipLaunchKernelGGL((histogram_last_kernel<T>), dim3((unsigned)((total + kLastChunk - 1) / kLastChunk)), dim3(kThreads), 0, stream, in, total, &tab->counts[0][0]);
-        } else if (vec)
-            hipLaunchKernelGGL((histogram_kernel<T, true>), dim3(grid), dim3(kThreads), 0, stream, in, lay, &tab->counts[0][0]);
-        else
-            hipLaunchKernelGGL((histogram_kernel<T, false>), dim3(grid), dim3(kThreads), 0, stream, in, lay, &tab->counts[0][0]);
+        histogram_pass<T, false>(in, lay, vec, &tab->counts[0][0], stream);
         if (hist_out) {
             hipLaunchKernelGGL(normalise_kernel, dim3(3), dim3(kBins), 0, stream, tab, hist_out);
             return check_launch("histogram fit");
@@ -892,29 +907,16 @@ static int run(const void* images, void* out, int64_t n, int64_t h, int64_t w, i
 // One histogram and one LUT per tile: clear, histogram pass, 3N LUT workgroups, apply pass
 template <typename T>
 static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, uint32_t* counts_out, float* lut_out, void* ws, hipStream_t stream) {
-    Layout lay{n, h * w, channels_last};
+    const Layout lay{n, h * w, channels_last};
     Tables* tab = static_cast<Tables*>(ws);
     const TileAreas areas = tile_areas(ws, n, counts_out, lut_out);
     const T* in = static_cast<const T*>(images);
-    constexpr int V = VecOf<T>::n;
-    const int64_t per_tile = 3 * lay.pixels;
-    // vector path: 16-byte aligned bases, and a pack crosses neither a channel plane nor a tile
-    const bool vec = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (channels_last ? (per_tile % V == 0) : (lay.pixels % V == 0));
-    // (the pooled live counters and the status word with the tiles' counters: any contents in, a READY workspace out)
-    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + sizeof(uint32_t) * (size_t)n * 3 * kBins, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
-    if (vec && !channels_last) {
-        const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
-        hipLaunchKernelGGL((histogram_planar_kernel<T, true>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, areas.counts);
-    } else if (vec) {
-        const int chunks_per_tile = (int)((per_tile + kLastChunk - 1) / kLastChunk);
-        hipLaunchKernelGGL((histogram_last_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, per_tile, areas.counts, chunks_per_tile);
-    } else {
-        const int blocks_per_tile = (int)std::min<int64_t>((per_tile + kThreads * 4 - 1) / (kThreads * 4), 64);
-        hipLaunchKernelGGL((histogram_tile_kernel<T>), dim3((unsigned)(n * blocks_per_tile)), dim3(kThreads), 0, stream, in, lay, blocks_per_tile, areas.counts);
-    }
+    const bool vec = vector_path<T>(lay, images, out, /*within_tile=*/true);
+    if (const int rc = clear_counters(tab, sizeof(uint32_t) * (size_t)n * 3 * kBins, stream)) return rc;
+    histogram_pass<T, true>(in, lay, vec, areas.counts, stream);
     hipLaunchKernelGGL((lut_kernel<T, true>), dim3((unsigned)(3 * n)), dim3(kBins), 0, stream, tab, nullptr, true, ref_hist, (double)lay.pixels, areas);
-    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kTilePacks;
-    const int chunks_per_tile = (int)((per_tile + chunk - 1) / chunk);
+    const int64_t chunk = (int64_t)kThreads * (vec ? VecOf<T>::n : 1) * kTilePacks;
+    const int chunks_per_tile = (int)((3 * lay.pixels + chunk - 1) / chunk);
     if (vec)
         hipLaunchKernelGGL((apply_tiles_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, static_cast<T*>(out), lay, chunks_per_tile, static_cast<const T*>(areas.typed));
     else
@@ -922,72 +924,68 @@ static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_
     return check_launch("histogram transform (per tile)");
 }
 
-// The masked calls: behind the Tables one tissue counter per set, then the per-tile areas of `sets` sets (a pooled call: one set).  One
-// clear covers the pooled live counters, the status word, the tissue counters and the sets' live counters: any contents in, READY out.
-static size_t masked_tissue_bytes(int64_t n) { return (sizeof(uint32_t) * (size_t)n + 255) / 256 * 256; }
-static size_t masked_workspace_bytes(int64_t n) { return workspace_bytes() + masked_tissue_bytes(n) + tile_area_bytes(n); }
-
+// The masked calls: the histogram pass over tissue, then the normalised histogram (hist_out), the counts alone (counts64_out:
+// sx_hm_estimate_masked) or the tables and the apply pass.
 template <typename T>
-static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, tissue::Source tis, bool per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, hipStream_t stream, unsigned long long* counts64_out = nullptr) {
-    Layout lay{n, h * w, channels_last};
+static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, tissue::Source tis, bool per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, hipStream_t stream, unsigned long long* counts64_out) {
+    const Layout lay{n, h * w, channels_last};
     Tables* tab = static_cast<Tables*>(ws);
     const int64_t sets = per_tile ? n : 1;
     uint32_t* tissue_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + sizeof(Tables));
     const TileAreas areas = tile_areas(static_cast<char*>(ws) + masked_tissue_bytes(n), sets, counts_out, lut_out);
     const T* in = static_cast<const T*>(images);
-    constexpr int V = VecOf<T>::n;
-    // vector path: 16-byte aligned bases, whole packs of pixels per tile, a pack's mask bytes aligned
-    const bool vec = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) && (lay.pixels % V == 0) && (reinterpret_cast<uintptr_t>(tis.mask) % V == 0);
-    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + masked_tissue_bytes(n) + sizeof(uint32_t) * (size_t)sets * 3 * kBins, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
-    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kMaskTrips;
+    const bool vec = vector_path<T>(lay, images, out, /*within_tile=*/true, /*masked=*/true, tis.mask);
+    if (const int rc = clear_counters(tab, masked_tissue_bytes(n) + sizeof(uint32_t) * (size_t)sets * 3 * kBins, stream)) return rc;
+    const int64_t chunk = (int64_t)kThreads * (vec ? VecOf<T>::n : 1) * kMaskTrips;
     const int chunks_per_tile = (int)((lay.pixels + chunk - 1) / chunk);
-    const unsigned grid = (unsigned)(n * chunks_per_tile);
-#define SX_HM_MASKED_LAUNCH(kernel, ...)                                                                                                  \
-    if (vec && channels_last) hipLaunchKernelGGL((kernel<T, true, true>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);            \
-    else if (vec) hipLaunchKernelGGL((kernel<T, true, false>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);                       \
-    else if (channels_last) hipLaunchKernelGGL((kernel<T, false, true>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);             \
-    else hipLaunchKernelGGL((kernel<T, false, false>), dim3(grid), dim3(kThreads), 0, stream, __VA_ARGS__);
-    SX_HM_MASKED_LAUNCH(histogram_masked_kernel, in, lay, chunks_per_tile, per_tile ? 1 : 0, tis, areas.counts, tissue_counts)
+    const dim3 grid((unsigned)(n * chunks_per_tile)), block(kThreads);
+    with_flags(vec, channels_last != 0, [&](auto kVec, auto kLast) {
+        hipLaunchKernelGGL((histogram_masked_kernel<T, decltype(kVec)::value, decltype(kLast)::value>), grid, block, 0, stream, in, lay, chunks_per_tile, per_tile ? 1 : 0, tis, areas.counts, tissue_counts);
+    });
     if (hist_out) {
         hipLaunchKernelGGL(normalise_masked_kernel, dim3(3), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, tissue_counts, hist_out, tissue_out);
         return check_launch("histogram fit (tissue mask)");
     }
-    if (counts64_out) {      // sx_hm_estimate_masked: the histogram pass alone
+    if (counts64_out) {
         hipLaunchKernelGGL((export_counts_kernel<true>), dim3((unsigned)(3 * sets)), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, counts64_out, tissue_out, 0.0, tissue_counts);
         return check_launch("histogram estimate (tissue mask)");
     }
     hipLaunchKernelGGL((lut_masked_kernel<T>), dim3((unsigned)(3 * sets)), dim3(kBins), 0, stream, tab, ref_hist, areas, tissue_counts, tissue_out);
-    SX_HM_MASKED_LAUNCH(apply_masked_kernel, in, static_cast<T*>(out), lay, chunks_per_tile, per_tile ? 1 : 0, tis, static_cast<const T*>(areas.typed))
-#undef SX_HM_MASKED_LAUNCH
+    with_flags(vec, channels_last != 0, [&](auto kVec, auto kLast) {
+        hipLaunchKernelGGL((apply_masked_kernel<T, decltype(kVec)::value, decltype(kLast)::value>), grid, block, 0, stream, in, static_cast<T*>(out), lay, chunks_per_tile, per_tile ? 1 : 0, tis, static_cast<const T*>(areas.typed));
+    });
     return check_launch("histogram transform (tissue mask)");
+}
+
+static int check_tile_count(int64_t n) {      // (3 n workgroups of the table launches, 64 work items per tile of the histogram pass)
+    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
+    return SX_OK;
+}
+
+// what sx_hm_transform_tiles and sx_hm_estimate check behind their pointers: both run on the per-tile workspace
+static int check_tiles_call(int dtype, int64_t n, int64_t h, int64_t w, const void* ws, size_t ws_bytes) {
+    if (const int rc = check_sizes_got(n, h, w)) return rc;
+    if (const int rc = check_tile_count(n)) return rc;
+    if (const int rc = dtype_ok(dtype)) return rc;
+    return check_workspace(ws, ws_bytes, tiles_workspace_bytes(n));
 }
 
 static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, const uint8_t* mask, double threshold, int per_tile, uint32_t* counts_out, float* lut_out, unsigned long long* tissue_out, void* ws, size_t ws_bytes, void* stream_ptr, unsigned long long* counts64_out = nullptr) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
-    if (!mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
-    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    const size_t need = masked_workspace_bytes(n);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = check_sizes_got(n, h, w)) return rc;
+    if (const int rc = check_tile_count(n)) return rc;
+    if (const int rc = tissue::check_source(mask, threshold)) return rc;
+    if (const int rc = dtype_ok(dtype)) return rc;
+    if (const int rc = check_workspace(ws, ws_bytes, masked_workspace_bytes(n))) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(threshold)};
-    const bool tiles = per_tile != 0;
-    switch (dtype) {
-        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
-        case SX_F16: return run_masked<__half>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
-        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
-        case SX_F32: return run_masked<float>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
-        default: return run_masked<double>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, tiles, counts_out, lut_out, tissue_out, ws, stream, counts64_out);
-    }
+    const tissue::Source tis = tissue::source_of(mask, threshold);
+    return with_dtype(dtype, [&](auto t) { return run_masked<typename decltype(t)::type>(images, out, n, h, w, channels_last, ref_hist, hist_out, tis, per_tile != 0, counts_out, lut_out, tissue_out, ws, stream, counts64_out); });
 }
 
 static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, float* hist_out, unsigned long long* counts_out, const unsigned long long* counts_in, double n_total, void* ws, size_t ws_bytes, void* stream_ptr, bool ready = false) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (!ws || ws_bytes < workspace_bytes()) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", workspace_bytes(), ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = check_sizes_got(n, h, w)) return rc;
+    if (const int rc = check_workspace(ws, ws_bytes, workspace_bytes())) return rc;      // (the dtype code: with_dtype, below)
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     return with_dtype(dtype, [&](auto t) { return run<typename decltype(t)::type>(images, out, n, h, w, channels_last, ref_hist, hist_out, counts_out, counts_in, n_total, ws, stream, ready); });
 }
@@ -996,87 +994,51 @@ static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t
 // per-tile layout either way; a pooled call counts into the Tables' own live counters.
 template <typename T>
 static int run_estimate(const void* images, int64_t n, int64_t h, int64_t w, int channels_last, bool per_tile, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, hipStream_t stream) {
-    Layout lay{n, h * w, channels_last};
+    const Layout lay{n, h * w, channels_last};
     Tables* tab = static_cast<Tables*>(ws);
     const TileAreas areas = tile_areas(ws, n, nullptr, nullptr);
     const T* in = static_cast<const T*>(images);
-    constexpr int V = VecOf<T>::n;
-    const int64_t per_tile_elems = 3 * lay.pixels, total = lay.elements();
-    const bool aligned = reinterpret_cast<uintptr_t>(images) % 16 == 0;
-    if (hipMemsetAsync(tab->counts, 0, sizeof(Tables) - offsetof(Tables, counts) + (per_tile ? sizeof(uint32_t) * (size_t)n * 3 * kBins : 0), stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
+    const bool vec = vector_path<T>(lay, images, nullptr, per_tile);
+    if (const int rc = clear_counters(tab, per_tile ? sizeof(uint32_t) * (size_t)n * 3 * kBins : 0, stream)) return rc;
     if (per_tile) {
-        const bool vec = aligned && (channels_last ? (per_tile_elems % V == 0) : (lay.pixels % V == 0));
-        if (vec && !channels_last) {
-            const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
-            hipLaunchKernelGGL((histogram_planar_kernel<T, true>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, areas.counts);
-        } else if (vec) {
-            const int chunks_per_tile = (int)((per_tile_elems + kLastChunk - 1) / kLastChunk);
-            hipLaunchKernelGGL((histogram_last_kernel<T, true>), dim3((unsigned)(n * chunks_per_tile)), dim3(kThreads), 0, stream, in, per_tile_elems, areas.counts, chunks_per_tile);
-        } else {
-            const int blocks_per_tile = (int)std::min<int64_t>((per_tile_elems + kThreads * 4 - 1) / (kThreads * 4), 64);
-            hipLaunchKernelGGL((histogram_tile_kernel<T>), dim3((unsigned)(n * blocks_per_tile)), dim3(kThreads), 0, stream, in, lay, blocks_per_tile, areas.counts);
-        }
+        histogram_pass<T, true>(in, lay, vec, areas.counts, stream);
         hipLaunchKernelGGL((export_counts_kernel<false>), dim3((unsigned)(3 * n)), dim3(kBins), 0, stream, tab, areas.counts, areas.counted, counts_out, pixels_out, (double)lay.pixels, nullptr);
     } else {
-        const bool vec = aligned && (channels_last ? (total % V == 0) : (lay.pixels % V == 0));
-        if (vec && !channels_last) {
-            const int chunks_per_plane = (int)((lay.pixels + kPlaneChunk - 1) / kPlaneChunk);
-            hipLaunchKernelGGL((histogram_planar_kernel<T>), dim3((unsigned)(n * 3 * chunks_per_plane)), dim3(kPlaneThreads), 0, stream, in, lay, chunks_per_plane, &tab->counts[0][0]);
-        } else if (vec) {
-            hipLaunchKernelGGL((histogram_last_kernel<T>), dim3((unsigned)((total + kLastChunk - 1) / kLastChunk)), dim3(kThreads), 0, stream, in, total, &tab->counts[0][0]);
-        } else {
-            const int64_t per_block = (int64_t)kThreads * 4;
-            const unsigned grid = (unsigned)std::min<int64_t>((total + per_block - 1) / per_block, 256 * 8);
-            hipLaunchKernelGGL((histogram_kernel<T, false>), dim3(grid), dim3(kThreads), 0, stream, in, lay, &tab->counts[0][0]);
-        }
+        histogram_pass<T, false>(in, lay, vec, &tab->counts[0][0], stream);
         hipLaunchKernelGGL((export_counts_kernel<false>), dim3(3), dim3(kBins), 0, stream, tab, &tab->counts[0][0], &tab->counted[0][0], counts_out, pixels_out, (double)(n * lay.pixels), nullptr);
     }
     return check_launch("histogram estimate");
 }
 
-// sx_hm_apply_tables(_masked): ONE launch, the float tables read by the kernel
+// sx_hm_apply_tables(_masked): ONE launch, the float tables read by the kernel; the pack rule and the work items of run_masked() (masked)
+// or run_tiles()
 template <typename T>
 static int run_apply_tables(const void* images, void* out, int64_t n, int64_t h, int64_t w, int channels_last, const float* tables, int64_t n_sources, tissue::Source tis, bool masked, hipStream_t stream) {
-    Layout lay{n, h * w, channels_last};
+    const Layout lay{n, h * w, channels_last};
     const T* in = static_cast<const T*>(images);
     T* dst = static_cast<T*>(out);
-    constexpr int V = VecOf<T>::n;
     const int per_tile = n_sources > 1 ? 1 : 0;      // (n_sources == n_tiles == 1: table 0 either way)
-    const bool aligned = (reinterpret_cast<uintptr_t>(images) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    if (masked) {
-        // vector path: whole packs of pixels per tile, a pack's mask bytes aligned (run_masked)
-        const bool vec = aligned && (lay.pixels % V == 0) && (reinterpret_cast<uintptr_t>(tis.mask) % V == 0);
-        const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kMaskTrips;
-        const int64_t chunks_per_tile = (lay.pixels + chunk - 1) / chunk;
-        if (n * chunks_per_tile > 0x7fffffffll) return fail(SX_ERR_BAD_ARG, "batch too large for one launch: %lld tiles of %lld pixels", (long long)n, (long long)lay.pixels);
-        const dim3 grid((unsigned)(n * chunks_per_tile));
-        if (vec && channels_last) hipLaunchKernelGGL((apply_tables_masked_kernel<T, true, true>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
-        else if (vec) hipLaunchKernelGGL((apply_tables_masked_kernel<T, true, false>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
-        else if (channels_last) hipLaunchKernelGGL((apply_tables_masked_kernel<T, false, true>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
-        else hipLaunchKernelGGL((apply_tables_masked_kernel<T, false, false>), grid, dim3(kThreads), 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
-        return check_launch("histogram apply with given tables (tissue mask)");
-    }
-    // vector path: a pack crosses neither a channel plane nor a tile (run_tiles)
-    const int64_t per_tile_elems = 3 * lay.pixels;
-    const bool vec = aligned && (channels_last ? (per_tile_elems % V == 0) : (lay.pixels % V == 0));
-    const int64_t chunk = (int64_t)kThreads * (vec ? V : 1) * kTilePacks;
-    const int64_t chunks_per_tile = (per_tile_elems + chunk - 1) / chunk;
+    const bool vec = vector_path<T>(lay, images, out, /*within_tile=*/true, masked, tis.mask);
+    const int64_t chunk = (int64_t)kThreads * (vec ? VecOf<T>::n : 1) * (masked ? kMaskTrips : kTilePacks);
+    const int64_t chunks_per_tile = ((masked ? lay.pixels : 3 * lay.pixels) + chunk - 1) / chunk;
     if (n * chunks_per_tile > 0x7fffffffll) return fail(SX_ERR_BAD_ARG, "batch too large for one launch: %lld tiles of %lld pixels", (long long)n, (long long)lay.pixels);
-    const dim3 grid((unsigned)(n * chunks_per_tile));
-    if (vec && channels_last) hipLaunchKernelGGL((apply_tables_kernel<T, true, true>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
-    else if (vec) hipLaunchKernelGGL((apply_tables_kernel<T, true, false>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
-    else if (channels_last) hipLaunchKernelGGL((apply_tables_kernel<T, false, true>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
-    else hipLaunchKernelGGL((apply_tables_kernel<T, false, false>), grid, dim3(kThreads), 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
-    return check_launch("histogram apply with given tables");
+    const dim3 grid((unsigned)(n * chunks_per_tile)), block(kThreads);
+    with_flags(vec, channels_last != 0, [&](auto kVec, auto kLast) {
+        if (masked) hipLaunchKernelGGL((apply_tables_masked_kernel<T, decltype(kVec)::value, decltype(kLast)::value>), grid, block, 0, stream, in, dst, lay, (int)chunks_per_tile, per_tile, tis, tables);
+        else hipLaunchKernelGGL((apply_tables_kernel<T, decltype(kVec)::value, decltype(kLast)::value>), grid, block, 0, stream, in, dst, lay.pixels, (int)chunks_per_tile, tables, per_tile);
+    });
+    return check_launch(masked ? "histogram apply with given tables (tissue mask)" : "histogram apply with given tables");
 }
 
 static int dispatch_apply_tables(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* tables, int64_t n_sources, bool masked, const uint8_t* mask, double threshold, void* stream_ptr) {
     if (!images || !out || !tables) return fail(SX_ERR_BAD_ARG, "images / out / lut pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
+    if (const int rc = check_sizes_got(n, h, w)) return rc;
     if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles = %lld, got %lld", (long long)n, (long long)n_sources);
-    if (masked && !mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
+    if (masked) {
+        if (const int rc = tissue::check_source(mask, threshold)) return rc;
+    }
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const tissue::Source tis{mask, (masked && !mask) ? tissue::y_cut_of(threshold) : 0.0f};
+    const tissue::Source tis = masked ? tissue::source_of(mask, threshold) : tissue::Source{mask, 0.0f};
     return with_dtype(dtype, [&](auto t) { return run_apply_tables<typename decltype(t)::type>(images, out, n, h, w, channels_last, tables, n_sources, tis, masked, stream); });
 }
 
@@ -1147,25 +1109,14 @@ extern "C" int sx_hm_apply(const void* images, void* out, int dtype, int64_t n, 
 // image): the pooled kernels with a set of counters and tables per tile behind the pooled Tables.
 extern "C" size_t sx_hm_tiles_workspace_bytes(int64_t n, int64_t h, int64_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    return histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
+    return histmatch::tiles_workspace_bytes(n);
 }
 
 extern "C" int sx_hm_transform_tiles(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, const float* ref_hist, uint32_t* tile_counts_out, float* tile_lut_out, void* ws, size_t ws_bytes, void* stream_ptr) {
     if (!images || !out || !ref_hist) return fail(SX_ERR_BAD_ARG, "images / out / ref_hist pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
-    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    const size_t need = histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = histmatch::check_tiles_call(dtype, n, h, w, ws, ws_bytes)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return histmatch::run_tiles<uint8_t>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
-        case SX_F16: return histmatch::run_tiles<__half>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
-        case SX_BF16: return histmatch::run_tiles<__hip_bfloat16>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
-        case SX_F32: return histmatch::run_tiles<float>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
-        default: return histmatch::run_tiles<double>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream);
-    }
+    return with_dtype(dtype, [&](auto t) { return histmatch::run_tiles<typename decltype(t)::type>(images, out, n, h, w, channels_last, ref_hist, tile_counts_out, tile_lut_out, ws, stream); });
 }
 
 // ---- tissue masks: histograms over tissue pixels only, background pixels copied (an extension) --------------------------------------------
@@ -1185,28 +1136,11 @@ extern "C" int sx_hm_transform_masked(const void* images, void* out, int dtype, 
 }
 
 // ---- slide level: estimate histograms, build tables from given counts, apply given tables (an extension) --------------------
-static int estimate_checks(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const unsigned long long* counts_out) {
-    if (!images || !counts_out) return fail(SX_ERR_BAD_ARG, "images / counts_out pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must have positive sizes, got N=%lld H=%lld W=%lld", (long long)n, (long long)h, (long long)w);
-    if (n * 3 > 0x7fffffffll / 64) return fail(SX_ERR_BAD_ARG, "too many tiles for one call: %lld", (long long)n);
-    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    return SX_OK;
-}
-
 extern "C" int sx_hm_estimate(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, int per_tile, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, size_t ws_bytes, void* stream_ptr) {
-    if (const int rc = estimate_checks(images, dtype, n, h, w, counts_out)) return rc;
-    const size_t need = histmatch::workspace_bytes() + histmatch::tile_area_bytes(n);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (!images || !counts_out) return fail(SX_ERR_BAD_ARG, "images / counts_out pointer is null");
+    if (const int rc = histmatch::check_tiles_call(dtype, n, h, w, ws, ws_bytes)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const bool tiles = per_tile != 0;
-    switch (dtype) {
-        case SX_U8: return histmatch::run_estimate<uint8_t>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
-        case SX_F16: return histmatch::run_estimate<__half>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
-        case SX_BF16: return histmatch::run_estimate<__hip_bfloat16>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
-        case SX_F32: return histmatch::run_estimate<float>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
-        default: return histmatch::run_estimate<double>(images, n, h, w, channels_last, tiles, counts_out, pixels_out, ws, stream);
-    }
+    return with_dtype(dtype, [&](auto t) { return histmatch::run_estimate<typename decltype(t)::type>(images, n, h, w, channels_last, per_tile != 0, counts_out, pixels_out, ws, stream); });
 }
 
 extern "C" int sx_hm_estimate_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, int channels_last, int per_tile, const uint8_t* mask, double luminosity_threshold, unsigned long long* counts_out, unsigned long long* pixels_out, void* ws, size_t ws_bytes, void* stream) {

@@ -291,17 +291,6 @@ static int run_percentile(const char* who, const void* images, int dtype, int64_
     return check_launch("luminosity percentile");
 }
 
-template <typename T>
-static int run_apply(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* luminance, int per_tile, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
-    if (vector_path<T>(images, out, g.pixels))
-        hipLaunchKernelGGL((standardize_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, luminance, per_tile);
-    else
-        hipLaunchKernelGGL((standardize_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, luminance, per_tile);
-    return check_launch("luminosity apply");
-}
-
 }  // namespace luminosity
 }  // namespace sx
 
@@ -335,12 +324,9 @@ extern "C" int sx_luminosity_apply(const void* images, void* out, int dtype, int
     if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "sx_luminosity_apply: n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
     if (out == images) return fail(SX_ERR_BAD_ARG, "sx_luminosity_apply: out must not be images (the call is not in place)");
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const int per_tile = n_sources == n && n != 1 ? 1 : 0;
-    switch (dtype) {
-        case SX_U8: return run_apply<uint8_t>(images, out, n, h, w, luminance_dev, per_tile, stream);
-        case SX_F16: return run_apply<__half>(images, out, n, h, w, luminance_dev, per_tile, stream);
-        case SX_BF16: return run_apply<__hip_bfloat16>(images, out, n, h, w, luminance_dev, per_tile, stream);
-        case SX_F32: return run_apply<float>(images, out, n, h, w, luminance_dev, per_tile, stream);
-        default: return run_apply<double>(images, out, n, h, w, luminance_dev, per_tile, stream);
-    }
+    const int per_tile = sx::rows_per_tile(n_sources, n);
+    return run_one_launch("luminosity apply", dtype, images, out, n, h, w, nullptr, [&](auto v, auto* in, auto* dst, const Geometry& g, dim3 grid) {
+        using T = std::remove_pointer_t<decltype(dst)>;
+        hipLaunchKernelGGL((standardize_kernel<T, decltype(v)::value>), grid, dim3(kStreamThreads), 0, stream, in, dst, g, luminance_dev, per_tile);
+    });
 }

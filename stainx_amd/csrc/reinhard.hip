@@ -613,15 +613,15 @@ static int blocks_for(int64_t n, int64_t pixels) {
     const int64_t chunk = (int64_t)kStreamThreads * 4 * sweeps_for(n, pixels);
     return (int)((pixels + chunk - 1) / chunk);
 }
-static size_t partial_bytes(int64_t n, int64_t pixels) { return align_up(sizeof(double) * kSums * (size_t)blocks_for(n, pixels) * (size_t)n, 256); }
-// The per-tile arrival counters lie directly behind the State, in front of the partial sums, in a region of FIXED size for batches of up to
-// kReadyTiles tiles: a completed call of ANY shape then leaves every counter of every shape zero (with the counters behind the partial
-// sums -- whose size follows the shape -- a call of one shape left its fp64 sums where another shape's counters lie: a READY call of that
-// other shape never saw its last arrival and normalised with stale statistics; ADVICE r3).  Larger batches: the region grows with the
-// batch and a READY call is treated as a plain one (the clearing launch runs).
-constexpr int64_t kReadyTiles = 4096;
-static size_t counter_bytes(int64_t n) { return align_up(sizeof(unsigned int) * kTileCounterStride * (size_t)std::max<int64_t>(n, kReadyTiles), 256); }
-static size_t workspace_bytes(int64_t n, int64_t pixels) { return align_up(sizeof(State), 256) + counter_bytes(n) + partial_bytes(n, pixels); }
+// The geometry and the grid of every streaming launch over a batch: blocks_per_tile work items of `chunk` pixels per tile.
+struct Launch {
+    Geometry g;
+    dim3 grid;
+};
+static Launch geometry(int64_t n, int64_t h, int64_t w) {
+    const Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
+    return Launch{g, dim3((unsigned)(n * g.blocks_per_tile))};
+}
 
 __global__ void init_state_kernel(State* st, unsigned int* tile_arrivals, int64_t n_tiles) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -645,230 +645,191 @@ __global__ void finalize_kernel(const double* __restrict__ sums, double n, State
 static std::atomic<unsigned int> g_calls{0};      // numbers the calls (of every element type) for the ready-state check, see State
 static std::atomic<unsigned int> g_code_epoch{0x2545F491u};      // numbers the coded calls (see Codes): a flag word left by another call means nothing to this one
 // coded calls: float32 tiles of whole 4-pixel packs, batches of at least 2^20 pixels; the codes and the per-tile flags lie behind the workspace
-static bool coded_size(int64_t n, int64_t pixels) { return pixels % 4 == 0 && n * pixels >= (1ll << 20); }
-static size_t coded_bytes(int64_t n, int64_t pixels) { return align_up(sizeof(unsigned int) * (size_t)n, 256) + align_up((size_t)3 * pixels * n, 256); }
+static bool coded_size(bool is_float32, int64_t n, int64_t pixels) { return is_float32 && pixels % 4 == 0 && n * pixels >= (1ll << 20); }
+
+// ---- the workspace --------------------------------------------------------------------------------------------------------------------
+// ONE walk over the areas, in their order in memory: it yields the pointers of a workspace at `base` and its end (what the size queries
+// and the run functions both read).  Every kind of call -- pooled, per tile, masked -- keeps the pooled layout in front (State, arrival
+// counters, partial sums): a workspace left READY by one kind stays ready for another.
+//
+// The per-tile arrival counters lie directly behind the State, in front of the partial sums, in a region of FIXED size for batches of up to
+// kReadyTiles tiles: a completed call of ANY shape then leaves every counter of every shape zero (with the counters behind the partial
+// sums -- whose size follows the shape -- a call of one shape left its fp64 sums where another shape's counters lie: a READY call of that
+// other shape never saw its last arrival and normalised with stale statistics; ADVICE r3).  Larger batches: the region grows with the
+// batch and a READY call is treated as a plain one (the clearing launch runs).
+//
+// The per-tile and the masked calls put the tiles' statistics -- N x 3 means, then N x 3 standard deviations -- where the partial sums of
+// the FINEST grid (one sweep per work item) would end: the pooled size follows sweeps_for() and shrinks where a larger batch takes more
+// sweeps; theirs never decreases with the batch.  The masked calls hold SEVEN partial sums per work item (the seventh: the tissue
+// count), so their statistics never lie in front of the per-tile calls' and their size is never the smaller one.
+constexpr int64_t kReadyTiles = 4096;
+enum Kind { kPooled, kTiles, kMasked };
+struct Workspace {
+    State* st;
+    unsigned int* tile_arrivals;
+    double* partial;
+    float* tile_stats;            // kTiles, kMasked
+    unsigned int* code_flags;     // coded (float32 batches of coded_size(); not the masked calls): Codes::bad, Codes::planes
+    uint8_t* code_planes;
+};
+struct WorkspaceLayout {
+    Workspace ws;
+    size_t end;
+};
+static WorkspaceLayout workspace_layout(void* base, Kind kind, int64_t n_tiles, int64_t pixels, bool coded = false) {
+    WorkspaceLayout l{};
+    Workspace& w = l.ws;
+    const uintptr_t at = reinterpret_cast<uintptr_t>(base);
+    const size_t n = (size_t)n_tiles, finest = (size_t)((pixels + (int64_t)kStreamThreads * 4 - 1) / ((int64_t)kStreamThreads * 4));
+    const size_t sums = kind == kPooled ? kSums * (size_t)blocks_for(n_tiles, pixels) : (kind == kMasked ? kSums + 1 : kSums) * finest;
+    size_t off = 0;
+    auto area = [&](auto*& field, size_t bytes) {
+        field = reinterpret_cast<std::remove_reference_t<decltype(field)>>(at + off);
+        off += align_up(bytes, 256);
+    };
+    area(w.st, sizeof(State));
+    area(w.tile_arrivals, sizeof(unsigned int) * kTileCounterStride * (size_t)std::max<int64_t>(n_tiles, kReadyTiles));
+    area(w.partial, sizeof(double) * sums * n);
+    if (kind != kPooled) area(w.tile_stats, sizeof(float) * 6 * n);
+    if (coded) {
+        area(w.code_flags, sizeof(unsigned int) * n);
+        area(w.code_planes, (size_t)3 * pixels * n);
+    }
+    l.end = off;
+    return l;
+}
+static size_t workspace_bytes(Kind kind, int64_t n, int64_t pixels, bool coded = false) { return workspace_layout(nullptr, kind, n, pixels, coded).end; }
+
+// The codes of a call (see Codes) where it takes them and its workspace has room for them, none otherwise; the epoch skips 0 ("no codes").
+static Codes coded_setup(const WorkspaceLayout& l, bool takes_codes, size_t ws_bytes) {
+    if (!takes_codes || ws_bytes < l.end) return Codes{nullptr, nullptr, 0u};
+    Codes codes{l.ws.code_planes, l.ws.code_flags, ++g_code_epoch};
+    if (codes.epoch == 0u) codes.epoch = ++g_code_epoch;
+    return codes;
+}
+
+// ---- the launch rules -----------------------------------------------------------------------------------------------------------------
+// Packs of four pixels: tiles of whole packs, the images and (where there is one) the output at a pack's alignment, and (where there is
+// one) the mask at a word's -- a pack's mask bytes are one 32-bit word.  Single pixels otherwise.
+template <typename T>
+static bool vector_path(const void* images, const void* out, int64_t pixels, const uint8_t* mask = nullptr) {
+    const auto aligned = [](const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; };      // (a null pointer: no such operand)
+    return pixels % 4 == 0 && aligned(images, sizeof(T) * 4) && aligned(out, sizeof(T) * 4) && aligned(mask, 4);
+}
+// launch(int_constant<V>{}): V = 4 or 1
+template <typename L>
+static void with_pack(bool vec, L&& launch) {
+    with_layout<4, /*kPlanarOnly=*/true>(vec, false, [&](auto v, auto) { launch(v); return (int)SX_OK; });
+}
+// The calls that are ONE launch over the images with given rows: the element type, the geometry, the pack rule, then
+// launch(int_constant<V>{}, const T* images, T* out, Geometry, grid) names the kernel and its own arguments.
+template <typename L>
+static int run_one_launch(const char* what, int dtype, const void* images, void* out, int64_t n, int64_t h, int64_t w, const uint8_t* mask, L&& launch) {
+    return with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const Launch l = geometry(n, h, w);
+        with_pack(vector_path<T>(images, out, l.g.pixels, mask), [&](auto v) { launch(v, static_cast<const T*>(images), static_cast<T*>(out), l.g, l.grid); });
+        return check_launch(what);
+    });
+}
 
 template <typename T>
 static int run(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, float* mean_out, float* std_out, double* sums_out, const double* sums_in, double n_total, void* ws, size_t ws_bytes, hipStream_t stream, bool ready) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    State* st = static_cast<State*>(ws);
-    unsigned int* tile_arrivals = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + align_up(sizeof(State), 256));
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(tile_arrivals) + counter_bytes(n));
-    if (n > kReadyTiles) ready = false;      // (the counters of such a batch do not lie in the shape-independent region)
-    const bool vec = (g.pixels % 4 == 0) && (reinterpret_cast<uintptr_t>(images) % (sizeof(T) * 4) == 0) && (!out || reinterpret_cast<uintptr_t>(out) % (sizeof(T) * 4) == 0);
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
-    const T* in = static_cast<const T*>(images);
+    const Launch l = geometry(n, h, w);
+    const Geometry& g = l.g;
+    const bool vec = vector_path<T>(images, out, g.pixels);
     // float32 batches, statistics and apply pass in this one call: the tiles' 8-bit codes behind the workspace (see Codes)
-    Codes codes{nullptr, nullptr, 0u};
-    if (std::is_same<T, float>::value && vec && out && !sums_in && !sums_out && coded_size(n, g.pixels) && ws_bytes >= workspace_bytes(n, g.pixels) + coded_bytes(n, g.pixels)) {
-        char* base = static_cast<char*>(ws) + workspace_bytes(n, g.pixels);
-        codes.bad = reinterpret_cast<unsigned int*>(base);
-        codes.planes = reinterpret_cast<uint8_t*>(base + align_up(sizeof(unsigned int) * (size_t)n, 256));
-        codes.epoch = ++g_code_epoch;
-        if (codes.epoch == 0u) codes.epoch = ++g_code_epoch;
-    }
+    const bool coded = coded_size(std::is_same<T, float>::value, n, g.pixels);
+    const WorkspaceLayout lay = workspace_layout(ws, kPooled, n, g.pixels, coded);
+    const Workspace& a = lay.ws;
+    const Codes codes = coded_setup(lay, coded && vec && out && !sums_in && !sums_out, ws_bytes);
+    if (n > kReadyTiles) ready = false;      // (the counters of such a batch do not lie in the shape-independent region)
+    const T* in = static_cast<const T*>(images);
+    const dim3 block(kStreamThreads);
     unsigned int call = 0;
     if (sums_in) {            // statistics come from outside (all-reduced over ranks)
-        hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, stream, sums_in, n_total, st);
+        hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, stream, sums_in, n_total, a.st);
     } else {
         call = ++g_calls;
         if (call == 0) call = ++g_calls;      // (0 means "no check" to the apply pass)
-        if (!ready) hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st, tile_arrivals, n);
-        if (vec)
-            hipLaunchKernelGGL((stats_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, sums_out, call, codes);
-        else
-            hipLaunchKernelGGL((stats_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, sums_out, call);
+        if (!ready) hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.st, a.tile_arrivals, n);
+        with_pack(vec, [&](auto v) { hipLaunchKernelGGL((stats_kernel<T, decltype(v)::value>), l.grid, block, 0, stream, in, g, a.st, a.partial, a.tile_arrivals, mean_out, std_out, sums_out, call, codes); });
     }
-    if (out) {
-        if (vec)
-            hipLaunchKernelGGL((apply_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, st, ref_mean, ref_std, ready ? call : 0u, codes);
-        else
-            hipLaunchKernelGGL((apply_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, st, ref_mean, ref_std, ready ? call : 0u);
-    }
+    if (out) with_pack(vec, [&](auto v) { hipLaunchKernelGGL((apply_kernel<T, decltype(v)::value>), l.grid, block, 0, stream, in, static_cast<T*>(out), g, a.st, ref_mean, ref_std, ready ? call : 0u, codes); });
     return check_launch("reinhard");
 }
 
 static int dispatch(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* rm, const float* rs, float* mo, float* so, double* sums_out, const double* sums_in, double n_total, void* ws, size_t ws_bytes, void* stream_ptr, bool ready = false) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    const size_t need = workspace_bytes(n, h * w);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = check_sizes(n, h, w)) return rc;
+    if (const int rc = check_workspace(ws, ws_bytes, workspace_bytes(kPooled, n, h * w))) return rc;      // (the dtype code: with_dtype, below)
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
     return with_dtype(dtype, [&](auto t) { return run<typename decltype(t)::type>(images, out, n, h, w, rm, rs, mo, so, sums_out, sums_in, n_total, ws, ws_bytes, stream, ready); });
 }
 
-// ---- per-tile statistics, given statistics ------------------------------------------------------------------------------------------
-// The per-tile calls keep the pooled workspace's layout (State, arrival counters, partial sums: a READY workspace stays ready) and put
-// the tiles' statistics -- N x 3 means, then N x 3 standard deviations -- behind it, the codes of a float32 batch behind those.
-// (They lie where the partial sums of the finest grid -- one sweep per work item -- would end: the pooled size follows sweeps_for() and
-// shrinks where a larger batch takes more sweeps; this one never decreases with the batch.)
-static size_t tile_stat_bytes(int64_t n) { return align_up(sizeof(float) * 6 * (size_t)n, 256); }
-static size_t tile_stat_offset(int64_t n, int64_t pixels) {
-    const size_t finest = (size_t)((pixels + (int64_t)kStreamThreads * 4 - 1) / ((int64_t)kStreamThreads * 4));
-    return align_up(sizeof(State), 256) + counter_bytes(n) + align_up(sizeof(double) * kSums * finest * (size_t)n, 256);
-}
-static size_t tiles_workspace_bytes(int64_t n, int64_t pixels) { return tile_stat_offset(n, pixels) + tile_stat_bytes(n); }
-
-template <typename T>
-static bool vector_path(const void* images, const void* out, int64_t pixels) {
-    return (pixels % 4 == 0) && (reinterpret_cast<uintptr_t>(images) % (sizeof(T) * 4) == 0) && (!out || reinterpret_cast<uintptr_t>(out) % (sizeof(T) * 4) == 0);
-}
-
+// ---- per-tile statistics ------------------------------------------------------------------------------------------------------------
 // statistics pass with a finish per tile; with `out` the apply pass with the tile's own row
 template <typename T>
 static int run_tiles(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, float* mean_out, float* std_out, void* ws, size_t ws_bytes, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    State* st = static_cast<State*>(ws);
-    unsigned int* tile_arrivals = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + align_up(sizeof(State), 256));
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(tile_arrivals) + counter_bytes(n));
-    char* behind = static_cast<char*>(ws) + tile_stat_offset(n, g.pixels);
+    const Launch l = geometry(n, h, w);
+    const Geometry& g = l.g;
+    const bool vec = vector_path<T>(images, out, g.pixels);
+    const bool coded = coded_size(std::is_same<T, float>::value, n, g.pixels);
+    const WorkspaceLayout lay = workspace_layout(ws, kTiles, n, g.pixels, coded);
+    const Workspace& a = lay.ws;
+    const Codes codes = coded_setup(lay, coded && vec && out, ws_bytes);
     if (!mean_out) {      // (both or neither: checked by the entry points)
-        mean_out = reinterpret_cast<float*>(behind);
+        mean_out = a.tile_stats;
         std_out = mean_out + 3 * n;
     }
-    const bool vec = vector_path<T>(images, out, g.pixels);
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
     const T* in = static_cast<const T*>(images);
-    Codes codes{nullptr, nullptr, 0u};
-    if (std::is_same<T, float>::value && vec && out && coded_size(n, g.pixels) && ws_bytes >= tiles_workspace_bytes(n, g.pixels) + coded_bytes(n, g.pixels)) {
-        char* base = behind + tile_stat_bytes(n);
-        codes.bad = reinterpret_cast<unsigned int*>(base);
-        codes.planes = reinterpret_cast<uint8_t*>(base + align_up(sizeof(unsigned int) * (size_t)n, 256));
-        codes.epoch = ++g_code_epoch;
-        if (codes.epoch == 0u) codes.epoch = ++g_code_epoch;
-    }
-    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st, tile_arrivals, n);
-    if (vec)
-        hipLaunchKernelGGL((stats_kernel<T, 4, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, codes);
-    else
-        hipLaunchKernelGGL((stats_kernel<T, 1, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u});
-    if (out) {
-        if (vec)
-            hipLaunchKernelGGL((apply_stats_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, 1, ref_mean, ref_std, codes);
-        else
-            hipLaunchKernelGGL((apply_stats_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, 1, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
-    }
+    const dim3 block(kStreamThreads);
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.st, a.tile_arrivals, n);
+    with_pack(vec, [&](auto v) { hipLaunchKernelGGL((stats_kernel<T, decltype(v)::value, true>), l.grid, block, 0, stream, in, g, a.st, a.partial, a.tile_arrivals, mean_out, std_out, nullptr, 0u, codes); });
+    if (out) with_pack(vec, [&](auto v) { hipLaunchKernelGGL((apply_stats_kernel<T, decltype(v)::value>), l.grid, block, 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, 1, ref_mean, ref_std, codes); });
     return check_launch("reinhard (per tile)");
 }
 
 static int dispatch_tiles(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* rm, const float* rs, float* mo, float* so, void* ws, size_t ws_bytes, void* stream_ptr) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    const size_t need = tiles_workspace_bytes(n, h * w);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = check_sizes(n, h, w)) return rc;
+    if (const int rc = dtype_ok(dtype)) return rc;
+    if (const int rc = check_workspace(ws, ws_bytes, workspace_bytes(kTiles, n, h * w))) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    switch (dtype) {
-        case SX_U8: return run_tiles<uint8_t>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
-        case SX_F16: return run_tiles<__half>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
-        case SX_BF16: return run_tiles<__hip_bfloat16>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
-        case SX_F32: return run_tiles<float>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
-        default: return run_tiles<double>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream);
-    }
-}
-
-// the apply pass alone, with the caller's statistics: one launch
-template <typename T>
-static int run_apply_stats(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* ref_mean, const float* ref_std, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
-    if (vector_path<T>(images, out, g.pixels))
-        hipLaunchKernelGGL((apply_stats_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
-    else
-        hipLaunchKernelGGL((apply_stats_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, Codes{nullptr, nullptr, 0u});
-    return check_launch("reinhard (given statistics)");
+    return with_dtype(dtype, [&](auto t) { return run_tiles<typename decltype(t)::type>(images, out, n, h, w, rm, rs, mo, so, ws, ws_bytes, stream); });
 }
 
 // ---- tissue masks -----------------------------------------------------------------------------------------------------------------
-// The masked calls keep the per-tile calls' layout -- State, arrival counters, partial sums, then the statistics -- with SEVEN partial
-// sums per work item of the finest grid (the seventh: the tissue count); a READY workspace stays ready.
-static size_t masked_stat_offset(int64_t n, int64_t pixels) {
-    const size_t finest = (size_t)((pixels + (int64_t)kStreamThreads * 4 - 1) / ((int64_t)kStreamThreads * 4));
-    return align_up(sizeof(State), 256) + counter_bytes(n) + align_up(sizeof(double) * (kSums + 1) * finest * (size_t)n, 256);
-}
-static size_t masked_workspace_bytes(int64_t n, int64_t pixels) { return std::max(masked_stat_offset(n, pixels) + tile_stat_bytes(n), tiles_workspace_bytes(n, pixels)); }
-
-template <typename T>
-static bool masked_vector_path(const void* images, const void* out, const uint8_t* mask, int64_t pixels) {
-    return vector_path<T>(images, out, pixels) && reinterpret_cast<uintptr_t>(mask) % 4 == 0;      // (a pack's mask bytes: one 32-bit word)
-}
-
 // masked statistics (a finish per tile, or one for the batch), then with `out` the masked apply pass with those rows
 template <typename T>
 static int run_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* ref_mean, const float* ref_std, tissue::Source tis, bool per_tile, float* mean_out, float* std_out, unsigned long long* counts_out, void* ws, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    State* st = static_cast<State*>(ws);
-    unsigned int* tile_arrivals = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + align_up(sizeof(State), 256));
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(tile_arrivals) + counter_bytes(n));
+    const Launch l = geometry(n, h, w);
+    const Geometry& g = l.g;
+    const bool vec = vector_path<T>(images, out, g.pixels, tis.mask);
+    const Workspace a = workspace_layout(ws, kMasked, n, g.pixels).ws;
     if (!mean_out) {      // (both or neither: checked by the entry points)
-        mean_out = reinterpret_cast<float*>(static_cast<char*>(ws) + masked_stat_offset(n, g.pixels));
+        mean_out = a.tile_stats;
         std_out = mean_out + 3 * n;
     }
-    const bool vec = masked_vector_path<T>(images, out, tis.mask, g.pixels);
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
     const T* in = static_cast<const T*>(images);
-    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st, tile_arrivals, n);
-    if (vec && per_tile)
-        hipLaunchKernelGGL((stats_kernel<T, 4, true, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
-    else if (vec)
-        hipLaunchKernelGGL((stats_kernel<T, 4, false, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
-    else if (per_tile)
-        hipLaunchKernelGGL((stats_kernel<T, 1, true, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
-    else
-        hipLaunchKernelGGL((stats_kernel<T, 1, false, true>), dim3(grid), dim3(kStreamThreads), 0, stream, in, g, st, partial, tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
-    if (out) {
-        if (vec)
-            hipLaunchKernelGGL((apply_stats_masked_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, per_tile ? 1 : 0, ref_mean, ref_std, tis);
-        else
-            hipLaunchKernelGGL((apply_stats_masked_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, per_tile ? 1 : 0, ref_mean, ref_std, tis);
-    }
+    const dim3 block(kStreamThreads);
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a.st, a.tile_arrivals, n);
+    with_flags(vec, per_tile, [&](auto kVec, auto kPerTile) {
+        hipLaunchKernelGGL((stats_kernel<T, decltype(kVec)::value ? 4 : 1, decltype(kPerTile)::value, true>), l.grid, block, 0, stream, in, g, a.st, a.partial, a.tile_arrivals, mean_out, std_out, nullptr, 0u, Codes{nullptr, nullptr, 0u}, MaskArgs<true>{tis, counts_out});
+    });
+    if (out) with_pack(vec, [&](auto v) { hipLaunchKernelGGL((apply_stats_masked_kernel<T, decltype(v)::value>), l.grid, block, 0, stream, in, static_cast<T*>(out), g, mean_out, std_out, per_tile ? 1 : 0, ref_mean, ref_std, tis); });
     return check_launch("reinhard (tissue mask)");
 }
 
 static int dispatch_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* rm, const float* rs, const uint8_t* mask, double threshold, int per_tile, float* mo, float* so, unsigned long long* co, void* ws, size_t ws_bytes, void* stream_ptr) {
     if (!images) return fail(SX_ERR_BAD_ARG, "images pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    if (!mask && !tissue::threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
-    if (dtype < SX_U8 || dtype > SX_F64) return fail(SX_ERR_DTYPE, "unsupported dtype code %d", dtype);
-    const size_t need = masked_workspace_bytes(n, h * w);
-    if (!ws || ws_bytes < need) return fail(SX_ERR_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return fail(SX_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+    if (const int rc = check_sizes(n, h, w)) return rc;
+    if (const int rc = tissue::check_source(mask, threshold)) return rc;
+    if (const int rc = dtype_ok(dtype)) return rc;
+    if (const int rc = check_workspace(ws, ws_bytes, workspace_bytes(kMasked, n, h * w))) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(threshold)};
-    const bool tiles = per_tile != 0;
-    switch (dtype) {
-        case SX_U8: return run_masked<uint8_t>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
-        case SX_F16: return run_masked<__half>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
-        case SX_BF16: return run_masked<__hip_bfloat16>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
-        case SX_F32: return run_masked<float>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
-        default: return run_masked<double>(images, out, n, h, w, rm, rs, tis, tiles, mo, so, co, ws, stream);
-    }
-}
-
-template <typename T>
-static int run_apply_stats_masked(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* ref_mean, const float* ref_std, tissue::Source tis, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
-    if (masked_vector_path<T>(images, out, tis.mask, g.pixels))
-        hipLaunchKernelGGL((apply_stats_masked_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, tis);
-    else
-        hipLaunchKernelGGL((apply_stats_masked_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, ref_mean, ref_std, tis);
-    return check_launch("reinhard (given statistics, tissue mask)");
-}
-
-// a target row per tile: the geometry and the pack rule of the two calls above, one launch
-template <typename T, bool kMasked>
-static int run_apply_targets(const void* images, void* out, int64_t n, int64_t h, int64_t w, const float* src_mean, const float* src_std, int per_tile, const float* tgt_mean, const float* tgt_std, int per_target, tissue::Source tis, hipStream_t stream) {
-    Geometry g{n, h * w, blocks_for(n, h * w), kStreamThreads * 4 * sweeps_for(n, h * w)};
-    const unsigned grid = (unsigned)(n * g.blocks_per_tile);
-    const bool vec = kMasked ? masked_vector_path<T>(images, out, tis.mask, g.pixels) : vector_path<T>(images, out, g.pixels);
-    if (vec)
-        hipLaunchKernelGGL((apply_targets_kernel<T, 4, kMasked>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, tgt_mean, tgt_std, per_target, tis);
-    else
-        hipLaunchKernelGGL((apply_targets_kernel<T, 1, kMasked>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), static_cast<T*>(out), g, src_mean, src_std, per_tile, tgt_mean, tgt_std, per_target, tis);
-    return check_launch(kMasked ? "reinhard (targets per tile, tissue mask)" : "reinhard (targets per tile)");
+    const tissue::Source tis = tissue::source_of(mask, threshold);
+    return with_dtype(dtype, [&](auto t) { return run_masked<typename decltype(t)::type>(images, out, n, h, w, rm, rs, tis, per_tile != 0, mo, so, co, ws, stream); });
 }
 
 // sx_tissue_mask: the rule as a call of its own.  Workgroup b takes share b % blocks_per_tile of tile b / blocks_per_tile; a thread a pack
@@ -920,14 +881,11 @@ template <typename T>
 static int run_tissue_mask(const void* images, int64_t n, int64_t h, int64_t w, int channels_last, float y_cut, uint8_t* mask_out, unsigned long long* counts_out, hipStream_t stream) {
     const int64_t pixels = h * w;
     if (counts_out && hipMemsetAsync(counts_out, 0, sizeof(unsigned long long) * (size_t)n, stream) != hipSuccess) return fail(SX_ERR_LAUNCH, "hipMemsetAsync failed");
-    const bool vec = !channels_last && pixels % 4 == 0 && reinterpret_cast<uintptr_t>(images) % (sizeof(T) * 4) == 0 && reinterpret_cast<uintptr_t>(mask_out) % 4 == 0;
+    const bool vec = !channels_last && vector_path<T>(images, nullptr, pixels, mask_out);      // (the mask written: a pack's bytes are one word, as of a mask read)
     const int per_block = kStreamThreads * (vec ? 4 : 1);
     const int blocks_per_tile = (int)std::min<int64_t>((pixels + per_block - 1) / per_block, kMaskBlocksPerTile);
     const unsigned grid = (unsigned)(n * blocks_per_tile);
-    if (vec)
-        hipLaunchKernelGGL((tissue_mask_kernel<T, 4>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), pixels, channels_last, blocks_per_tile, y_cut, mask_out, counts_out);
-    else
-        hipLaunchKernelGGL((tissue_mask_kernel<T, 1>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), pixels, channels_last, blocks_per_tile, y_cut, mask_out, counts_out);
+    with_pack(vec, [&](auto v) { hipLaunchKernelGGL((tissue_mask_kernel<T, decltype(v)::value>), dim3(grid), dim3(kStreamThreads), 0, stream, static_cast<const T*>(images), pixels, channels_last, blocks_per_tile, y_cut, mask_out, counts_out); });
     return check_launch("tissue mask");
 }
 
@@ -938,15 +896,13 @@ using namespace sx;
 
 extern "C" size_t sx_reinhard_workspace_bytes(int64_t n, int64_t h, int64_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    return reinhard::workspace_bytes(n, h * w);
+    return reinhard::workspace_bytes(reinhard::kPooled, n, h * w);
 }
 // ... with room for the 8-bit codes of a float32 batch (3 bytes per pixel): sx_reinhard_transform(_ready) then reads the tiles that consist
 // of grey levels as bytes in its second pass.  A call on the smaller workspace of sx_reinhard_workspace_bytes() runs without.
 extern "C" size_t sx_reinhard_workspace_bytes_for(int dtype, int64_t n, int64_t h, int64_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    size_t need = reinhard::workspace_bytes(n, h * w);
-    if (dtype == SX_F32 && reinhard::coded_size(n, h * w)) need += reinhard::coded_bytes(n, h * w);
-    return need;
+    return reinhard::workspace_bytes(reinhard::kPooled, n, h * w, reinhard::coded_size(dtype == SX_F32, n, h * w));
 }
 
 extern "C" int sx_reinhard_fit(const void* images, int dtype, int64_t n, int64_t h, int64_t w, float* mean_out, float* std_out, void* ws, size_t ws_bytes, void* stream) {
@@ -990,9 +946,7 @@ extern "C" int sx_reinhard_apply(const void* images, void* out, int dtype, int64
 // finish per tile, and the pooled apply pass's arithmetic on the tile's own row.
 extern "C" size_t sx_reinhard_tiles_workspace_bytes(int dtype, int64_t n, int64_t h, int64_t w) {
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    size_t need = reinhard::tiles_workspace_bytes(n, h * w);
-    if (dtype == SX_F32 && reinhard::coded_size(n, h * w)) need += reinhard::coded_bytes(n, h * w);
-    return need;
+    return reinhard::workspace_bytes(reinhard::kTiles, n, h * w, reinhard::coded_size(dtype == SX_F32, n, h * w));
 }
 
 extern "C" int sx_reinhard_tile_stats(const void* images, int dtype, int64_t n, int64_t h, int64_t w, float* tile_mean_out, float* tile_std_out, void* ws, size_t ws_bytes, void* stream) {
@@ -1006,14 +960,29 @@ extern "C" int sx_reinhard_transform_tiles(const void* images, void* out, int dt
     return reinhard::dispatch_tiles(images, out, dtype, n, h, w, ref_mean, ref_std, tile_mean_out, tile_std_out, ws, ws_bytes, stream);
 }
 
-extern "C" int sx_reinhard_apply_stats(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, void* stream_ptr) {
+// the apply pass alone, with the caller's statistics: one launch (kMasked: the tissue form, below)
+template <bool kMasked>
+static int apply_stats_call(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
     if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
     if (!source_mean || !source_std || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / ref_mean / ref_std pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
+    if (const int rc = check_sizes(n, h, w)) return rc;
+    if (const int rc = check_rows("n_sources", n_sources, n)) return rc;
+    if constexpr (kMasked) {
+        if (const int rc = tissue::check_source(mask, luminosity_threshold)) return rc;
+    }
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const int per_tile = n_sources == n && n != 1 ? 1 : 0;
-    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_stats<typename decltype(t)::type>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, stream); });
+    const int per_tile = rows_per_tile(n_sources, n);
+    return reinhard::run_one_launch(kMasked ? "reinhard (given statistics, tissue mask)" : "reinhard (given statistics)", dtype, images, out, n, h, w, mask, [&](auto v, auto* in, auto* dst, const reinhard::Geometry& g, dim3 grid) {
+        using T = std::remove_pointer_t<decltype(dst)>;
+        if constexpr (kMasked)
+            hipLaunchKernelGGL((reinhard::apply_stats_masked_kernel<T, decltype(v)::value>), grid, dim3(kStreamThreads), 0, stream, in, dst, g, source_mean, source_std, per_tile, ref_mean, ref_std, tissue::source_of(mask, luminosity_threshold));
+        else
+            hipLaunchKernelGGL((reinhard::apply_stats_kernel<T, decltype(v)::value>), grid, dim3(kStreamThreads), 0, stream, in, dst, g, source_mean, source_std, per_tile, ref_mean, ref_std, reinhard::Codes{nullptr, nullptr, 0u});
+    });
+}
+
+extern "C" int sx_reinhard_apply_stats(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, void* stream_ptr) {
+    return apply_stats_call<false>(images, out, dtype, n, h, w, source_mean, source_std, n_sources, ref_mean, ref_std, nullptr, 0.0, stream_ptr);
 }
 
 // ---- tissue masks (an extension: HistomicsTK's reinhard(mask_out=), staintools' LuminosityThresholdTissueLocator) ------------------------------
@@ -1031,7 +1000,7 @@ extern "C" int sx_tissue_mask(const void* images, int dtype, int64_t n, int64_t 
 extern "C" size_t sx_reinhard_masked_workspace_bytes(int dtype, int64_t n, int64_t h, int64_t w) {
     (void)dtype;
     if (n <= 0 || h <= 0 || w <= 0) return 0;
-    return reinhard::masked_workspace_bytes(n, h * w);
+    return reinhard::workspace_bytes(reinhard::kMasked, n, h * w);
 }
 
 extern "C" int sx_reinhard_stats_masked(const void* images, int dtype, int64_t n, int64_t h, int64_t w, const uint8_t* mask, double luminosity_threshold, int per_tile, float* mean_out, float* std_out, unsigned long long* counts_out, void* ws, size_t ws_bytes, void* stream) {
@@ -1046,30 +1015,28 @@ extern "C" int sx_reinhard_transform_masked(const void* images, void* out, int d
 }
 
 extern "C" int sx_reinhard_apply_stats_masked(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* ref_mean, const float* ref_std, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
-    if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
-    if (!source_mean || !source_std || !ref_mean || !ref_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / ref_mean / ref_std pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
-    if (!mask && !tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
-    hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const int per_tile = n_sources == n && n != 1 ? 1 : 0;
-    const tissue::Source tis{mask, mask ? 0.0f : tissue::y_cut_of(luminosity_threshold)};
-    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_stats_masked<typename decltype(t)::type>(images, out, n, h, w, source_mean, source_std, per_tile, ref_mean, ref_std, tis, stream); });
+    return apply_stats_call<true>(images, out, dtype, n, h, w, source_mean, source_std, n_sources, ref_mean, ref_std, mask, luminosity_threshold, stream_ptr);
 }
 
 // ---- a target per tile (statistics-space augmentation, Reinhard to per-tile / per-slide targets without a fit) ------------------------------
+// the geometry and the pack rule of the two calls above, one launch
 template <bool kMasked>
 static int apply_targets_call(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* target_mean, const float* target_std, int64_t n_targets, const uint8_t* mask, double luminosity_threshold, void* stream_ptr) {
     if (!images || !out) return fail(SX_ERR_BAD_ARG, "images / out pointer is null");
     if (!source_mean || !source_std || !target_mean || !target_std) return fail(SX_ERR_BAD_ARG, "source_mean / source_std / target_mean / target_std pointer is null");
-    if (n <= 0 || h <= 0 || w <= 0) return fail(SX_ERR_BAD_ARG, "images must be (N,3,H,W) with positive sizes");
-    if (n_sources != 1 && n_sources != n) return fail(SX_ERR_BAD_ARG, "n_sources must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_sources);
-    if (n_targets != 1 && n_targets != n) return fail(SX_ERR_BAD_ARG, "n_targets must be 1 or n_tiles (%lld), got %lld", (long long)n, (long long)n_targets);
-    if (kMasked && !mask && !tissue::threshold_ok(luminosity_threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", luminosity_threshold);
+    if (const int rc = check_sizes(n, h, w)) return rc;
+    if (const int rc = check_rows("n_sources", n_sources, n)) return rc;
+    if (const int rc = check_rows("n_targets", n_targets, n)) return rc;
+    if constexpr (kMasked) {
+        if (const int rc = tissue::check_source(mask, luminosity_threshold)) return rc;
+    }
     hipStream_t stream = static_cast<hipStream_t>(stream_ptr);
-    const int per_tile = n_sources == n && n != 1 ? 1 : 0, per_target = n_targets == n && n != 1 ? 1 : 0;
-    const tissue::Source tis{mask, kMasked && !mask ? tissue::y_cut_of(luminosity_threshold) : 0.0f};
-    return with_dtype(dtype, [&](auto t) { return reinhard::run_apply_targets<typename decltype(t)::type, kMasked>(images, out, n, h, w, source_mean, source_std, per_tile, target_mean, target_std, per_target, tis, stream); });
+    const int per_tile = rows_per_tile(n_sources, n), per_target = rows_per_tile(n_targets, n);
+    const tissue::Source tis = kMasked ? tissue::source_of(mask, luminosity_threshold) : tissue::Source{nullptr, 0.0f};
+    return reinhard::run_one_launch(kMasked ? "reinhard (targets per tile, tissue mask)" : "reinhard (targets per tile)", dtype, images, out, n, h, w, mask, [&](auto v, auto* in, auto* dst, const reinhard::Geometry& g, dim3 grid) {
+        using T = std::remove_pointer_t<decltype(dst)>;
+        hipLaunchKernelGGL((reinhard::apply_targets_kernel<T, decltype(v)::value, kMasked>), grid, dim3(kStreamThreads), 0, stream, in, dst, g, source_mean, source_std, per_tile, target_mean, target_std, per_target, tis);
+    });
 }
 
 extern "C" int sx_reinhard_apply_targets(const void* images, void* out, int dtype, int64_t n, int64_t h, int64_t w, const float* source_mean, const float* source_std, int64_t n_sources, const float* target_mean, const float* target_std, int64_t n_targets, void* stream_ptr) {

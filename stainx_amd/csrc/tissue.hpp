@@ -64,6 +64,12 @@ inline float y_cut_of(double threshold) {
     const double f = (100.0 * threshold + 16.0) / 116.0;
     return (float)(f * f * f > 0.008856 ? f * f * f : (f - 16.0 / 116.0) / 7.787);
 }
+// the masked entry points: an explicit mask, or the rule with a threshold in range
+inline int check_source(const uint8_t* mask, double threshold) {
+    if (!mask && !threshold_ok(threshold)) return fail(SX_ERR_BAD_ARG, "luminosity_threshold must lie in (0, 1), got %g", threshold);
+    return SX_OK;
+}
+inline Source source_of(const uint8_t* mask, double threshold) { return Source{mask, mask ? 0.0f : y_cut_of(threshold)}; }
 
 }  // namespace tissue
 }  // namespace sx

@@ -1,7 +1,8 @@
 """The Macenko workspace sizes as the C ABI reports them (pure host functions, no GPU): one walk over the areas (macenko.hip:
 workspace_layout) yields both the pointers and the end of every level, and these are the relations its answers must keep -- the part of
 the buffer one call needs is a prefix of the whole, every level ends on a 256-byte boundary, and a call sent to the four passes needs
-what SX_MACENKO_CLASSIC needs."""
+what SX_MACENKO_CLASSIC needs.  The Reinhard sizes come from one walk of their own (reinhard.hip: workspace_layout): pooled, per tile
+and masked calls keep the pooled areas in front, and the relations between their sizes are those below."""
 from __future__ import annotations
 
 import itertools
@@ -49,3 +50,21 @@ def test_non_positive_sizes_give_zero(lib, n, h, w):
     for dtype, flags in itertools.product(DTYPES, FLAG_SETS):
         assert lib.sx_macenko_workspace_bytes_for(dtype, n, h, w, flags) == 0
         assert lib.sx_macenko_form(dtype, n, h, w, flags) == 0
+
+
+@pytest.mark.parametrize("n", BATCHES + (4096, 5000))
+def test_reinhard_and_histogram_matching_sizes(lib, n):
+    f32 = 3
+    for (h, w), dtype in itertools.product(TILES, DTYPES):
+        plain, sized, tiles = lib.sx_reinhard_workspace_bytes(n, h, w), lib.sx_reinhard_workspace_bytes_for(dtype, n, h, w), lib.sx_reinhard_tiles_workspace_bytes(dtype, n, h, w)
+        masked = lib.sx_reinhard_masked_workspace_bytes(dtype, n, h, w)
+        for size in (plain, sized, tiles, masked):
+            assert size > 0 and size % 256 == 0, (dtype, n, h, w, size)
+        assert plain <= sized <= tiles, (dtype, n, h, w, plain, sized, tiles)
+        coded = dtype == f32 and (h * w) % 4 == 0 and n * h * w >= 1 << 20      # (the codes of a float32 batch lie behind the other areas)
+        assert (sized > plain) == coded, (dtype, n, h, w, plain, sized)
+        assert (tiles > lib.sx_reinhard_tiles_workspace_bytes(0, n, h, w)) == coded, (dtype, n, h, w, tiles)
+        assert masked >= lib.sx_reinhard_tiles_workspace_bytes(0, n, h, w), (dtype, n, h, w, masked)      # (NOT the float32 per-tile size: the masked calls keep no codes)
+    for h, w in TILES:
+        pooled, tiles, masked = lib.sx_hm_workspace_bytes(n, h, w), lib.sx_hm_tiles_workspace_bytes(n, h, w), lib.sx_hm_masked_workspace_bytes(n, h, w)
+        assert 0 < pooled < tiles < masked, (n, h, w, pooled, tiles, masked)

@@ -50,8 +50,46 @@ CALLS = {
     "sx_deconv_combine": "conc out dtype n h w basis n_bases flags stream",
     "sx_deconv_quantify": "images dtype n h w basis n_bases bin_log2 zero_bin per_tile qout flags stream",
     "sx_deconv_quantify_masked": "images dtype n h w basis n_bases bin_log2 zero_bin per_tile qout mask flags stream",
+    # the Reinhard and histogram-matching host layer, sx_tissue_mask, sx_luminosity_apply
+    "sx_reinhard_fit": "images dtype n h w mean_out std_out ws ws_bytes stream",
+    "sx_reinhard_transform": "images out dtype n h w ref_mean ref_std ws ws_bytes stream",
+    "sx_reinhard_transform_ready": "images out dtype n h w ref_mean ref_std ws ws_bytes stream",
+    "sx_reinhard_sums": "images dtype n h w sums ws ws_bytes stream",
+    "sx_reinhard_apply": "images out dtype n h w sums n_total ref_mean ref_std ws ws_bytes stream",
+    "sx_reinhard_tile_stats": "images dtype n h w mean_out std_out ws ws_bytes stream",
+    "sx_reinhard_transform_tiles": "images out dtype n h w ref_mean ref_std mean_out std_out ws ws_bytes stream",
+    "sx_reinhard_apply_stats": "images out dtype n h w src_mean src_std n_sources ref_mean ref_std stream",
+    "sx_reinhard_stats_masked": "images dtype n h w mask threshold per_tile mean_out std_out counts ws ws_bytes stream",
+    "sx_reinhard_transform_masked": "images out dtype n h w ref_mean ref_std mask threshold per_tile mean_out std_out counts ws ws_bytes stream",
+    "sx_reinhard_apply_stats_masked": "images out dtype n h w src_mean src_std n_sources ref_mean ref_std mask threshold stream",
+    "sx_reinhard_apply_targets": "images out dtype n h w src_mean src_std n_sources tgt_mean tgt_std n_targets stream",
+    "sx_reinhard_apply_targets_masked": "images out dtype n h w src_mean src_std n_sources tgt_mean tgt_std n_targets mask threshold stream",
+    "sx_hm_fit": "images dtype n h w channels_last hist ws ws_bytes stream",
+    "sx_hm_transform": "images out dtype n h w channels_last ref_hist ws ws_bytes stream",
+    "sx_hm_fit_ready": "images dtype n h w channels_last hist ws ws_bytes stream",
+    "sx_hm_transform_ready": "images out dtype n h w channels_last ref_hist ws ws_bytes stream",
+    "sx_hm_counts_ready": "images dtype n h w channels_last counts ws ws_bytes stream",
+    "sx_hm_counts": "images dtype n h w channels_last counts ws ws_bytes stream",
+    "sx_hm_apply": "images out dtype n h w channels_last counts n_total ref_hist ws ws_bytes stream",
+    "sx_hm_transform_tiles": "images out dtype n h w channels_last ref_hist tile_counts lut ws ws_bytes stream",
+    "sx_hm_fit_masked": "images dtype n h w channels_last mask threshold hist tissue_out ws ws_bytes stream",
+    "sx_hm_transform_masked": "images out dtype n h w channels_last ref_hist mask threshold per_tile tile_counts lut tissue_out ws ws_bytes stream",
+    "sx_hm_estimate": "images dtype n h w channels_last per_tile counts pixels_out ws ws_bytes stream",
+    "sx_hm_estimate_masked": "images dtype n h w channels_last per_tile mask threshold counts pixels_out ws ws_bytes stream",
+    "sx_hm_apply_tables": "images out dtype n h w channels_last lut n_sources stream",
+    "sx_hm_apply_tables_masked": "images out dtype n h w channels_last lut n_sources mask threshold stream",
+    "sx_tissue_mask": "images dtype n h w channels_last threshold mask_out counts stream",
+    "sx_luminosity_apply": "images out2 dtype n h w luminance n_sources stream",
 }
-POINTERS = {k for k, v in DEFAULTS.items() if v == P} | {"ws"}
+DEFAULTS.update(dict(mean_out=P, std_out=P, ref_mean=P, ref_std=P, src_mean=P, src_std=P, tgt_mean=P, tgt_std=P, hist=P, ref_hist=P, tile_counts=P, lut=P, tissue_out=P, pixels_out=P,
+                     mask_out=P, luminance=P, out2=P + 0x100000, n_total=4608.0, threshold=0.8, channels_last=0))
+POINTERS = {k for k, v in DEFAULTS.items() if v == P} | {"ws", "out2"}
+# two faults in one call: which of the two an entry point reports is the order of its checks
+PAIRS = [dict(dtype=7, ws_bytes=0), dict(dtype=7, n=0), dict(images=None, ws_bytes=0), dict(n_sources=3, dtype=7), dict(n_targets=3, dtype=7), dict(n=0, ws_bytes=0), dict(n=1 << 25, dtype=7),
+         dict(n=1 << 25, ws_bytes=0), dict(mask=None, threshold=1.5, dtype=7), dict(mask=None, threshold=1.5, ws_bytes=0), dict(mask=None, threshold=1.5, n=0), dict(mask=None, threshold=1.5, n_sources=3),
+         dict(mask=None, threshold=1.5, n=1 << 25), dict(n_sources=3, n=0), dict(n_sources=3, n_targets=3), dict(dtype=7, ws=W + 8), dict(out2=P, dtype=7), dict(out2=P, n_sources=3),
+         dict(n_total=0.5, dtype=7), dict(n_total=0.5, images=None), dict(mean_out=None, images=None), dict(ref_mean=None, images=None), dict(counts=None, images=None), dict(lut=None, n=0),
+         dict(mask_out=None, counts=None), dict(mask_out=None, counts=None, images=None)]
 
 
 def mutations(params):
@@ -85,6 +123,9 @@ def mutations(params):
         yield "zero_bin=256", dict(zero_bin=256)
     if "stage" in params:
         yield "stage=2", dict(stage=2)
+    for o in (dict(threshold=1.5), dict(threshold=0.0), dict(mask=None, threshold=1.5), dict(mask=None, threshold=0.0), dict(n_total=0.5), dict(channels_last=1), dict(per_tile=1), dict(out2=P),
+              dict(n=1 << 25), dict(n=4097, h=8, w=8), *PAIRS):
+        yield " ".join(f"{k}={'null' if v is None else v}" for k, v in o.items()), o
 
 
 def cpu_part(lib):
@@ -151,8 +192,9 @@ class Gpu:
         return None if t is None else t.data_ptr()
 
     def images(self, n, h, w, dtype, nhwc, offset):
-        if (n, h, w) not in self.batches:
-            self.batches[(n, h, w)] = synth.he_batch(n, h, w, seed0=4100 + h, scale_step=0.05)
+        if (n, h, w) not in self.batches:      # (more than 16 tiles: the first 16, shifted by a column more per repeat)
+            base = synth.he_batch(min(n, 16), h, w, seed0=4100 + h, scale_step=0.05)
+            self.batches[(n, h, w)] = base if n <= 16 else torch.cat([base.roll(k, dims=-1) for k in range((n + 15) // 16)])[:n]
         x = synth.as_dtype(self.batches[(n, h, w)], dtype)
         if nhwc:
             x = x.permute(0, 2, 3, 1).contiguous()
@@ -272,8 +314,145 @@ class Gpu:
         raise ValueError(call)
 
 
+def siblings(g, tag, dtype, n, h, w, offset=0, out_offset=0, masks=("half", "ones", "rule"), mask_offset=0, reinhard_bytes=None, only=None):
+    """Every Reinhard / histogram-matching / tissue-mask / luminosity-apply entry point on one batch: records `<entry point> <tag> ...`.
+    Workspaces are zero-filled per call (the READY state); reinhard_bytes: the Reinhard workspace's size instead of the largest query."""
+    lib, dev, code, p, s = g.lib, g.dev, _native.DTYPE_CODES[dtype], g.ptr, None
+    px, rows = n * h * w, torch.arange(n * 3, dtype=torch.float32, device=dev)
+    z = lambda count, dt=torch.float32: torch.zeros(count, dtype=dt, device=dev)
+    img_out = lambda: z(3 * px + 16, dtype)[out_offset:out_offset + 3 * px]
+    want = lambda name: only is None or name in only
+    ref_mean, ref_std = torch.tensor([0.62, 0.11, -0.04], device=dev), torch.tensor([0.17, 0.08, 0.05], device=dev)
+    tgt_mean, tgt_std = (0.55 + 0.01 * rows).contiguous(), (0.12 + 0.002 * rows).contiguous()
+    src_mean, src_std = (0.60 - 0.01 * rows).contiguous(), (0.15 + 0.001 * rows).contiguous()
+    ref_hist = torch.linspace(1.0, 2.0, 768, device=dev).reshape(3, 256)
+    ref_hist = (ref_hist / ref_hist.sum(dim=1, keepdim=True)).contiguous()
+
+    def mask_of(kind):      # (pointer or None, threshold)
+        return (None, 0.8) if kind == "rule" else (g.mask(n, h, w, kind, mask_offset), 0.0)
+
+    # ---- Reinhard (planar only)
+    x = g.images(n, h, w, dtype, False, offset)
+    rb = reinhard_bytes or max(lib.sx_reinhard_workspace_bytes_for(code, n, h, w), lib.sx_reinhard_tiles_workspace_bytes(code, n, h, w), lib.sx_reinhard_masked_workspace_bytes(code, n, h, w))
+    ws = lambda: z(rb, torch.uint8)
+    status = lambda wsp: wsp[lib.sx_reinhard_workspace_status_offset():][:4]
+    if want("reinhard_pooled"):
+        m, sd, wsp = z(3), z(3), ws()
+        g.record(f"sx_reinhard_fit {tag}", lib.sx_reinhard_fit(p(x), code, n, h, w, p(m), p(sd), p(wsp), rb, s), m, sd)
+        for name in ("sx_reinhard_transform", "sx_reinhard_transform_ready"):
+            out, wsp = img_out(), ws()
+            g.record(f"{name} {tag}", getattr(lib, name)(p(x), p(out), code, n, h, w, p(ref_mean), p(ref_std), p(wsp), rb, s), out, status(wsp))
+        sums, out, wsp = z(6, torch.float64), img_out(), ws()
+        rc = lib.sx_reinhard_sums(p(x), code, n, h, w, p(sums), p(wsp), rb, s)
+        rc = rc or lib.sx_reinhard_apply(p(x), p(out), code, n, h, w, p(sums), float(px), p(ref_mean), p(ref_std), p(wsp), rb, s)
+        g.record(f"sx_reinhard_sums+apply {tag}", rc, sums, out)
+    if want("reinhard_tiles"):
+        tm, ts, wsp = z(3 * n), z(3 * n), ws()
+        g.record(f"sx_reinhard_tile_stats {tag}", lib.sx_reinhard_tile_stats(p(x), code, n, h, w, p(tm), p(ts), p(wsp), rb, s), tm, ts)
+        for given in (True, False):
+            out, m, sd, wsp = img_out(), z(3 * n) if given else None, z(3 * n) if given else None, ws()
+            g.record(f"sx_reinhard_transform_tiles {tag} stats_out={given}", lib.sx_reinhard_transform_tiles(p(x), p(out), code, n, h, w, p(ref_mean), p(ref_std), p(m), p(sd), p(wsp), rb, s), out, m, sd)
+    if want("reinhard_given"):
+        for ns in sorted({1, n}):
+            out = img_out()
+            g.record(f"sx_reinhard_apply_stats {tag} n_sources={ns}", lib.sx_reinhard_apply_stats(p(x), p(out), code, n, h, w, p(src_mean), p(src_std), ns, p(ref_mean), p(ref_std), s), out)
+            out = img_out()
+            g.record(f"sx_reinhard_apply_targets {tag} n_sources=n_targets={ns}", lib.sx_reinhard_apply_targets(p(x), p(out), code, n, h, w, p(src_mean), p(src_std), ns, p(tgt_mean), p(tgt_std), ns, s), out)
+        lum = (0.85 + 0.01 * rows[:n]).contiguous()
+        for ns in sorted({1, n}):
+            out = img_out()
+            g.record(f"sx_luminosity_apply {tag} n_sources={ns}", lib.sx_luminosity_apply(p(x), p(out), code, n, h, w, p(lum), ns, s), out)
+    for mk in masks:
+        mp, thr = mask_of(mk)
+        mtag = f"{tag} mask={mk}" + (f"+{mask_offset}" if mask_offset and mk != "rule" else "")
+        if want("reinhard_masked"):
+            for per_tile in (0, 1):
+                k = n if per_tile else 1
+                m, sd, cnt, wsp = z(3 * k), z(3 * k), z(k, torch.int64), ws()
+                g.record(f"sx_reinhard_stats_masked {mtag} per_tile={per_tile}", lib.sx_reinhard_stats_masked(p(x), code, n, h, w, p(mp), thr, per_tile, p(m), p(sd), p(cnt), p(wsp), rb, s), m, sd, cnt)
+                out, cnt, wsp = img_out(), z(k, torch.int64), ws()
+                g.record(f"sx_reinhard_transform_masked {mtag} per_tile={per_tile}",
+                         lib.sx_reinhard_transform_masked(p(x), p(out), code, n, h, w, p(ref_mean), p(ref_std), p(mp), thr, per_tile, None, None, p(cnt), p(wsp), rb, s), out, cnt)
+            out = img_out()
+            g.record(f"sx_reinhard_apply_stats_masked {mtag}", lib.sx_reinhard_apply_stats_masked(p(x), p(out), code, n, h, w, p(src_mean), p(src_std), n, p(ref_mean), p(ref_std), p(mp), thr, s), out)
+            out = img_out()
+            g.record(f"sx_reinhard_apply_targets_masked {mtag}", lib.sx_reinhard_apply_targets_masked(p(x), p(out), code, n, h, w, p(src_mean), p(src_std), n, p(tgt_mean), p(tgt_std), n, p(mp), thr, s), out)
+    # ---- histogram matching and the tissue rule, both layouts
+    hb = lib.sx_hm_masked_workspace_bytes(n, h, w)
+    for cl in (0, 1):
+        x = g.images(n, h, w, dtype, bool(cl), offset)
+        ltag = f"{tag} channels_last={cl}"
+        hws = lambda ready=False: z(hb, torch.uint8)
+        hstatus = lambda wsp: wsp[lib.sx_hm_workspace_status_offset():][:4]
+        if want("hm_pooled"):
+            for name, ready in (("sx_hm_fit", False), ("sx_hm_fit_ready", True)):
+                hist, wsp = z(768), hws(ready)
+                g.record(f"{name} {ltag}", getattr(lib, name)(p(x), code, n, h, w, cl, p(hist), p(wsp), hb, s), hist, hstatus(wsp))
+            for name, ready in (("sx_hm_transform", False), ("sx_hm_transform_ready", True)):
+                out, wsp = img_out(), hws(ready)
+                g.record(f"{name} {ltag}", getattr(lib, name)(p(x), p(out), code, n, h, w, cl, p(ref_hist), p(wsp), hb, s), out, hstatus(wsp))
+            cnt, wsp = z(768, torch.int64), hws(True)
+            g.record(f"sx_hm_counts_ready {ltag}", lib.sx_hm_counts_ready(p(x), code, n, h, w, cl, p(cnt), p(wsp), hb, s), cnt, hstatus(wsp))
+            cnt, out, wsp = z(768, torch.int64), img_out(), hws()
+            rc = lib.sx_hm_counts(p(x), code, n, h, w, cl, p(cnt), p(wsp), hb, s)
+            rc = rc or lib.sx_hm_apply(p(x), p(out), code, n, h, w, cl, p(cnt), float(px), p(ref_hist), p(wsp), hb, s)
+            g.record(f"sx_hm_counts+apply {ltag}", rc, cnt, out)
+        if want("hm_tiles"):
+            out, cnt, lut, wsp = img_out(), z(n * 768, torch.int32), z(n * 768), hws()
+            g.record(f"sx_hm_transform_tiles {ltag}", lib.sx_hm_transform_tiles(p(x), p(out), code, n, h, w, cl, p(ref_hist), p(cnt), p(lut), p(wsp), hb, s), out, cnt, lut, hstatus(wsp))
+            for per_tile in (0, 1):
+                k = n if per_tile else 1
+                cnt, pix, lut, wsp = z(k * 768, torch.int64), z(k, torch.int64), z(k * 768), hws()
+                rc = lib.sx_hm_estimate(p(x), code, n, h, w, cl, per_tile, p(cnt), p(pix), p(wsp), hb, s)
+                g.record(f"sx_hm_estimate {ltag} per_tile={per_tile}", rc, cnt, pix, hstatus(wsp))
+                out = img_out()
+                rc = rc or lib.sx_hm_tables(p(cnt), p(pix), k, p(ref_hist), p(lut), s)
+                rc = rc or lib.sx_hm_apply_tables(p(x), p(out), code, n, h, w, cl, p(lut), k, s)
+                g.record(f"sx_hm_tables+apply_tables {ltag} n_sources={k}", rc, lut, out)
+        if want("tissue_mask"):
+            mo, cnt = z(px + 16, torch.uint8)[mask_offset:mask_offset + px], z(n, torch.int64)
+            g.record(f"sx_tissue_mask {ltag}" + (f" mask_out+{mask_offset}" if mask_offset else ""), lib.sx_tissue_mask(p(x), code, n, h, w, cl, 0.8, p(mo), p(cnt), s), mo, cnt)
+        for mk in masks:
+            mp, thr = mask_of(mk)
+            mtag = f"{ltag} mask={mk}" + (f"+{mask_offset}" if mask_offset and mk != "rule" else "")
+            if not want("hm_masked"):
+                continue
+            hist, tis, wsp = z(768), z(1, torch.int64), hws()
+            g.record(f"sx_hm_fit_masked {mtag}", lib.sx_hm_fit_masked(p(x), code, n, h, w, cl, p(mp), thr, p(hist), p(tis), p(wsp), hb, s), hist, tis)
+            for per_tile in (0, 1):
+                k = n if per_tile else 1
+                out, cnt, lut, tis, wsp = img_out(), z(k * 768, torch.int32), z(k * 768), z(k, torch.int64), hws()
+                g.record(f"sx_hm_transform_masked {mtag} per_tile={per_tile}",
+                         lib.sx_hm_transform_masked(p(x), p(out), code, n, h, w, cl, p(ref_hist), p(mp), thr, per_tile, p(cnt), p(lut), p(tis), p(wsp), hb, s), out, cnt, lut, tis, hstatus(wsp))
+                cnt, pix, wsp = z(k * 768, torch.int64), z(k, torch.int64), hws()
+                g.record(f"sx_hm_estimate_masked {mtag} per_tile={per_tile}", lib.sx_hm_estimate_masked(p(x), code, n, h, w, cl, per_tile, p(mp), thr, p(cnt), p(pix), p(wsp), hb, s), cnt, pix, hstatus(wsp))
+                out = img_out()
+                g.record(f"sx_hm_apply_tables_masked {mtag} n_sources={k}", lib.sx_hm_apply_tables_masked(p(x), p(out), code, n, h, w, cl, p(lut), k, p(mp), thr, s), out)
+
+
+def siblings_part(g):
+    for dtype in DTYPES:
+        dn = str(dtype).split(".")[-1]
+        siblings(g, f"{dn} 2x48x48", dtype, 2, 48, 48)                                       # whole packs for every element type
+        siblings(g, f"{dn} 2x47x49", dtype, 2, 47, 49)                                       # no whole packs
+        siblings(g, f"{dn} 2x48x48+1", dtype, 2, 48, 48, offset=1)                           # single elements by the images' pointer
+        siblings(g, f"{dn} 2x48x48 out+1", dtype, 2, 48, 48, out_offset=1, masks=("half",))  # ... by the output's
+        siblings(g, f"{dn} 2x48x48", dtype, 2, 48, 48, masks=("half",), mask_offset=1, only=("reinhard_masked", "hm_masked", "tissue_mask"))      # ... by the mask's
+        siblings(g, f"{dn} 2x512x512", dtype, 2, 512, 512, masks=("half",))                  # more than one 65536-element chunk per plane and per tile
+    # the Reinhard codes (4 x 512 x 512: exactly 2^20 pixels): with room for them, and on the plain size without
+    siblings(g, "float32 4x512x512 coded", torch.float32, 4, 512, 512, masks=(), only=("reinhard_pooled", "reinhard_tiles"))
+    siblings(g, "float32 4x512x512 plain size", torch.float32, 4, 512, 512, masks=(), only=("reinhard_pooled",), reinhard_bytes=g.lib.sx_reinhard_workspace_bytes(4, 512, 512))
+    for n in (1, 16, 64):      # the steps of sweeps_for()
+        siblings(g, f"uint8 {n}x512x512", torch.uint8, n, 512, 512, masks=("half",), only=("reinhard_pooled", "reinhard_tiles", "reinhard_given", "reinhard_masked"))
+        g.batches.pop((n, 512, 512), None)
+    siblings(g, "uint8 4097x8x8", torch.uint8, 4097, 8, 8, masks=(), only=("reinhard_pooled",))      # beyond kReadyTiles: a READY call runs as a plain one
+    siblings(g, "uint8 48x512x512", torch.uint8, 48, 512, 512, masks=(), only=("hm_pooled",))         # the cap of 2048 workgroups
+    g.batches.pop((48, 512, 512), None)
+
+
 def gpu_part(lib):
     g = Gpu(lib)
+    siblings_part(g)
     shapes = [("48x48", 48, 48, 0), ("47x49", 47, 49, 0), ("48x48+1", 48, 48, 1)]      # whole packs / scalar by size / scalar by pointer
     def out_flag_sets(dtype):
         return [0, NORM] + ([OUT_BF16, OUT_F16, OUT_BF16 | NORM, OUT_F16 | NORM] if dtype == torch.uint8 else [])
@@ -348,8 +527,10 @@ def summary(res):
         out["failed"] = sorted(k for k, v in res["outputs"].items() if v["rc"] != 0)
         out["outputs"] = group(sorted(res["outputs"].items()), lambda r: r[0].replace("[", " ").split()[0])
     else:
-        out["refused"] = group(res["refused"], lambda r: r[0])
-        out["not_refused"] = group(res["not_refused"], lambda r: r[0])
+        refused, passed = group(res["refused"], lambda r: r[0]), group(res["not_refused"], lambda r: r[0])      # (one line per entry point)
+        none = {"records": 0, "sha256": ""}
+        out["calls"] = {k: {"refused": refused.get(k, none)["records"], "not_refused": passed.get(k, none)["records"],
+                            "sha256": hashlib.sha256((refused.get(k, none)["sha256"] + passed.get(k, none)["sha256"]).encode()).hexdigest()} for k in sorted(set(refused) | set(passed))}
         out["sizes"] = group(res["sizes"], lambda r: f"{r['h']}x{r['w']}")
         out["sizes_16x512x512"] = next(r for r in res["sizes"] if (r["n"], r["h"], r["w"]) == (16, 512, 512))
     return out
