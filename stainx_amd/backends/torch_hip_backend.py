@@ -6,6 +6,19 @@ reference's types (``ImportError`` when the native library is missing, ``ValueEr
 device or bad shapes, ``RuntimeError`` from the native layer).  Unlike the reference, fit-time
 statistics are computed on the device by the same library (reference: always torch on CPU,
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
+
+Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_statistics_rows``,
+``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
+check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
+(``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
+pointers, ``None`` the null pointer, the current stream comes last, and the status is checked against ``self._lib`` -- the error
+string is read from the library that was called.
+
+The order of refusals, for a call with more than one fault: (1) the options that are the method's own (precision, which outputs, scalar
+ranges); (2) the images: layout and shape, then the dtype -- also for an empty batch; (3) ``out_dtype``; (4) the reference, then the
+other tensor arguments in the order of the signature, a pair's "go together" in front of its shapes; (5) an empty batch returns its
+empty result here; (6) an explicit mask.
 """
 from __future__ import annotations
 
@@ -18,8 +31,10 @@ import torch
 from stainx_amd import _native
 
 HIP_AVAILABLE = _native.library_available()
+_Tensor, _stream_ptr = torch.Tensor, _native.stream_ptr      # (the call rule looks both up once per argument / per call)
 
 
+# ---- the shape and dtype rules: pure functions, CPU tensors welcome ---------------------------------------------------------------
 def _dtype_code(t: torch.Tensor) -> int:
     try:
         return _native.DTYPE_CODES[t.dtype]
@@ -27,8 +42,129 @@ def _dtype_code(t: torch.Tensor) -> int:
         raise TypeError(f"unsupported image dtype {t.dtype}; supported: {sorted(str(d) for d in _native.DTYPE_CODES)}") from None
 
 
+def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, what: str = "") -> tuple[int, int, int]:
+    """``(n, h, w)`` of a batch, NCHW or -- ``channels_last`` -- NHWC.  Anything but four dimensions with three channels is refused in
+    the family's words; ``family=None`` (the mask / level functions and luminosity, whose callers have checked) refuses nothing."""
+    shape = images.shape
+    if family is not None and (len(shape) != 4 or shape[3 if channels_last else 1] != 3):
+        shape = tuple(shape)
+        if family == "Macenko fit":
+            raise ValueError(f"Macenko fit expects NCHW with C=3, got shape {shape}")
+        if family == "Macenko":
+            if channels_last:
+                raise ValueError(f"Macenko {what} with channels_last expects NHWC images with C=3, got shape {shape}")
+            if len(shape) != 4:
+                raise ValueError(f"Macenko expects NCHW images, got shape {shape}")
+            raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
+        if family == "deconvolution":
+            raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
+        if family == "Reinhard":
+            raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
+        if len(shape) != 4:
+            raise ValueError(f"HistogramMatching expects 4D images, got shape {shape}")
+        raise ValueError(f"HistogramMatching expects 3 channels, got {shape[-1] if channels_last else shape[1]} with shape {shape}")
+    return (shape[0], shape[1], shape[2]) if channels_last else (shape[0], shape[2], shape[3])
+
+
+def _out_flags(images: torch.Tensor, out_dtype: torch.dtype | None, normalize_to_0_1: bool, channels_last: bool) -> tuple[int, torch.dtype]:
+    """The flags and the result's dtype: ``out_dtype`` (an extension, uint8 input only) is bfloat16 / float16 written directly; without
+    it the input's dtype, or float32 for the ``/ 255`` of a uint8 batch."""
+    flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+    if out_dtype is not None and out_dtype != images.dtype:
+        if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
+        return flags | (_native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16), out_dtype
+    return flags, torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+
+
+def _reference_pair(stain_matrix: torch.Tensor | None, target_max_conc: torch.Tensor | None, together: str | None = None) -> bool:
+    """A fitted reference, (3, 2) and 2 values: is one given?  ``together`` is the call's wording of "both or neither"; None: the call
+    requires the pair."""
+    if together is not None:
+        if (stain_matrix is None) != (target_max_conc is None):
+            raise ValueError(f"stain_matrix and target_max_conc go together: {together}")
+        if stain_matrix is None:
+            return False
+    if tuple(stain_matrix.shape) != (3, 2):
+        raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
+    if target_max_conc.numel() != 2:
+        raise ValueError(f"target_max_conc must have 2 elements, got {target_max_conc.numel()}")
+    return True
+
+
+def _source_rows(source_he: torch.Tensor, source_max_c: torch.Tensor | None, n: int, need_max_c: bool) -> int:
+    """A given source basis, (3, 2), (1, 3, 2) or (N, 3, 2) with 2 values of ``source_max_c`` per row: the number of rows, 1 or N."""
+    he_shape = tuple(source_he.shape)
+    if he_shape == (3, 2):
+        n_sources = 1
+    elif len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n):
+        n_sources = he_shape[0]
+    else:
+        raise ValueError(f"source_he must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
+    if source_max_c is not None:
+        if source_max_c.numel() != 2 * n_sources or (source_max_c.dim() == 2 and tuple(source_max_c.shape) != (n_sources, 2)) or source_max_c.dim() > 2:
+            raise ValueError(f"source_max_c must hold 2 values per source basis, ({n_sources}, 2), got shape {tuple(source_max_c.shape)}")
+    elif need_max_c:
+        raise ValueError("source_max_c is required to normalise to a reference (it may be None in own-basis mode only)")
+    return n_sources
+
+
+def _check_factors(alpha: torch.Tensor, beta: torch.Tensor, n: int, k: int) -> None:
+    if tuple(alpha.shape) != (n, k) or tuple(beta.shape) != (n, k):
+        raise ValueError(f"alpha and beta must have shape (N, {k}) = ({n}, {k}), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+
+
+def _basis_rows(basis: torch.Tensor, n: int, what: str) -> int:
+    """A given three-stain basis, (3, 3), (1, 3, 3) or (N, 3, 3): the number of rows, 1 or N."""
+    shape = tuple(basis.shape)
+    if shape == (3, 3):
+        return 1
+    if len(shape) == 3 and shape[1:] == (3, 3) and shape[0] in (1, n):
+        return shape[0]
+    raise ValueError(f"{what} must have shape (3, 3), (1, 3, 3) or (N, 3, 3) = ({n}, 3, 3), got {shape}")
+
+
+def _statistics_rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str, accepted: str = "(3,), (1, 3)") -> tuple[torch.Tensor, torch.Tensor]:
+    """Rows of LAB statistics, one for the batch or one per tile, as (rows, 3) tensors.  ``accepted``: the call's wording of the shapes
+    it takes beside (N, 3)."""
+    if mean.dim() == 1:
+        mean = mean.unsqueeze(0)
+    if std.dim() == 1:
+        std = std.unsqueeze(0)
+    for name, t in ((f"{what}_mean", mean), (f"{what}_std", std)):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
+            raise ValueError(f"{name} must be {accepted} or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
+    if mean.shape[0] != std.shape[0]:
+        raise ValueError(f"{what}_mean and {what}_std must have the same number of rows, got {mean.shape[0]} and {std.shape[0]}")
+    return mean, std
+
+
+def _reference_statistics(reference_mean: torch.Tensor, reference_std: torch.Tensor) -> None:
+    if reference_mean.numel() != 3 or reference_std.numel() != 3:
+        raise ValueError("reference_mean / reference_std must have 3 elements")
+
+
+def _mask_bytes(mask: torch.Tensor | None, device: torch.device) -> torch.Tensor | None:
+    """An explicit tissue mask as the dense (N, H, W) uint8 tensor the library reads (bool: the same bytes; no copy where it is dense already)."""
+    if mask is None:
+        return None
+    mask = mask.to(device)
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _explicit_mask(mask: torch.Tensor, n: int, h: int, w: int, device: torch.device) -> torch.Tensor:
+    """``_mask_bytes`` of an explicit mask that has to be uint8 / bool (N, H, W)."""
+    mask = _mask_bytes(mask, device)
+    if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
+        raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+    return mask
+
+
 class TorchHIPBackendBase:
-    """Common device checks (mirrors TorchCUDABackendBase, torch_cuda_backend.py:17-33)."""
+    """Common device checks (mirrors TorchCUDABackendBase, torch_cuda_backend.py:17-33), the image preamble and the call rule."""
 
     def __init__(self, device: str | torch.device | None = None):
         if not _native.library_available():
@@ -46,25 +182,60 @@ class TorchHIPBackendBase:
         self._lib = _native.require()
         _native.check_arch(self.device)
         self._scratch = _native.Scratch()
-        self._pfit_bytes: dict[tuple[int, int, int], int] = {}
 
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
+        # (already float32, contiguous and on the device -- the case of a captured call's fixed buffers, and of every call in a loop --
+        # this is the tensor itself; asking first is a third of the time of the two no-op conversions)
+        if t.dtype is torch.float32 and t.device == self.device and t.is_contiguous():
+            return t
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
+    def _images(self, images: torch.Tensor, channels_last: bool, family: str | None, what: str = "") -> tuple[torch.Tensor, int, int, int, int]:
+        """The image preamble: the dense batch on the device, ``n, h, w`` and the dtype code, or the family's refusal."""
+        if images.device != self.device:
+            images = images.to(self.device)
+        n, h, w = _image_shape(images, channels_last, family, what)
+        code = _native.DTYPE_CODES.get(images.dtype)
+        if code is None:
+            _dtype_code(images)      # (raises the TypeError)
+        return images.contiguous(), n, h, w, code
 
-def _mask_bytes(mask: torch.Tensor | None, device: torch.device) -> torch.Tensor | None:
-    """An explicit tissue mask as the dense (N, H, W) uint8 tensor the library reads (bool: the same bytes; no copy where it is dense already)."""
-    if mask is None:
-        return None
-    mask = mask.to(device)
-    if mask.dim() == 4:
-        mask = mask[:, 0]
-    mask = mask.contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    def _call(self, name: str, *args, on_failure=None) -> None:
+        """The call rule; inside the public call's ``on_device`` guard.  ``on_failure`` runs before a bad status is raised."""
+        rc = getattr(self._lib, name)(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args], _stream_ptr(self.device))
+        if rc != 0:
+            if on_failure is not None:
+                on_failure()
+            _native.check(rc, name, self._lib)
+
+    def _check(self, rc: int, what: str) -> None:
+        """(the calls that stay written out -- the staged pooled fit, tissue_mask_native -- have their status read here)"""
+        if rc != 0:
+            _native.check(rc, what, self._lib)
+
+    def _mask_for(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
+        """The dense (N, H, W) uint8 mask a masked call reads: the explicit one, or -- ``mask=None`` -- the luminosity rule's, made by an
+        ``sx_tissue_mask`` launch in front of the call on the same stream (one extra streaming pass over the images and its bytes: the
+        library's masked Macenko and deconvolution calls take explicit masks only).  ``images``: dense NCHW on the device."""
+        n, _, h, w = images.shape
+        if mask is not None:
+            return _explicit_mask(mask, n, h, w, self.device)
+        made = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        self._call("sx_tissue_mask", images, _dtype_code(images), n, h, w, 0, float(luminosity_threshold), made, None)
+        return made
+
+
+# ---- the mask / level functions (stainx_amd.masks, stainx_amd.sampling): their callers have checked the arguments --------------------
+def _for_levels(levels: torch.Tensor) -> tuple:
+    base = TorchHIPBackendBase(levels.device)
+    src = _mask_bytes(levels, base.device)
+    return (base, src, *src.shape)
 
 
 def tissue_mask_native(images: torch.Tensor, luminosity_threshold: float, channels_last: bool) -> tuple[torch.Tensor, torch.Tensor]:
     """``stainx_amd.tissue_mask`` behind its checks: (N, H, W) uint8 mask and (N,) int64 tissue counts (include/stainx_hip.h: sx_tissue_mask)."""
+    # (written out: the mask in front of every masked call of the normalisers, and the shared preamble and call rule measured about
+    # 1 us of 18 slower here -- profiles/binding_host_time.txt)
     base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
     images = images.to(base.device).contiguous()
     n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
@@ -75,25 +246,18 @@ def tissue_mask_native(images: torch.Tensor, luminosity_threshold: float, channe
     with _native.on_device(base.device):
         rc = base._lib.sx_tissue_mask(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), float(luminosity_threshold), mask.data_ptr(),
                                       counts.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_tissue_mask")
+    base._check(rc, "sx_tissue_mask")
     return mask, counts
-
-
-def _image_sizes(images: torch.Tensor, channels_last: bool) -> tuple[int, int, int]:
-    return (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
 
 
 def luminosity_histogram_native(images: torch.Tensor, pooled: bool, channels_last: bool) -> torch.Tensor:
     """``stainx_amd.luminosity_histogram`` behind its checks: (rows, 256) int64 counts on the device (include/stainx_hip.h: sx_luminosity_histogram)."""
     base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
-    images = images.to(base.device).contiguous()
-    n, h, w = _image_sizes(images, channels_last)
+    images, n, h, w, code = base._images(images, channels_last, None)
     counts = torch.zeros((1 if pooled else n, 256), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return counts
-    with _native.on_device(base.device):
-        rc = base._lib.sx_luminosity_histogram(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), int(pooled), counts.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_luminosity_histogram")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_luminosity_histogram", images, code, n, h, w, int(channels_last), int(pooled), counts)
     return counts
 
 
@@ -101,127 +265,93 @@ def tissue_mask_tiles_native(images: torch.Tensor, thresholds: torch.Tensor, cha
     """The rule with a threshold per tile (``thresholds``: (N,) float64 on the CPU, each in (0, 1)): (N, H, W) uint8 mask and (N,) int64 counts
     (include/stainx_hip.h: sx_tissue_mask_tiles, with the constants sx_tissue_y_cut gives)."""
     base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
-    images = images.to(base.device).contiguous()
-    n, h, w = _image_sizes(images, channels_last)
+    images, n, h, w, code = base._images(images, channels_last, None)
     mask = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
     counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return mask, counts
-    cuts = torch.tensor([base._lib.sx_tissue_y_cut(float(t)) for t in thresholds.tolist()], dtype=torch.float32).to(base.device)
-    with _native.on_device(base.device):
-        rc = base._lib.sx_tissue_mask_tiles(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), cuts.data_ptr(), mask.data_ptr(), counts.data_ptr(),
-                                            _native.stream_ptr(base.device))
-    _native.check(rc, "sx_tissue_mask_tiles")
+    if n * h * w != 0:
+        cuts = torch.tensor([base._lib.sx_tissue_y_cut(float(t)) for t in thresholds.tolist()], dtype=torch.float32).to(base.device)
+        with _native.on_device(base.device):
+            base._call("sx_tissue_mask_tiles", images, code, n, h, w, int(channels_last), cuts, mask, counts)
     return mask, counts
 
 
 def mask_morphology_native(mask: torch.Tensor, op: str, radius: int, element: str) -> tuple[torch.Tensor, torch.Tensor]:
     """``stainx_amd.mask_morphology`` behind its checks: (N, H, W) uint8 result, 1 / 0, and (N,) int64 set pixels per tile (sx_mask_morphology)."""
-    base = TorchHIPBackendBase(mask.device)
-    src = _mask_bytes(mask, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(mask)
     out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
     counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return out, counts
-    scratch = torch.empty_like(out) if op in ("open", "close") else None
-    with _native.on_device(base.device):
-        rc = base._lib.sx_mask_morphology(src.data_ptr(), out.data_ptr(), n, h, w, _native.MORPH_OPS[op], _native.MORPH_ELEMENTS[element], int(radius),
-                                          None if scratch is None else scratch.data_ptr(), counts.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_mask_morphology")
+    if n * h * w != 0:
+        scratch = torch.empty_like(out) if op in ("open", "close") else None
+        with _native.on_device(base.device):
+            base._call("sx_mask_morphology", src, out, n, h, w, _native.MORPH_OPS[op], _native.MORPH_ELEMENTS[element], int(radius), scratch, counts)
     return out, counts
 
 
 def mask_components_native(mask: torch.Tensor, connectivity: int, holes: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``stainx_amd.mask_components`` behind its checks: (N, H, W) int32 labels and areas, (N,) int64 components per tile (sx_mask_components)."""
-    base = TorchHIPBackendBase(mask.device)
-    src = _mask_bytes(mask, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(mask)
     labels = torch.empty((n, h, w), dtype=torch.int32, device=base.device)
     areas = torch.empty((n, h, w), dtype=torch.int32, device=base.device)
     counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return labels, areas, counts
-    with _native.on_device(base.device):
-        rc = base._lib.sx_mask_components(src.data_ptr(), n, h, w, int(connectivity), int(holes), labels.data_ptr(), areas.data_ptr(), counts.data_ptr(),
-                                          _native.stream_ptr(base.device))
-    _native.check(rc, "sx_mask_components")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_mask_components", src, n, h, w, int(connectivity), int(holes), labels, areas, counts)
     return labels, areas, counts
 
 
 def mask_area_filter_native(mask: torch.Tensor, min_area: int, connectivity: int, holes: bool) -> tuple[torch.Tensor, torch.Tensor]:
     """``stainx_amd.remove_small_objects`` / ``remove_small_holes`` behind their checks: (N, H, W) uint8 result, 1 / 0, and (N,) int64 set pixels per
     tile (sx_mask_area_filter; the workspace comes from its size query)."""
-    base = TorchHIPBackendBase(mask.device)
-    src = _mask_bytes(mask, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(mask)
     out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
     counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return out, counts
-    workspace = torch.empty((int(base._lib.sx_mask_components_workspace_bytes(n, h, w)),), dtype=torch.uint8, device=base.device)
-    with _native.on_device(base.device):
-        rc = base._lib.sx_mask_area_filter(src.data_ptr(), out.data_ptr(), n, h, w, int(connectivity), int(holes), int(min_area), workspace.data_ptr(), counts.data_ptr(),
-                                           _native.stream_ptr(base.device))
-    _native.check(rc, "sx_mask_area_filter")
+    if n * h * w != 0:
+        workspace = torch.empty((int(base._lib.sx_mask_components_workspace_bytes(n, h, w)),), dtype=torch.uint8, device=base.device)
+        with _native.on_device(base.device):
+            base._call("sx_mask_area_filter", src, out, n, h, w, int(connectivity), int(holes), int(min_area), workspace, counts)
     return out, counts
 
 
 def saturation_map_native(images: torch.Tensor, channels_last: bool) -> torch.Tensor:
     """``stainx_amd.saturation_map`` behind its checks: (N, H, W) uint8 saturation levels on the device (include/stainx_hip.h: sx_saturation_map)."""
     base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
-    images = images.to(base.device).contiguous()
-    n, h, w = _image_sizes(images, channels_last)
+    images, n, h, w, code = base._images(images, channels_last, None)
     out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
-    if n == 0 or h * w == 0:
-        return out
-    with _native.on_device(base.device):
-        rc = base._lib.sx_saturation_map(images.data_ptr(), _dtype_code(images), n, h, w, int(channels_last), out.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_saturation_map")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_saturation_map", images, code, n, h, w, int(channels_last), out)
     return out
 
 
 def median_filter_native(levels: torch.Tensor, size: int) -> torch.Tensor:
     """``stainx_amd.median_filter`` behind its checks: (N, H, W) uint8 medians of the size x size windows (sx_median_filter_u8)."""
-    base = TorchHIPBackendBase(levels.device)
-    src = _mask_bytes(levels, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(levels)
     out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
-    if n == 0 or h * w == 0:
-        return out
-    with _native.on_device(base.device):
-        rc = base._lib.sx_median_filter_u8(src.data_ptr(), out.data_ptr(), n, h, w, int(size), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_median_filter_u8")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_median_filter_u8", src, out, n, h, w, int(size))
     return out
 
 
 def level_histogram_native(levels: torch.Tensor, pooled: bool) -> torch.Tensor:
     """``stainx_amd.level_histogram`` behind its checks: (rows, 256) int64 counts on the device (sx_level_histogram)."""
-    base = TorchHIPBackendBase(levels.device)
-    src = _mask_bytes(levels, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(levels)
     counts = torch.zeros((1 if pooled else n, 256), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return counts
-    with _native.on_device(base.device):
-        rc = base._lib.sx_level_histogram(src.data_ptr(), n, h, w, int(pooled), counts.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_level_histogram")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_level_histogram", src, n, h, w, int(pooled), counts)
     return counts
 
 
 def level_mask_native(levels: torch.Tensor, thresholds: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """``stainx_amd.level_mask`` behind its checks (``thresholds``: (N,) int32 on the device): (N, H, W) uint8 mask, 1 where level > threshold, and
     (N,) int64 set pixels per tile (sx_level_mask_tiles)."""
-    base = TorchHIPBackendBase(levels.device)
-    src = _mask_bytes(levels, base.device)
-    n, h, w = src.shape
+    base, src, n, h, w = _for_levels(levels)
     mask = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
     counts = torch.zeros((n,), dtype=torch.int64, device=base.device)
-    if n == 0 or h * w == 0:
-        return mask, counts
-    with _native.on_device(base.device):
-        rc = base._lib.sx_level_mask_tiles(src.data_ptr(), n, h, w, thresholds.data_ptr(), mask.data_ptr(), counts.data_ptr(), _native.stream_ptr(base.device))
-    _native.check(rc, "sx_level_mask_tiles")
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_level_mask_tiles", src, n, h, w, thresholds, mask, counts)
     return mask, counts
 
 
@@ -231,26 +361,21 @@ def sample_pixels_native(images: torch.Tensor, mask: torch.Tensor | None, height
     type, (G, height, width) uint8 validity, (G,) int32 taken and (G,) int64 population, G = 1 pooled, else N (include/stainx_hip.h:
     sx_sample_pixels; the workspace comes from its size query).  Nothing synchronises."""
     base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
-    images = images.to(base.device).contiguous()
-    n, h, w = _image_sizes(images, channels_last)
+    images, n, h, w, code = base._images(images, channels_last, None)
     groups = 1 if pooled else n
-    if n == 0 or h * w == 0:      # nothing to rank: empty groups (a pooled call keeps its one row)
-        return (torch.zeros((groups, 3, height, width), dtype=images.dtype, device=base.device), torch.zeros((groups, height, width), dtype=torch.uint8, device=base.device),
-                torch.zeros((groups,), dtype=torch.int32, device=base.device), torch.zeros((groups,), dtype=torch.int64, device=base.device))
-    code = _dtype_code(images)
-    src = _mask_bytes(mask, base.device)
-    pixels = torch.empty((groups, 3, height, width), dtype=images.dtype, device=base.device)
-    valid = torch.empty((groups, height, width), dtype=torch.uint8, device=base.device)
-    taken = torch.empty((groups,), dtype=torch.int32, device=base.device)
-    population = torch.empty((groups,), dtype=torch.int64, device=base.device)
-    nbytes = int(base._lib.sx_sample_workspace_bytes(n, h, w))
-    if nbytes == 0:
-        raise ValueError(f"sample_pixels: a tile of {h} x {w} pixels is too large for one call (a group holds fewer than 2^31 pixels)")
-    workspace = torch.empty((nbytes,), dtype=torch.uint8, device=base.device)
-    with _native.on_device(base.device):
-        rc = base._lib.sx_sample_pixels(images.data_ptr(), code, n, h, w, int(channels_last), None if src is None else src.data_ptr(), int(pooled), height * width, int(offset),
-                                        pixels.data_ptr(), valid.data_ptr(), taken.data_ptr(), population.data_ptr(), workspace.data_ptr(), nbytes, _native.stream_ptr(base.device))
-    _native.check(rc, "sx_sample_pixels")
+    make = torch.zeros if n * h * w == 0 else torch.empty      # nothing to rank: empty groups (a pooled call keeps its one row)
+    pixels = make((groups, 3, height, width), dtype=images.dtype, device=base.device)
+    valid = make((groups, height, width), dtype=torch.uint8, device=base.device)
+    taken = make((groups,), dtype=torch.int32, device=base.device)
+    population = make((groups,), dtype=torch.int64, device=base.device)
+    if n * h * w != 0:
+        src = _mask_bytes(mask, base.device)
+        nbytes = int(base._lib.sx_sample_workspace_bytes(n, h, w))
+        if nbytes == 0:
+            raise ValueError(f"sample_pixels: a tile of {h} x {w} pixels is too large for one call (a group holds fewer than 2^31 pixels)")
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=base.device)
+        with _native.on_device(base.device):
+            base._call("sx_sample_pixels", images, code, n, h, w, int(channels_last), src, int(pooled), height * width, int(offset), pixels, valid, taken, population, workspace, nbytes)
     return pixels, valid, taken, population
 
 
@@ -271,6 +396,7 @@ class MacenkoHIP(TorchHIPBackendBase):
         # exact ones -- moments pass + one per-tile stage + reconstruct; mean error ~0.5, worst ~5 grey levels.  The fit is always exact.
         self._precision = precision
         self.last_workspace: torch.Tensor | None = None
+        self._pfit_bytes: dict[tuple[int, int, int], int] = {}
         # Feedback for the choice between the two forms of the transform (see _route / _watch): the two-pass form speculates per
         # tile and pays a whole-tile exact select (0.1-0.5 ms) for a tile it cannot speculate on -- no tissue, no stable stain
         # plane.  The library counts those; the count is read back asynchronously and a batch stream that produces them is
@@ -288,12 +414,24 @@ class MacenkoHIP(TorchHIPBackendBase):
         # A/B switch for benchmarks (it used to live inside the library): the four-pass form everywhere
         self._env_flags = _native.MACENKO_CLASSIC if os.environ.get("STAINX_MACENKO_CLASSIC", "").strip().lower() in ("1", "true", "yes", "on") else 0
 
-    @staticmethod
-    def _check_images(images: torch.Tensor, what: str) -> None:
-        if images.dim() != 4:
-            raise ValueError(f"Macenko expects NCHW images, got shape {tuple(images.shape)}")
-        if images.shape[1] != 3:
-            raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={images.shape[1]} with shape {tuple(images.shape)}")
+    def _reference(self, stain_matrix, target_max_conc, together: str | None = None) -> tuple[torch.Tensor | None, torch.Tensor | None]:
+        """The fitted reference as float32 device tensors, (3, 2) and (2,), or ``(None, None)`` where the call may do without."""
+        if not _reference_pair(stain_matrix, target_max_conc, together):
+            return None, None
+        return self._f32(stain_matrix), self._f32(target_max_conc).flatten()
+
+    def _check_sources(self, source_he: torch.Tensor, source_max_c: torch.Tensor | None, n: int, need_max_c: bool) -> tuple[torch.Tensor, torch.Tensor | None, int]:
+        """A given source basis as float32 device tensors, and the number of its rows, 1 or N."""
+        n_sources = _source_rows(source_he, source_max_c, n, need_max_c)
+        return self._f32(source_he), None if source_max_c is None else self._f32(source_max_c), n_sources
+
+    def _masked_images(self, images: torch.Tensor, what: str) -> tuple[torch.Tensor, int, int, int, int]:
+        if self._precision == "sampled":
+            raise ValueError(f"{what} with a mask runs the exact four-pass form; precision='sampled' has no masked form")
+        return self._images(images, False, "Macenko", what)
+
+    def _classic_workspace(self, code: int, n: int, h: int, w: int) -> torch.Tensor:
+        return self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
 
     def transform(self, images: torch.Tensor, stain_matrix: torch.Tensor, target_max_conc: torch.Tensor, *, normalize_to_0_1: bool = False,
                   channels_last: bool = False, out_dtype: torch.dtype | None = None, _extra_flags: int = 0) -> torch.Tensor:
@@ -301,35 +439,14 @@ class MacenkoHIP(TorchHIPBackendBase):
         hand tiles over, and so is the result -- the permute + copy a caller would otherwise do first is fused away.
         ``out_dtype=torch.bfloat16 / torch.float16`` (an extension, uint8 input only): the result of the call without it, cast
         with ``.to(out_dtype)``, written directly -- a decoder's uint8 tile becomes a model's half-precision input in one call."""
-        images = images.to(self.device)
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            _extra_flags = int(_extra_flags) | (_native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16)
-        else:
-            out_dtype = None
-        if tuple(stain_matrix.shape) != (3, 2):
-            raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko transform with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, "transform")
-        sm = self._f32(stain_matrix)
-        tmc = self._f32(target_max_conc).flatten()
-        if tmc.numel() != 2:
-            raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        images = images.contiguous()
-        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
-        code = _dtype_code(images)
-        if out_dtype is None:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+        images, n, h, w, code = self._images(images, channels_last, "Macenko", "transform")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        sm, tmc = self._reference(stain_matrix, target_max_conc)
         out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
-            flags = ((_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
-                     | (_native.MACENKO_SAMPLED if self._precision == "sampled" else 0) | int(_extra_flags) | self._env_flags)
+            flags |= (_native.MACENKO_SAMPLED if self._precision == "sampled" else 0) | int(_extra_flags) | self._env_flags
             # (only calls the library would run in its two-pass form take part in the feedback: for the others -- small batches,
             # narrow pixels -- the event, the side-stream copy and the stream bookkeeping are 7 us of host time per call for nothing)
             routed = (not (flags & (_native.MACENKO_CLASSIC | _native.MACENKO_TWO_PASS | _native.MACENKO_SAMPLED))
@@ -341,9 +458,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             if routed:
                 with self._tele_lock:
                     flags |= self._route()
-            rc = self._lib.sx_macenko_transform(images.data_ptr(), out.data_ptr(), code, n, h, w, sm.data_ptr(), tmc.data_ptr(),
-                                                flags, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_transform", self._lib)
+            self._call("sx_macenko_transform", images, out, code, n, h, w, sm, tmc, flags, ws, ws.numel())
             if routed and not (flags & _native.MACENKO_CLASSIC):
                 with self._tele_lock:
                     self._watch(ws)
@@ -358,49 +473,25 @@ class MacenkoHIP(TorchHIPBackendBase):
         rebuilt -- with its own ``HE_source`` when no reference is given, with the fitted ``stain_matrix`` after the transform's
         rescaling ``C * target_max_conc / maxC`` otherwise.  Images, layout and output types as in ``transform``.  The factors are
         read on the device: a captured call replayed after new values are copied into the same tensors uses the new values."""
-        images = images.to(self.device)
-        flags = 0
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = None
-        if (stain_matrix is None) != (target_max_conc is None):
-            raise ValueError("stain_matrix and target_max_conc go together: both (normalise and jitter) or neither (each tile's own stain basis)")
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko augment with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, "augment")
-        n = images.shape[0]
-        if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
-            raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
-        sm = tmc = None
-        if stain_matrix is not None:
-            if tuple(stain_matrix.shape) != (3, 2):
-                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-            sm = self._f32(stain_matrix)
-            tmc = self._f32(target_max_conc).flatten()
-            if tmc.numel() != 2:
-                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        # (already float32, contiguous and on the device -- the case of a captured call's fixed buffers -- these are the tensors themselves)
+        return self._augment_call(self._images(images, channels_last, "Macenko", "augment"), alpha, beta, stain_matrix, target_max_conc, None, normalize_to_0_1, channels_last, out_dtype)
+
+    def _augment_call(self, batch: tuple, alpha, beta, stain_matrix, target_max_conc, masking: tuple | None, normalize_to_0_1: bool, channels_last: bool, out_dtype) -> torch.Tensor:
+        """augment / augment_masked: ``masking`` is None or ``(mask, luminosity_threshold)``."""
+        images, n, h, w, code = batch
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        sm, tmc = self._reference(stain_matrix, target_max_conc, "both (normalise and jitter) or neither (each tile's own stain basis)")
+        _check_factors(alpha, beta, n, 2)
         a, b = self._f32(alpha), self._f32(beta)
-        images = images.contiguous()
-        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
-        code = _dtype_code(images)
-        if out_dtype is None:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
         out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_augment(images.data_ptr(), out.data_ptr(), code, n, h, w, a.data_ptr(), b.data_ptr(),
-                                              sm.data_ptr() if sm is not None else None, tmc.data_ptr() if tmc is not None else None,
-                                              flags, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_augment", self._lib)
+            mask = None if masking is None else self._mask_for(images, *masking)
+            ws = self._classic_workspace(code, n, h, w)
+            if masking is None:
+                self._call("sx_macenko_augment", images, out, code, n, h, w, a, b, sm, tmc, flags, ws, ws.numel())
+            else:
+                self._call("sx_macenko_augment_masked", images, out, code, n, h, w, mask, a, b, sm, tmc, flags, ws, ws.numel())
         self.last_workspace = ws
         return out
 
@@ -414,57 +505,8 @@ class MacenkoHIP(TorchHIPBackendBase):
         float32, ``he`` (N, 3, 2) and ``max_c`` (N, 2); an output not asked for is None.  ``max_c`` comes with normalised mode for free;
         in own-basis mode ``max_conc=True`` adds the two launches that compute it.  ``channels_last``: NHWC images, (2, N, H, W, 3)
         images and (N, H, W, 2) concentrations."""
-        images = images.to(self.device)
-        if not (stains or concentrations):
-            raise ValueError("separate: ask for stains, concentrations or both")
-        flags = 0
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = None
-        if (stain_matrix is None) != (target_max_conc is None):
-            raise ValueError("stain_matrix and target_max_conc go together: both (normalised) or neither (each tile's own stain basis)")
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko separate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, "separate")
-        sm = tmc = None
-        if stain_matrix is not None:
-            if tuple(stain_matrix.shape) != (3, 2):
-                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-            sm = self._f32(stain_matrix)
-            tmc = self._f32(target_max_conc).flatten()
-            if tmc.numel() != 2:
-                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        images = images.contiguous()
-        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
-        code = _dtype_code(images)
-        if out_dtype is None:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
-        want_max_c = max_conc or sm is not None
-        out = {
-            "stains": torch.empty((2, *images.shape), dtype=out_dtype, device=self.device) if stains else None,
-            "concentrations": torch.empty((n, h, w, 2) if channels_last else (n, 2, h, w), dtype=torch.float32, device=self.device) if concentrations else None,
-            "he": torch.empty((n, 3, 2), dtype=torch.float32, device=self.device),
-            "max_c": torch.empty((n, 2), dtype=torch.float32, device=self.device) if want_max_c else None,
-        }
-        if n == 0 or h * w == 0:
-            return out
-        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
-        with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_separate(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, ptr(sm), ptr(tmc),
-                                               ptr(out["he"]), ptr(out["max_c"]), flags, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_separate", self._lib)
-        self.last_workspace = ws
-        return out
+        return self._separate_call(images, stain_matrix, target_max_conc, source=None, masking=None, stains=stains, concentrations=concentrations, max_conc=max_conc,
+                                   normalize_to_0_1=normalize_to_0_1, channels_last=channels_last, out_dtype=out_dtype, neither="each tile's own stain basis")
 
     def estimate(self, images: torch.Tensor, *, channels_last: bool = False) -> dict[str, torch.Tensor]:
         """The transform's per-tile estimate as a call of its own (include/stainx_hip.h: sx_macenko_estimate): ``he`` (N, 3, 2),
@@ -472,27 +514,17 @@ class MacenkoHIP(TorchHIPBackendBase):
         the exact percentiles: ``precision="sampled"`` is refused."""
         if self._precision == "sampled":
             raise ValueError("estimate computes the exact per-tile estimate; precision='sampled' has no estimate of its own")
-        images = images.to(self.device)
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko estimate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, "estimate")
-        images = images.contiguous()
-        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
-        code = _dtype_code(images)
+        images, n, h, w, code = self._images(images, channels_last, "Macenko", "estimate")
         out = {
             "he": torch.empty((n, 3, 2), dtype=torch.float32, device=self.device),
             "max_c": torch.empty((n, 2), dtype=torch.float32, device=self.device),
             "tissue": torch.empty((n,), dtype=torch.float32, device=self.device),
         }
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_estimate(images.data_ptr(), code, n, h, w, out["he"].data_ptr(), out["max_c"].data_ptr(), out["tissue"].data_ptr(),
-                                               _native.MACENKO_CHANNELS_LAST if channels_last else 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_estimate", self._lib)
+            ws = self._classic_workspace(code, n, h, w)
+            self._call("sx_macenko_estimate", images, code, n, h, w, out["he"], out["max_c"], out["tissue"], _native.MACENKO_CHANNELS_LAST if channels_last else 0, ws, ws.numel())
         self.last_workspace = ws
         return out
 
@@ -506,110 +538,36 @@ class MacenkoHIP(TorchHIPBackendBase):
         the factors are required, the tile is rebuilt with ``source_he`` and ``source_max_c`` is not read (it may be None).  Images,
         layout and output types as in ``transform``.  Source, factors and reference are read on the device: a captured call replayed
         after new values are copied into the same tensors uses the new values."""
-        images = images.to(self.device)
-        flags = 0
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = None
-        if (stain_matrix is None) != (target_max_conc is None):
-            raise ValueError("stain_matrix and target_max_conc go together: both (normalise) or neither (the given source basis is kept)")
+        images, n, h, w, code = self._images(images, channels_last, "Macenko", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        sm, tmc = self._reference(stain_matrix, target_max_conc, "both (normalise) or neither (the given source basis is kept)")
         if (alpha is None) != (beta is None):
             raise ValueError("alpha and beta go together: both or neither")
-        if stain_matrix is None and alpha is None:
+        if sm is None and alpha is None:
             raise ValueError("apply without a reference (own basis) needs the factors alpha and beta")
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko apply with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, "apply")
-        n = images.shape[0]
-        he_shape = tuple(source_he.shape)
-        if he_shape == (3, 2):
-            n_sources = 1
-        elif len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n):
-            n_sources = he_shape[0]
-        else:
-            raise ValueError(f"source_he must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
-        he = self._f32(source_he)
-        mc = None
-        if source_max_c is not None:
-            if source_max_c.numel() != 2 * n_sources or (source_max_c.dim() == 2 and tuple(source_max_c.shape) != (n_sources, 2)) or source_max_c.dim() > 2:
-                raise ValueError(f"source_max_c must hold 2 values per source basis, ({n_sources}, 2), got shape {tuple(source_max_c.shape)}")
-            mc = self._f32(source_max_c)
-        elif stain_matrix is not None:
-            raise ValueError("source_max_c is required to normalise to a reference (it may be None in own-basis mode only)")
+        he, mc, n_sources = self._check_sources(source_he, source_max_c, n, sm is not None)
         a = b = None
         if alpha is not None:
-            if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
-                raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+            _check_factors(alpha, beta, n, 2)
             a, b = self._f32(alpha), self._f32(beta)
-        sm = tmc = None
-        if stain_matrix is not None:
-            if tuple(stain_matrix.shape) != (3, 2):
-                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-            sm = self._f32(stain_matrix)
-            tmc = self._f32(target_max_conc).flatten()
-            if tmc.numel() != 2:
-                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        images = images.contiguous()
-        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
-        code = _dtype_code(images)
-        if out_dtype is None:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
         out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
         with _native.on_device(self.device):
-            if _masking is not None:      # (apply_masked: the same arguments and one more; the rule's mask is a launch of its own in front)
-                mask = self._mask_for(images, *_masking)
-                rc = self._lib.sx_macenko_apply_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, he.data_ptr(), ptr(mc), n_sources, ptr(a), ptr(b),
-                                                       ptr(sm), ptr(tmc), mask.data_ptr(), flags, _native.stream_ptr(self.device))
-                _native.check(rc, "sx_macenko_apply_masked", self._lib)
-                return out
-            rc = self._lib.sx_macenko_apply(images.data_ptr(), out.data_ptr(), code, n, h, w, he.data_ptr(), ptr(mc), n_sources, ptr(a), ptr(b),
-                                            ptr(sm), ptr(tmc), flags, _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_apply", self._lib)
+            if _masking is None:
+                self._call("sx_macenko_apply", images, out, code, n, h, w, he, mc, n_sources, a, b, sm, tmc, flags)
+            else:      # (apply_masked: the same arguments and one more; the rule's mask is a launch of its own in front)
+                self._call("sx_macenko_apply_masked", images, out, code, n, h, w, he, mc, n_sources, a, b, sm, tmc, self._mask_for(images, *_masking), flags)
         return out
 
     # ---- tissue masks (include/stainx_hip.h: sx_macenko_*_masked): the estimate over the masked-in pixels, masked-out pixels copied ----
-    def _mask_for(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
-        """The dense (N, H, W) uint8 mask a masked call reads: the explicit one, or -- ``mask=None`` -- the luminosity rule's, made by an
-        ``sx_tissue_mask`` launch in front of the call on the same stream (one extra streaming pass over the images and its bytes: the
-        library's masked Macenko calls take explicit masks only).  ``images``: dense NCHW on the device."""
-        if mask is not None:
-            mask = _mask_bytes(mask, self.device)
-            if tuple(mask.shape) != (images.shape[0], images.shape[2], images.shape[3]) or mask.dtype != torch.uint8:
-                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(images.shape[0], images.shape[2], images.shape[3])}, got {mask.dtype} {tuple(mask.shape)}")
-            return mask
-        n, _, h, w = images.shape
-        made = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
-        rc = self._lib.sx_tissue_mask(images.data_ptr(), _dtype_code(images), n, h, w, 0, float(luminosity_threshold), made.data_ptr(), None, _native.stream_ptr(self.device))
-        _native.check(rc, "sx_tissue_mask", self._lib)
-        return made
-
-    def _check_masked(self, images: torch.Tensor, what: str) -> torch.Tensor:
-        if self._precision == "sampled":
-            raise ValueError(f"{what} with a mask runs the exact four-pass form; precision='sampled' has no masked form")
-        images = images.to(self.device)
-        self._check_images(images, what)
-        return images.contiguous()
-
     def estimate_masked(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, pooled: bool = False) -> dict[str, torch.Tensor]:
         """``estimate`` over the masked-in pixels only (``mask``: (N, H, W) uint8 / bool, or None: the luminosity rule): ``he`` (rows, 3, 2),
         ``max_c`` (rows, 2), ``tissue`` (rows,) float32 -- the pixels of the selection set -- and ``mask_pixels`` (rows,) int64, the exact
         masked-in counts; rows = N, or 1 with ``pooled`` (one estimate over the masked-in pixels of the batch, the pooled fit's path).  A
         group without an estimate (per tile: fewer than 3 masked-in pixels; pooled: fewer than 3 that also pass the OD filter) has NaN
         rows and ``tissue`` 0."""
-        images = self._check_masked(images, "estimate")
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._masked_images(images, "estimate")
         rows = 1 if pooled else n
         out = {
             "he": torch.empty((rows, 3, 2), dtype=torch.float32, device=self.device),
@@ -617,15 +575,12 @@ class MacenkoHIP(TorchHIPBackendBase):
             "tissue": torch.empty((rows,), dtype=torch.float32, device=self.device),
             "mask_pixels": torch.empty((rows,), dtype=torch.int64, device=self.device),
         }
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        code = _dtype_code(images)
         with _native.on_device(self.device):
             mask = self._mask_for(images, mask, luminosity_threshold)
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_estimate_masked(images.data_ptr(), code, n, h, w, mask.data_ptr(), int(pooled), out["he"].data_ptr(), out["max_c"].data_ptr(),
-                                                      out["tissue"].data_ptr(), out["mask_pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_estimate_masked", self._lib)
+            ws = self._classic_workspace(code, n, h, w)
+            self._call("sx_macenko_estimate_masked", images, code, n, h, w, mask, int(pooled), out["he"], out["max_c"], out["tissue"], out["mask_pixels"], 0, ws, ws.numel())
         self.last_workspace = ws
         return out
 
@@ -638,31 +593,16 @@ class MacenkoHIP(TorchHIPBackendBase):
                          luminosity_threshold: float = 0.8, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, _extra_flags: int = 0) -> torch.Tensor:
         """``transform`` with a tissue mask: the per-tile estimate over the masked-in pixels, those pixels normalised with it, the others
         (and tiles without an estimate) copied.  Always the four-pass form: no routing, no telemetry, no host synchronisation."""
-        images = self._check_masked(images, "transform")
-        flags = int(_extra_flags) | (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0)
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
-        if tuple(stain_matrix.shape) != (3, 2):
-            raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-        sm = self._f32(stain_matrix)
-        tmc = self._f32(target_max_conc).flatten()
-        if tmc.numel() != 2:
-            raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        n, _, h, w = images.shape
-        code = _dtype_code(images)
+        images, n, h, w, code = self._masked_images(images, "transform")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, False)
+        sm, tmc = self._reference(stain_matrix, target_max_conc)
         out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
             mask = self._mask_for(images, mask, luminosity_threshold)
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_transform_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, mask.data_ptr(), sm.data_ptr(), tmc.data_ptr(), flags,
-                                                       ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_transform_masked", self._lib)
+            ws = self._classic_workspace(code, n, h, w)
+            self._call("sx_macenko_transform_masked", images, out, code, n, h, w, mask, sm, tmc, flags | int(_extra_flags), ws, ws.numel())
         self.last_workspace = ws
         return out
 
@@ -671,74 +611,24 @@ class MacenkoHIP(TorchHIPBackendBase):
                      beta: torch.Tensor | None = None, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None) -> torch.Tensor:
         """``apply`` with a tissue mask (all its modes): still one launch for an explicit mask; masked-out pixels, and tiles whose source row
         holds a NaN, are copied."""
-        images = self._check_masked(images, "apply")
+        images = self._masked_images(images, "apply")[0]
         return self.apply(images, source_he, source_max_c, stain_matrix, target_max_conc, alpha=alpha, beta=beta, normalize_to_0_1=normalize_to_0_1,
                           out_dtype=out_dtype, _masking=(mask, luminosity_threshold))
 
     # ---- separation / augmentation with a given source basis and under tissue masks (include/stainx_hip.h, DESIGN.md 4m) ----
-    def _check_sources(self, source_he: torch.Tensor, source_max_c: torch.Tensor | None, n: int, need_max_c: bool) -> tuple[torch.Tensor, torch.Tensor | None, int]:
-        """The shape checks of a given source basis (``apply``'s): float32 device tensors and the number of rows, 1 or N."""
-        he_shape = tuple(source_he.shape)
-        if he_shape == (3, 2):
-            n_sources = 1
-        elif len(he_shape) == 3 and he_shape[1:] == (3, 2) and he_shape[0] in (1, n):
-            n_sources = he_shape[0]
-        else:
-            raise ValueError(f"source_he must have shape (3, 2), (1, 3, 2) or (N, 3, 2) = ({n}, 3, 2), got {he_shape}")
-        mc = None
-        if source_max_c is not None:
-            if source_max_c.numel() != 2 * n_sources or (source_max_c.dim() == 2 and tuple(source_max_c.shape) != (n_sources, 2)) or source_max_c.dim() > 2:
-                raise ValueError(f"source_max_c must hold 2 values per source basis, ({n_sources}, 2), got shape {tuple(source_max_c.shape)}")
-            mc = self._f32(source_max_c)
-        elif need_max_c:
-            raise ValueError("source_max_c is required to normalise to a reference (it may be None in own-basis mode only)")
-        return self._f32(source_he), mc, n_sources
-
     def _separate_call(self, images: torch.Tensor, stain_matrix, target_max_conc, *, source, masking, stains: bool, concentrations: bool, max_conc: bool,
-                       normalize_to_0_1: bool, channels_last: bool, out_dtype) -> dict[str, torch.Tensor | None]:
-        """separate_apply / separate_apply_masked / separate_masked: ``source`` is None (the call's own masked estimate) or
+                       normalize_to_0_1: bool, channels_last: bool, out_dtype, neither: str = "the source basis itself") -> dict[str, torch.Tensor | None]:
+        """separate / separate_apply / separate_apply_masked / separate_masked: ``source`` is None (the call's own estimate) or
         ``(source_he, source_max_c)``; ``masking`` is None or ``(mask, luminosity_threshold)``."""
-        what = "separate"
-        if masking is not None:
-            if channels_last:
-                raise ValueError("the masked Macenko calls take planar (NCHW) tiles: channels_last has no masked form")
-            images = self._check_masked(images, what)
-        else:
-            images = images.to(self.device)
         if not (stains or concentrations):
             raise ValueError("separate: ask for stains, concentrations or both")
-        flags = 0
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = None
-        if (stain_matrix is None) != (target_max_conc is None):
-            raise ValueError("stain_matrix and target_max_conc go together: both (normalised) or neither (the source basis itself)")
-        if channels_last:
-            if images.dim() != 4 or images.shape[3] != 3:
-                raise ValueError(f"Macenko separate with channels_last expects NHWC images with C=3, got shape {tuple(images.shape)}")
-        else:
-            self._check_images(images, what)
-        n = images.shape[0]
+        images, n, h, w, code = self._images(images, channels_last, "Macenko", "separate") if masking is None else self._masked_images(images, "separate")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        sm, tmc = self._reference(stain_matrix, target_max_conc, f"both (normalised) or neither ({neither})")
         he = mc = None
         n_sources = n
         if source is not None:
-            he, mc, n_sources = self._check_sources(source[0], source[1], n, stain_matrix is not None)
-        sm = tmc = None
-        if stain_matrix is not None:
-            if tuple(stain_matrix.shape) != (3, 2):
-                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-            sm = self._f32(stain_matrix)
-            tmc = self._f32(target_max_conc).flatten()
-            if tmc.numel() != 2:
-                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        images = images.contiguous()
-        h, w = (images.shape[1], images.shape[2]) if channels_last else (images.shape[2], images.shape[3])
-        code = _dtype_code(images)
-        if out_dtype is None:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
+            he, mc, n_sources = self._check_sources(source[0], source[1], n, sm is not None)
         out = {
             "stains": torch.empty((2, *images.shape), dtype=out_dtype, device=self.device) if stains else None,
             "concentrations": torch.empty((n, h, w, 2) if channels_last else (n, 2, h, w), dtype=torch.float32, device=self.device) if concentrations else None,
@@ -749,30 +639,21 @@ class MacenkoHIP(TorchHIPBackendBase):
         else:
             out["he"] = torch.empty((n, 3, 2), dtype=torch.float32, device=self.device)
             out["max_c"] = torch.empty((n, 2), dtype=torch.float32, device=self.device) if (max_conc or sm is not None) else None
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        flags |= (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
         with _native.on_device(self.device):
-            stream = _native.stream_ptr(self.device)
             mask = self._mask_for(images, *masking) if masking is not None else None
             if source is None:
-                ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-                rc = self._lib.sx_macenko_separate_masked(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, mask.data_ptr(), ptr(sm), ptr(tmc),
-                                                          ptr(out["he"]), ptr(out["max_c"]), flags, ws.data_ptr(), ws.numel(), stream)
-                _native.check(rc, "sx_macenko_separate_masked", self._lib)
+                ws = self._classic_workspace(code, n, h, w)
+                if mask is None:
+                    self._call("sx_macenko_separate", images, out["stains"], out["concentrations"], code, n, h, w, sm, tmc, out["he"], out["max_c"], flags, ws, ws.numel())
+                else:
+                    self._call("sx_macenko_separate_masked", images, out["stains"], out["concentrations"], code, n, h, w, mask, sm, tmc, out["he"], out["max_c"], flags, ws, ws.numel())
                 self.last_workspace = ws
-            elif mask is not None:
-                rc = self._lib.sx_macenko_separate_apply_masked(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, he.data_ptr(), ptr(mc), n_sources,
-                                                                ptr(sm), ptr(tmc), mask.data_ptr(), flags, stream)
-                _native.check(rc, "sx_macenko_separate_apply_masked", self._lib)
+            elif mask is None:
+                self._call("sx_macenko_separate_apply", images, out["stains"], out["concentrations"], code, n, h, w, he, mc, n_sources, sm, tmc, flags)
             else:
-                rc = self._lib.sx_macenko_separate_apply(images.data_ptr(), ptr(out["stains"]), ptr(out["concentrations"]), code, n, h, w, he.data_ptr(), ptr(mc), n_sources,
-                                                         ptr(sm), ptr(tmc), flags, stream)
-                _native.check(rc, "sx_macenko_separate_apply", self._lib)
+                self._call("sx_macenko_separate_apply_masked", images, out["stains"], out["concentrations"], code, n, h, w, he, mc, n_sources, sm, tmc, mask, flags)
         return out
 
     def separate_apply(self, images: torch.Tensor, source_he: torch.Tensor, source_max_c: torch.Tensor | None, stain_matrix: torch.Tensor | None = None,
@@ -804,41 +685,7 @@ class MacenkoHIP(TorchHIPBackendBase):
                        mask: torch.Tensor | None, luminosity_threshold: float = 0.8, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None) -> torch.Tensor:
         """``augment`` with a tissue mask: the per-tile estimate over the masked-in pixels, the jitter on those pixels; masked-out pixels,
         and tiles without an estimate, are copied by ``transform_masked``'s background rule."""
-        images = self._check_masked(images, "augment")
-        flags = _native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            flags |= _native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16
-        else:
-            out_dtype = torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
-        if (stain_matrix is None) != (target_max_conc is None):
-            raise ValueError("stain_matrix and target_max_conc go together: both (normalise and jitter) or neither (each tile's own stain basis)")
-        n, _, h, w = images.shape
-        if tuple(alpha.shape) != (n, 2) or tuple(beta.shape) != (n, 2):
-            raise ValueError(f"alpha and beta must have shape (N, 2) = ({n}, 2), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
-        sm = tmc = None
-        if stain_matrix is not None:
-            if tuple(stain_matrix.shape) != (3, 2):
-                raise ValueError(f"stain_matrix must have shape (3, 2), got {stain_matrix.shape}")
-            sm = self._f32(stain_matrix)
-            tmc = self._f32(target_max_conc).flatten()
-            if tmc.numel() != 2:
-                raise ValueError(f"target_max_conc must have 2 elements, got {tmc.numel()}")
-        a, b = self._f32(alpha), self._f32(beta)
-        code = _dtype_code(images)
-        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
-            return out
-        with _native.on_device(self.device):
-            mask = self._mask_for(images, mask, luminosity_threshold)
-            ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(code, n, h, w, _native.MACENKO_CLASSIC), self.device)
-            rc = self._lib.sx_macenko_augment_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, mask.data_ptr(), a.data_ptr(), b.data_ptr(),
-                                                     sm.data_ptr() if sm is not None else None, tmc.data_ptr() if tmc is not None else None, flags,
-                                                     ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_macenko_augment_masked", self._lib)
-        self.last_workspace = ws
-        return out
+        return self._augment_call(self._masked_images(images, "augment"), alpha, beta, stain_matrix, target_max_conc, (mask, luminosity_threshold), normalize_to_0_1, False, out_dtype)
 
     def _route(self) -> int:
         """Flag for this call: the four-pass form while a recent call reported tiles the two-pass form could not speculate on.
@@ -903,19 +750,12 @@ class MacenkoHIP(TorchHIPBackendBase):
 
     def compute_reference_stain_matrix(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """Pooled stain estimate ``(HE (3,2), maxC (2,))`` (compute_reference_stain_matrix_torch, :463-519)."""
-        images = images.to(self.device)
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError(f"Macenko fit expects NCHW with C=3, got shape {tuple(images.shape)}")
-        images = images.contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Macenko fit")
         he = torch.empty((3, 2), dtype=torch.float32, device=self.device)
         max_c = torch.empty((2,), dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
-            nbytes = self._lib.sx_macenko_workspace_bytes_for(_dtype_code(images), n, h, w, _native.MACENKO_CLASSIC)
-            ws = self._scratch.get(nbytes, self.device)
-            rc = self._lib.sx_macenko_fit(images.data_ptr(), _dtype_code(images), n, h, w, he.data_ptr(), max_c.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_fit")
+            ws = self._classic_workspace(code, n, h, w)
+            self._call("sx_macenko_fit", images, code, n, h, w, he, max_c, ws, ws.numel())
         self.last_workspace = ws
         return he, max_c
 
@@ -923,6 +763,7 @@ class MacenkoHIP(TorchHIPBackendBase):
     compute_reference_stain_matrix_torch = compute_reference_stain_matrix
 
     # ---- staged pooled fit for a batch sharded across ranks (see stainx_amd/distributed.py) ----------
+    # (the pooled fit's host path, profiled call by call -- tools/host_time_pooled.py: the dfit_* / pfit_* calls stay written out)
     def dfit_moments(self, images: torch.Tensor) -> torch.Tensor:
         images = images.to(self.device)
         if images.dim() != 4 or images.shape[1] != 3:
@@ -934,7 +775,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._scratch.get(self._lib.sx_macenko_workspace_bytes_for(_dtype_code(images), n, h, w, _native.MACENKO_CLASSIC), self.device)
             rc = self._lib.sx_macenko_dfit_moments(images.data_ptr(), _dtype_code(images), n, h, w, mom.data_ptr(), ws.data_ptr(), ws.numel(),
                                                    _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_dfit_moments")
+        self._check(rc, "sx_macenko_dfit_moments")
         return mom
 
     def dfit_begin(self, moments: torch.Tensor) -> torch.Tensor:
@@ -942,7 +783,7 @@ class MacenkoHIP(TorchHIPBackendBase):
         moments = moments.to(self.device, torch.float64).contiguous()
         with _native.on_device(self.device):
             rc = self._lib.sx_macenko_dfit_begin(moments.data_ptr(), state.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_dfit_begin")
+        self._check(rc, "sx_macenko_dfit_begin")
         return state
 
     def dfit_histogram(self, images: torch.Tensor, state: torch.Tensor, stage: int) -> torch.Tensor:
@@ -952,21 +793,21 @@ class MacenkoHIP(TorchHIPBackendBase):
         with _native.on_device(self.device):
             rc = self._lib.sx_macenko_dfit_histogram(images.data_ptr(), _dtype_code(images), n, h, w, state.data_ptr(), int(stage), hist.data_ptr(),
                                                      _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_dfit_histogram")
+        self._check(rc, "sx_macenko_dfit_histogram")
         return hist
 
     def dfit_advance(self, state: torch.Tensor, stage: int, hist: torch.Tensor) -> None:
         hist = hist.to(self.device, torch.int64).contiguous()
         with _native.on_device(self.device):
             rc = self._lib.sx_macenko_dfit_advance(state.data_ptr(), int(stage), hist.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_dfit_advance")
+        self._check(rc, "sx_macenko_dfit_advance")
 
     def dfit_result(self, state: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         he = torch.empty((3, 2), dtype=torch.float32, device=self.device)
         max_c = torch.empty((2,), dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
             rc = self._lib.sx_macenko_dfit_result(state.data_ptr(), he.data_ptr(), max_c.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_dfit_result")
+        self._check(rc, "sx_macenko_dfit_result")
         return he, max_c
 
     # ---- the same pooled fit across ranks on the bracket machinery (three passes; see stainx_amd/distributed.py) ----
@@ -992,7 +833,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_stats(images.data_ptr(), _dtype_code(images), n, h, w, mom.data_ptr(), sample.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_stats")
+        self._check(rc, "sx_macenko_pfit_stats")
         self.last_workspace = ws
         return mom, sample
 
@@ -1004,7 +845,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_plane(moments.data_ptr(), int(n_all), sample_union.data_ptr(), int(sample_count), n, h, w, ws.data_ptr(), ws.numel(),
                                                  _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_plane")
+        self._check(rc, "sx_macenko_pfit_plane")
 
     def pfit_pass(self, images: torch.Tensor, stage: int, n_all: int, sample_count: int) -> torch.Tensor:
         images = images.to(self.device).contiguous()
@@ -1014,7 +855,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_pass(images.data_ptr(), _dtype_code(images), n, h, w, int(stage), int(n_all), int(sample_count), sums.data_ptr(), ws.data_ptr(),
                                                 ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_pass")
+        self._check(rc, "sx_macenko_pfit_pass")
         return sums
 
     def pfit_gather(self, sums_global: torch.Tensor, stage: int, n_all: int, sample_count: int, shape: tuple[int, int, int], share: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -1026,7 +867,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_gather(sums_global.data_ptr(), int(stage), int(n_all), int(sample_count), n, h, w, int(share), compact.data_ptr(), counts.data_ptr(),
                                                   ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_gather")
+        self._check(rc, "sx_macenko_pfit_gather")
         return compact, counts
 
     def pfit_finish(self, gathered_compact: torch.Tensor, gathered_counts: torch.Tensor, stage: int, n_all: int, sample_count: int, shape: tuple[int, int, int]):
@@ -1042,7 +883,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_finish(gathered_compact.data_ptr(), gathered_counts.data_ptr(), world, share, int(stage), int(n_all), int(sample_count), n, h, w,
                                                   he.data_ptr(), max_c.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_finish")
+        self._check(rc, "sx_macenko_pfit_finish")
         self.last_workspace = ws
         return (he, max_c, status) if stage == 1 else None
 
@@ -1058,7 +899,7 @@ class MacenkoHIP(TorchHIPBackendBase):
         with _native.on_device(self.device):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_stats_packed(images.data_ptr(), _dtype_code(images), n, h, w, record.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_stats_packed")
+        self._check(rc, "sx_macenko_pfit_stats_packed")
         self.last_workspace = ws
         return record
 
@@ -1079,7 +920,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_plane_packed(gathered.data_ptr(), world, _c.cast(counts, _c.c_void_p), expected_tiles.data_ptr() if expected_tiles is not None else None,
                                                         stale.data_ptr(), int(n_all), int(sample_count), n, h, w, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_plane_packed")
+        self._check(rc, "sx_macenko_pfit_plane_packed")
         return stale
 
     def pfit_gather_packed(self, sums_global: torch.Tensor, stage: int, n_all: int, sample_count: int, shape: tuple[int, int, int], share: int, stale: torch.Tensor | None) -> torch.Tensor:
@@ -1090,7 +931,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_gather_packed(sums_global.data_ptr(), int(stage), int(n_all), int(sample_count), n, h, w, int(share),
                                                          stale.data_ptr() if stale is not None else None, row.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_gather_packed")
+        self._check(rc, "sx_macenko_pfit_gather_packed")
         return row
 
     def pfit_finish_packed(self, gathered_rows: torch.Tensor, stage: int, n_all: int, sample_count: int, shape: tuple[int, int, int], share: int):
@@ -1105,7 +946,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             ws = self._pfit_ws(n, h, w)
             rc = self._lib.sx_macenko_pfit_finish_packed(gathered_rows.data_ptr(), world, int(share), int(stage), int(n_all), int(sample_count), n, h, w, he.data_ptr(), max_c.data_ptr(),
                                                          status.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_pfit_finish_packed")
+        self._check(rc, "sx_macenko_pfit_finish_packed")
         self.last_workspace = ws
         return (he, max_c, status) if stage == 1 else None
 
@@ -1115,8 +956,7 @@ class MacenkoHIP(TorchHIPBackendBase):
             raise RuntimeError("no transform / fit has run on this backend yet")
         raw = torch.empty((n_groups, _native.MACENKO_PARAM_FLOATS), dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
-            rc = self._lib.sx_macenko_tile_params(self.last_workspace.data_ptr(), n_groups, raw.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_macenko_tile_params")
+            self._call("sx_macenko_tile_params", self.last_workspace, n_groups, raw)
         raw = raw.cpu()
         return {"n_kept": raw[:, 0].long(), "use_all": raw[:, 1].long(), "vecs": raw[:, 2:8].reshape(-1, 3, 2), "phi_lo": raw[:, 8],
                 "phi_hi": raw[:, 9], "he": raw[:, 10:16].reshape(-1, 3, 2), "max_c": raw[:, 16:18], "fell_back": raw[:, 18].long(),
@@ -1128,62 +968,48 @@ class VahadaneHIP(MacenkoHIP):
     percentile concentrations of a given basis (sx_stain_max_concentrations).  Everything downstream of an estimate -- ``apply*``,
     ``separate_apply*`` -- is the Macenko engine's."""
 
-    def _planar(self, images: torch.Tensor, what: str) -> torch.Tensor:
-        images = images.to(self.device)
-        self._check_images(images, what)
-        return images.contiguous()
-
-    def _vahadane_workspace(self, code: int, n: int, h: int, w: int) -> torch.Tensor:
-        return self._scratch.get(self._lib.sx_vahadane_workspace_bytes(code, n, h, w), self.device)
+    def _matrices(self, matrices: torch.Tensor, rows: int, name: str) -> torch.Tensor:
+        matrices = self._f32(matrices).reshape(-1, 3, 2)
+        if matrices.shape[0] not in (1, rows):
+            raise ValueError(f"{name} must hold 1 or {rows} stain matrices, got {matrices.shape[0]}")
+        return matrices
 
     def vahadane_estimate(self, images: torch.Tensor, init: torch.Tensor, *, regularizer: float = 0.1, iterations: int = 30, pooled: bool = False, masked: bool = False,
                           mask: torch.Tensor | None = None, luminosity_threshold: float = 0.8, max_conc: bool = True) -> dict[str, torch.Tensor | None]:
         """``he`` (rows, 3, 2), ``max_c`` (rows, 2) or None, ``pixels`` (rows,) int64 -- the exact |S| --; rows = N, or 1 with ``pooled``.
         ``init``: (1, 3, 2) or (rows, 3, 2).  ``masked``: over ``mask`` (N, H, W), or with ``mask=None`` over the luminosity rule's
         mask (an ``sx_tissue_mask`` launch in front).  A group without a masked-in pixel has NaN rows and 0 pixels."""
-        images = self._planar(images, "estimate")
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Macenko", "estimate")
         rows = 1 if pooled else n
-        init = self._f32(init).reshape(-1, 3, 2)
-        if init.shape[0] not in (1, rows):
-            raise ValueError(f"init must hold 1 or {rows} stain matrices, got {init.shape[0]}")
+        init = self._matrices(init, rows, "init")
         out = {
             "he": torch.empty((rows, 3, 2), dtype=torch.float32, device=self.device),
             "max_c": torch.empty((rows, 2), dtype=torch.float32, device=self.device) if max_conc else None,
             "pixels": torch.empty((rows,), dtype=torch.int64, device=self.device),
         }
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        code = _dtype_code(images)
         with _native.on_device(self.device):
             mask = self._mask_for(images, mask, luminosity_threshold) if masked else None
-            ws = self._vahadane_workspace(code, n, h, w)
-            rc = self._lib.sx_vahadane_estimate(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), init.data_ptr(), init.shape[0],
-                                                float(regularizer), int(iterations), out["he"].data_ptr(), out["max_c"].data_ptr() if max_conc else None,
-                                                out["pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_vahadane_estimate", self._lib)
+            ws = self._scratch.get(self._lib.sx_vahadane_workspace_bytes(code, n, h, w), self.device)
+            self._call("sx_vahadane_estimate", images, code, n, h, w, mask, int(pooled), init, init.shape[0], float(regularizer), int(iterations), out["he"], out["max_c"],
+                       out["pixels"], 0, ws, ws.numel())
         return out
 
     def max_concentrations(self, images: torch.Tensor, stain_matrices: torch.Tensor, *, pooled: bool = False, masked: bool = False, mask: torch.Tensor | None = None,
                            luminosity_threshold: float = 0.8) -> dict[str, torch.Tensor]:
         """The nearest-rank 99th percentiles of the concentrations of GIVEN bases (1 or rows) over each group's masked-in pixels:
         ``max_c`` (rows, 2) float32 and ``pixels`` (rows,) int64."""
-        images = self._planar(images, "max_concentrations")
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Macenko", "max_concentrations")
         rows = 1 if pooled else n
-        he = self._f32(stain_matrices).reshape(-1, 3, 2)
-        if he.shape[0] not in (1, rows):
-            raise ValueError(f"stain_matrices must hold 1 or {rows} stain matrices, got {he.shape[0]}")
+        he = self._matrices(stain_matrices, rows, "stain_matrices")
         out = {"max_c": torch.empty((rows, 2), dtype=torch.float32, device=self.device), "pixels": torch.empty((rows,), dtype=torch.int64, device=self.device)}
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-        code = _dtype_code(images)
         with _native.on_device(self.device):
             mask = self._mask_for(images, mask, luminosity_threshold) if masked else None
-            ws = self._vahadane_workspace(code, n, h, w)
-            rc = self._lib.sx_stain_max_concentrations(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), he.data_ptr(), he.shape[0],
-                                                       out["max_c"].data_ptr(), out["pixels"].data_ptr(), 0, ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_stain_max_concentrations", self._lib)
+            ws = self._scratch.get(self._lib.sx_vahadane_workspace_bytes(code, n, h, w), self.device)
+            self._call("sx_stain_max_concentrations", images, code, n, h, w, mask, int(pooled), he, he.shape[0], out["max_c"], out["pixels"], 0, ws, ws.numel())
         return out
 
 
@@ -1195,35 +1021,28 @@ class LuminosityHIP(TorchHIPBackendBase):
     def percentile(self, images: torch.Tensor, percentile: float, *, pooled: bool = False, mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(luminance, pixels)``: (rows,) float32 -- NaN for an empty set -- and (rows,) int64, rows = N or 1 with ``pooled``.  ``mask``:
         (N, H, W) uint8 / bool, which pixels enter the set."""
-        images = images.to(self.device).contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, None)
         rows = 1 if pooled else n
         luminance = torch.full((rows,), float("nan"), dtype=torch.float32, device=self.device)
         pixels = torch.zeros((rows,), dtype=torch.int64, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return luminance, pixels
-        code = _dtype_code(images)
         mask = _mask_bytes(mask, self.device)
         with _native.on_device(self.device):
             ws = self._scratch.get(self._lib.sx_luminosity_workspace_bytes(code, n, h, w), self.device)
-            rc = self._lib.sx_luminosity_percentile(images.data_ptr(), code, n, h, w, mask.data_ptr() if mask is not None else None, int(pooled), float(percentile),
-                                                    luminance.data_ptr(), pixels.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_luminosity_percentile", self._lib)
+            self._call("sx_luminosity_percentile", images, code, n, h, w, mask, int(pooled), float(percentile), luminance, pixels, ws, ws.numel())
         return luminance, pixels
 
     def apply(self, images: torch.Tensor, luminance: torch.Tensor) -> torch.Tensor:
         """The map with GIVEN percentiles: ``luminance`` holds one row, or one per tile."""
-        images = images.to(self.device).contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, None)
         luminance = self._f32(luminance).reshape(-1)
         if luminance.shape[0] not in (1, n):
             raise ValueError(f"luminance must hold 1 or {n} rows, got {luminance.shape[0]}")
         out = torch.empty_like(images)
-        if n == 0 or h * w == 0:
-            return out
-        with _native.on_device(self.device):
-            rc = self._lib.sx_luminosity_apply(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, luminance.data_ptr(), luminance.shape[0], _native.stream_ptr(self.device))
-        _native.check(rc, "sx_luminosity_apply", self._lib)
+        if n * h * w != 0:
+            with _native.on_device(self.device):
+                self._call("sx_luminosity_apply", images, out, code, n, h, w, luminance, luminance.shape[0])
         return out
 
 
@@ -1233,29 +1052,8 @@ class DeconvHIP(TorchHIPBackendBase):
     new values are copied into the same tensors uses the new values."""
 
     def _bases(self, basis: torch.Tensor, n: int, what: str) -> tuple[torch.Tensor, int]:
-        shape = tuple(basis.shape)
-        if shape == (3, 3):
-            rows = 1
-        elif len(shape) == 3 and shape[1:] == (3, 3) and shape[0] in (1, n):
-            rows = shape[0]
-        else:
-            raise ValueError(f"{what} must have shape (3, 3), (1, 3, 3) or (N, 3, 3) = ({n}, 3, 3), got {shape}")
+        rows = _basis_rows(basis, n, what)
         return self._f32(basis), rows
-
-    @staticmethod
-    def _dims(images: torch.Tensor, channels_last: bool, what: str) -> tuple[int, int, int]:
-        if images.dim() != 4 or images.shape[3 if channels_last else 1] != 3:
-            raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {tuple(images.shape)}")
-        return (images.shape[0], images.shape[1], images.shape[2]) if channels_last else (images.shape[0], images.shape[2], images.shape[3])
-
-    @staticmethod
-    def _out_flags(images: torch.Tensor, out_dtype: torch.dtype | None, normalize_to_0_1: bool, channels_last: bool) -> tuple[int, torch.dtype]:
-        flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
-        if out_dtype is not None and out_dtype != images.dtype:
-            if images.dtype != torch.uint8 or out_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"out_dtype is supported for uint8 input and bfloat16 / float16 output, got {images.dtype} -> {out_dtype}")
-            return flags | (_native.MACENKO_OUT_BF16 if out_dtype == torch.bfloat16 else _native.MACENKO_OUT_F16), out_dtype
-        return flags, torch.float32 if (normalize_to_0_1 and images.dtype == torch.uint8) else images.dtype
 
     def apply(self, images: torch.Tensor, basis: torch.Tensor, target: torch.Tensor | None = None, *, alpha: torch.Tensor | None = None,
               beta: torch.Tensor | None = None, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False,
@@ -1263,75 +1061,48 @@ class DeconvHIP(TorchHIPBackendBase):
         """``C' = alpha * inverse(basis) OD + beta`` rebuilt with ``target`` (None: ``basis``).  ``basis`` / ``target``: (3, 3), (1, 3, 3)
         or (N, 3, 3); ``alpha`` / ``beta``: (N, 3), both or neither.  ``masking``: None, or ``(explicit mask or None, luminosity
         threshold)`` -- the masked call (planar tiles only); the rule's mask is an ``sx_tissue_mask`` launch in front."""
-        images = images.to(self.device)
-        n, h, w = self._dims(images, channels_last, "apply")
-        _dtype_code(images)
-        flags, out_dtype = self._out_flags(images, out_dtype, normalize_to_0_1, channels_last)
-        if (alpha is None) != (beta is None):
-            raise ValueError("alpha and beta go together: both or neither")
         if masking is not None and channels_last:
             raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "deconvolution", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
         b, n_bases = self._bases(basis, n, "basis")
         t, n_targets = (None, 0) if target is None else self._bases(target, n, "target")
+        if (alpha is None) != (beta is None):
+            raise ValueError("alpha and beta go together: both or neither")
         fa = fb = None
         if alpha is not None:
-            if tuple(alpha.shape) != (n, 3) or tuple(beta.shape) != (n, 3):
-                raise ValueError(f"alpha and beta must have shape (N, 3) = ({n}, 3), got {tuple(alpha.shape)} and {tuple(beta.shape)}")
+            _check_factors(alpha, beta, n, 3)
             fa, fb = self._f32(alpha), self._f32(beta)
-        mask = None
-        if masking is not None and masking[0] is not None:
-            mask = _mask_bytes(masking[0], self.device)
-            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
-                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
-        images = images.contiguous()
         out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
+        if n * h * w == 0:
             return out
-
-        def ptr(x):
-            return x.data_ptr() if x is not None else None
-
-        code, stream = _dtype_code(images), _native.stream_ptr(self.device)
         with _native.on_device(self.device):
-            if masking is not None:
-                if mask is None:
-                    mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
-                    rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
-                    _native.check(rc, "sx_tissue_mask", self._lib)
-                rc = self._lib.sx_deconv_apply_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, ptr(t), n_targets, ptr(fa), ptr(fb),
-                                                      mask.data_ptr(), flags, stream)
-                _native.check(rc, "sx_deconv_apply_masked", self._lib)
+            if masking is None:
+                self._call("sx_deconv_apply", images, out, code, n, h, w, b, n_bases, t, n_targets, fa, fb, flags)
             else:
-                rc = self._lib.sx_deconv_apply(images.data_ptr(), out.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, ptr(t), n_targets, ptr(fa), ptr(fb), flags, stream)
-                _native.check(rc, "sx_deconv_apply", self._lib)
+                self._call("sx_deconv_apply_masked", images, out, code, n, h, w, b, n_bases, t, n_targets, fa, fb, self._mask_for(images, *masking), flags)
         return out
 
     def separate(self, images: torch.Tensor, basis: torch.Tensor, *, stains: bool = True, concentrations: bool = False, normalize_to_0_1: bool = False,
                  out_dtype: torch.dtype | None = None, channels_last: bool = False) -> tuple[torch.Tensor | None, torch.Tensor | None]:
         """``(images (3, N, ...) or None, concentrations (N, 3, H, W) / (N, H, W, 3) float32 or None)``: image i is the tile rebuilt from
         stain i alone -- the bits of ``apply`` with ``alpha = e_i``."""
-        images = images.to(self.device)
-        n, h, w = self._dims(images, channels_last, "separate")
         if not stains and not concentrations:
             raise ValueError("separate: ask for the stain images, the concentrations, or both")
-        _dtype_code(images)
-        flags, out_dtype = self._out_flags(images, out_dtype if stains else None, normalize_to_0_1 and stains, channels_last)
+        images, n, h, w, code = self._images(images, channels_last, "deconvolution", "separate")
+        flags, out_dtype = _out_flags(images, out_dtype if stains else None, normalize_to_0_1 and stains, channels_last)
         b, n_bases = self._bases(basis, n, "basis")
-        images = images.contiguous()
         imgs = torch.empty((3,) + tuple(images.shape), dtype=out_dtype, device=self.device) if stains else None
         conc = torch.empty((n, h, w, 3) if channels_last else (n, 3, h, w), dtype=torch.float32, device=self.device) if concentrations else None
-        if n == 0 or h * w == 0:
-            return imgs, conc
-        with _native.on_device(self.device):
-            rc = self._lib.sx_deconv_separate(images.data_ptr(), imgs.data_ptr() if stains else None, conc.data_ptr() if concentrations else None, _dtype_code(images),
-                                              n, h, w, b.data_ptr(), n_bases, flags, _native.stream_ptr(self.device))
-            _native.check(rc, "sx_deconv_separate", self._lib)
+        if n * h * w != 0:
+            with _native.on_device(self.device):
+                self._call("sx_deconv_separate", images, imgs, conc, code, n, h, w, b, n_bases, flags)
         return imgs, conc
 
     def combine(self, concentrations: torch.Tensor, basis: torch.Tensor, *, out_dtype: torch.dtype = torch.uint8, normalize_to_0_1: bool = False,
                 channels_last: bool = False) -> torch.Tensor:
         """``separate``'s inverse: (N, 3, H, W) float32 concentrations (NHWC with ``channels_last``) -> the tile, cast to ``out_dtype``."""
-        n, h, w = self._dims(concentrations, channels_last, "combine")
+        n, h, w = _image_shape(concentrations, channels_last, "deconvolution", "combine")
         if concentrations.dtype != torch.float32:
             raise ValueError(f"concentrations must be float32, got {concentrations.dtype}")
         if out_dtype not in _native.DTYPE_CODES:
@@ -1341,12 +1112,28 @@ class DeconvHIP(TorchHIPBackendBase):
         b, n_bases = self._bases(basis, n, "basis")
         conc = concentrations.to(self.device).contiguous()
         out = torch.empty(tuple(conc.shape), dtype=out_dtype, device=self.device)
-        if n == 0 or h * w == 0:
-            return out
-        flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+        if n * h * w != 0:
+            flags = (_native.MACENKO_NORMALIZE_0_1 if normalize_to_0_1 else 0) | (_native.MACENKO_CHANNELS_LAST if channels_last else 0)
+            with _native.on_device(self.device):
+                self._call("sx_deconv_combine", conc, out, _native.DTYPE_CODES[out_dtype], n, h, w, b, n_bases, flags)
+        return out
+
+    def _sums(self, what: str, images: torch.Tensor, basis: torch.Tensor, scalars: tuple, words: int, per_tile: bool, channels_last: bool, masking: tuple | None) -> torch.Tensor:
+        """quantify / moments: the (S, words) int64 rows of ``sx_deconv_<what>[_masked]``, S = N (``per_tile``) or 1; zeros for an empty batch."""
+        if masking is not None and channels_last:
+            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "deconvolution", what)
+        b, n_bases = self._bases(basis, n, "basis")
+        sets = n if per_tile else 1
+        if n * h * w == 0:
+            return torch.zeros((sets, words), dtype=torch.int64, device=self.device)
+        out = torch.empty((sets, words), dtype=torch.int64, device=self.device)
+        flags = _native.MACENKO_CHANNELS_LAST if channels_last else 0
         with _native.on_device(self.device):
-            rc = self._lib.sx_deconv_combine(conc.data_ptr(), out.data_ptr(), _native.DTYPE_CODES[out_dtype], n, h, w, b.data_ptr(), n_bases, flags, _native.stream_ptr(self.device))
-            _native.check(rc, "sx_deconv_combine", self._lib)
+            if masking is None:
+                self._call(f"sx_deconv_{what}", images, code, n, h, w, b, n_bases, *scalars, int(bool(per_tile)), out, flags)
+            else:
+                self._call(f"sx_deconv_{what}_masked", images, code, n, h, w, b, n_bases, *scalars, int(bool(per_tile)), out, self._mask_for(images, *masking), flags)
         return out
 
     QUANT_WORDS = 3 * 256 + 3 + 1      # a row of sx_deconv_quantify's output: [counts 3 x 256][sums 3][pixels 1]
@@ -1356,42 +1143,12 @@ class DeconvHIP(TorchHIPBackendBase):
         """``(counts (S, 3, 256), sums (S, 3), pixels (S,))``, int64 views of ONE (S, 772) tensor; S = N (``per_tile``) or 1.  The
         histograms of the three concentrations ``separate`` would write, their fixed-point (2^-16) sums and the counted pixels: a memset
         and one launch, no map.  ``masking`` as in ``apply``."""
-        images = images.to(self.device)
-        n, h, w = self._dims(images, channels_last, "quantify")
-        code = _dtype_code(images)
         if not (isinstance(bin_log2, int) and 0 <= bin_log2 <= 8):
             raise ValueError(f"bin_log2 must be an integer in [0, 8], got {bin_log2!r}")
         if not (isinstance(zero_bin, int) and 0 <= zero_bin <= 255):
             raise ValueError(f"zero_bin must be an integer in [0, 255], got {zero_bin!r}")
-        if masking is not None and channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
-        b, n_bases = self._bases(basis, n, "basis")
-        mask = None
-        if masking is not None and masking[0] is not None:
-            mask = _mask_bytes(masking[0], self.device)
-            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
-                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
-        sets = n if per_tile else 1
-        if n == 0 or h * w == 0:
-            out = torch.zeros((sets, self.QUANT_WORDS), dtype=torch.int64, device=self.device)
-        else:
-            images = images.contiguous()
-            out = torch.empty((sets, self.QUANT_WORDS), dtype=torch.int64, device=self.device)
-            flags = _native.MACENKO_CHANNELS_LAST if channels_last else 0
-            stream = _native.stream_ptr(self.device)
-            with _native.on_device(self.device):
-                if masking is not None:
-                    if mask is None:
-                        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
-                        rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
-                        _native.check(rc, "sx_tissue_mask", self._lib)
-                    rc = self._lib.sx_deconv_quantify_masked(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, bin_log2, zero_bin, int(bool(per_tile)), out.data_ptr(),
-                                                             mask.data_ptr(), flags, stream)
-                    _native.check(rc, "sx_deconv_quantify_masked", self._lib)
-                else:
-                    rc = self._lib.sx_deconv_quantify(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, bin_log2, zero_bin, int(bool(per_tile)), out.data_ptr(), flags, stream)
-                    _native.check(rc, "sx_deconv_quantify", self._lib)
-        return out[:, :768].view(sets, 3, 256), out[:, 768:771], out[:, 771]
+        out = self._sums("quantify", images, basis, (bin_log2, zero_bin), self.QUANT_WORDS, per_tile, channels_last, masking)
+        return out[:, :768].view(out.shape[0], 3, 256), out[:, 768:771], out[:, 771]
 
     MOMENT_WORDS = 7      # a row of sx_deconv_moments' output: [sums 3][squares 3][pixels 1]
 
@@ -1400,46 +1157,20 @@ class DeconvHIP(TorchHIPBackendBase):
         """``(sums (S, 3), squares (S, 3), pixels (S,))``, int64 views of ONE (S, 7) tensor; S = N (``per_tile``) or 1.  Fixed-point sums
         (2^-16) and sums of squares (2^-24) of the three concentrations ``separate`` would write, and the counted pixels: a memset and one
         launch, no map.  ``masking`` as in ``apply``."""
-        images = images.to(self.device)
-        n, h, w = self._dims(images, channels_last, "moments")
-        code = _dtype_code(images)
-        if masking is not None and channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only")
-        b, n_bases = self._bases(basis, n, "basis")
-        mask = None
-        if masking is not None and masking[0] is not None:
-            mask = _mask_bytes(masking[0], self.device)
-            if tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8:
-                raise ValueError(f"mask must be uint8 / bool (N, H, W) = {(n, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
-        sets = n if per_tile else 1
-        if n == 0 or h * w == 0:
-            out = torch.zeros((sets, self.MOMENT_WORDS), dtype=torch.int64, device=self.device)
-        else:
-            images = images.contiguous()
-            out = torch.empty((sets, self.MOMENT_WORDS), dtype=torch.int64, device=self.device)
-            flags = _native.MACENKO_CHANNELS_LAST if channels_last else 0
-            stream = _native.stream_ptr(self.device)
-            with _native.on_device(self.device):
-                if masking is not None:
-                    if mask is None:
-                        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
-                        rc = self._lib.sx_tissue_mask(images.data_ptr(), code, n, h, w, 0, float(masking[1]), mask.data_ptr(), None, stream)
-                        _native.check(rc, "sx_tissue_mask", self._lib)
-                    rc = self._lib.sx_deconv_moments_masked(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, int(bool(per_tile)), out.data_ptr(), mask.data_ptr(), flags, stream)
-                    _native.check(rc, "sx_deconv_moments_masked", self._lib)
-                else:
-                    rc = self._lib.sx_deconv_moments(images.data_ptr(), code, n, h, w, b.data_ptr(), n_bases, int(bool(per_tile)), out.data_ptr(), flags, stream)
-                    _native.check(rc, "sx_deconv_moments", self._lib)
+        out = self._sums("moments", images, basis, (), self.MOMENT_WORDS, per_tile, channels_last, masking)
         return out[:, 0:3], out[:, 3:6], out[:, 6]
 
 
 class ReinhardHIP(TorchHIPBackendBase):
     """Reinhard LAB statistics matching on the GPU (numerics of ReinhardTorch, torch_backend.py:304-355)."""
 
-    @staticmethod
-    def _check(images: torch.Tensor) -> None:
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {tuple(images.shape)}")
+    def __init__(self, device: str | torch.device | None = None):
+        super().__init__(device)
+        self.last_workspace: torch.Tensor | None = None
+        self._ws_shape: dict[int, tuple[int, int, int]] = {}      # workspace pointer -> the (n, h, w) of the last call on it (see _workspace)
+        # workspaces of their own: the pooled transform's "last shape" bookkeeping is not touched by the per-tile and the masked calls
+        self._tile_scratch = _native.Scratch()
+        self._masked_scratch = _native.Scratch()
 
     def _workspace(self, n: int, h: int, w: int, ready: bool = False, code: int | None = None) -> torch.Tensor:
         """The stream's workspace.  Its arrival counters lie where (n, h, w) puts them and are zero between calls OF THAT SHAPE: the
@@ -1448,173 +1179,103 @@ class ReinhardHIP(TorchHIPBackendBase):
         # (`code`: the transform's element type -- a float32 batch gets room for its tiles' 8-bit codes behind the workspace proper)
         base = int(self._lib.sx_reinhard_workspace_bytes(n, h, w))
         ws = self._scratch.get(base if code is None else int(self._lib.sx_reinhard_workspace_bytes_for(code, n, h, w)), self.device)
-        shapes = self.__dict__.setdefault("_ws_shape", {})
         key = (int(n), int(h), int(w))
-        if ready and shapes.get(ws.data_ptr()) != key:      # (the workspace proper: the codes behind it need no clearing)
-            _native.check(self._lib.sx_reinhard_workspace_init(ws.data_ptr(), base, _native.stream_ptr(self.device)), "sx_reinhard_workspace_init")
-        shapes[ws.data_ptr()] = key
+        if ready and self._ws_shape.get(ws.data_ptr()) != key:      # (the workspace proper: the codes behind it need no clearing)
+            self._call("sx_reinhard_workspace_init", ws, base)
+        self._ws_shape[ws.data_ptr()] = key
         self.last_workspace = ws
         return ws
 
+    def _forget_shape(self) -> None:
+        self._ws_shape.pop(self.last_workspace.data_ptr(), None)      # (a failed call may have left counters behind)
+
     def workspace_status(self) -> int:
         """Bit 0: a transform found the workspace not in its ready state (synchronises; for tests and diagnosis)."""
-        ws = getattr(self, "last_workspace", None)
+        ws = self.last_workspace
         off = int(self._lib.sx_reinhard_workspace_status_offset())
         return 0 if ws is None else int(ws[off:off + 4].view(torch.int32).item())
 
     def compute_reference_mean_std(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Reinhard")
         mean = torch.empty(3, dtype=torch.float32, device=self.device)
         std = torch.empty(3, dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
             ws = self._workspace(n, h, w)
-            rc = self._lib.sx_reinhard_fit(images.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_fit")
+            self._call("sx_reinhard_fit", images, code, n, h, w, mean, std, ws, ws.numel())
         return mean, std
 
     compute_reference_mean_std_torch = compute_reference_mean_std
 
     def transform(self, images: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor) -> torch.Tensor:
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
+        images, n, h, w, code = self._images(images, False, "Reinhard")
+        _reference_statistics(reference_mean, reference_std)
         mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
-        if mean.numel() != 3 or std.numel() != 3:
-            raise ValueError("reference_mean / reference_std must have 3 elements")
-        n, _, h, w = images.shape
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
-            ws = self._workspace(n, h, w, ready=True, code=_dtype_code(images))
-            rc = self._lib.sx_reinhard_transform_ready(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(),
-                                                       std.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        if rc != 0:
-            self.__dict__.get("_ws_shape", {}).pop(ws.data_ptr(), None)      # (a failed call may have left counters behind)
-        _native.check(rc, "sx_reinhard_transform_ready")
+            ws = self._workspace(n, h, w, ready=True, code=code)
+            self._call("sx_reinhard_transform_ready", images, out, code, n, h, w, mean, std, ws, ws.numel(), on_failure=self._forget_shape)
         return out
 
     # ---- per-tile statistics, given statistics (include/stainx_hip.h: sx_reinhard_tile_stats ...) ---------
-    def _tiles_workspace(self, n: int, h: int, w: int, code: int) -> torch.Tensor:
-        # a workspace of its own: the pooled transform's "last shape" bookkeeping (see _workspace) is not touched by the per-tile calls
-        scratch = self.__dict__.get("_tile_scratch")
-        if scratch is None:
-            scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
-        return scratch.get(int(self._lib.sx_reinhard_tiles_workspace_bytes(code, n, h, w)), self.device)
-
     def tile_statistics(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """LAB mean and unbiased standard deviation of every tile: two (N, 3) float32 tensors, one statistics pass."""
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Reinhard")
         mean = torch.empty((n, 3), dtype=torch.float32, device=self.device)
         std = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        if images.numel() == 0:
-            return mean, std
-        with _native.on_device(self.device):
-            ws = self._tiles_workspace(n, h, w, _dtype_code(images))
-            rc = self._lib.sx_reinhard_tile_stats(images.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_tile_stats")
+        if n * h * w != 0:
+            with _native.on_device(self.device):
+                ws = self._tile_scratch.get(int(self._lib.sx_reinhard_tiles_workspace_bytes(code, n, h, w)), self.device)
+                self._call("sx_reinhard_tile_stats", images, code, n, h, w, mean, std, ws, ws.numel())
         return mean, std
 
     def transform_tiles(self, images: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor, *, return_statistics: bool = False):
         """Every tile normalised with its OWN statistics (two streaming launches for the batch).  With ``return_statistics`` also the
         tiles' (N, 3) mean and standard deviation."""
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
+        images, n, h, w, code = self._images(images, False, "Reinhard")
+        _reference_statistics(reference_mean, reference_std)
         mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
-        if mean.numel() != 3 or std.numel() != 3:
-            raise ValueError("reference_mean / reference_std must have 3 elements")
-        n, _, h, w = images.shape
         out = torch.empty_like(images)
         tile_mean = tile_std = None
         if return_statistics:
             tile_mean = torch.empty((n, 3), dtype=torch.float32, device=self.device)
             tile_std = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        if images.numel() != 0:
+        if n * h * w != 0:
             with _native.on_device(self.device):
-                ws = self._tiles_workspace(n, h, w, _dtype_code(images))
-                rc = self._lib.sx_reinhard_transform_tiles(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
-                                                           None if tile_mean is None else tile_mean.data_ptr(), None if tile_std is None else tile_std.data_ptr(),
-                                                           ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_reinhard_transform_tiles")
+                ws = self._tile_scratch.get(int(self._lib.sx_reinhard_tiles_workspace_bytes(code, n, h, w)), self.device)
+                self._call("sx_reinhard_transform_tiles", images, out, code, n, h, w, mean, std, tile_mean, tile_std, ws, ws.numel())
         return (out, tile_mean, tile_std) if return_statistics else out
 
     def apply_statistics(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor) -> torch.Tensor:
         """Normalise with GIVEN source statistics, (1, 3) for the whole batch or (N, 3) per tile: one launch, no workspace."""
-        images = images.to(self.device)
-        self._check(images)
-        n, _, h, w = images.shape
-        if source_mean.dim() == 1:
-            source_mean = source_mean.unsqueeze(0)
-        if source_std.dim() == 1:
-            source_std = source_std.unsqueeze(0)
-        for name, t in (("source_mean", source_mean), ("source_std", source_std)):
-            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
-                raise ValueError(f"{name} must be (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
-        if source_mean.shape[0] != source_std.shape[0]:
-            raise ValueError(f"source_mean and source_std must have the same number of rows, got {source_mean.shape[0]} and {source_std.shape[0]}")
-        images = images.contiguous()
-        mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
-        if mean.numel() != 3 or std.numel() != 3:
-            raise ValueError("reference_mean / reference_std must have 3 elements")
-        src_mean, src_std = self._f32(source_mean), self._f32(source_std)
-        out = torch.empty_like(images)
-        if images.numel() == 0:
-            return out
-        with _native.on_device(self.device):
-            rc = self._lib.sx_reinhard_apply_stats(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, src_mean.data_ptr(), src_std.data_ptr(),
-                                                   int(src_mean.shape[0]), mean.data_ptr(), std.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_apply_stats")
-        return out
+        return self._apply_statistics(images, source_mean, source_std, reference_mean, reference_std, None)
 
     # ---- tissue masks (include/stainx_hip.h: sx_reinhard_stats_masked ...) --------------------------------
-    def _masked_workspace(self, n: int, h: int, w: int, code: int) -> torch.Tensor:
-        scratch = self.__dict__.get("_masked_scratch")
-        if scratch is None:
-            scratch = self.__dict__.setdefault("_masked_scratch", _native.Scratch())
-        return scratch.get(int(self._lib.sx_reinhard_masked_workspace_bytes(code, n, h, w)), self.device)
-
     def masked_statistics(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float, *, per_tile: bool):
         """LAB mean / unbiased standard deviation over TISSUE pixels -- ``mask`` (N, H, W) uint8, or None: the luminosity rule -- of every
         tile (``per_tile``: (N, 3) each) or pooled over the batch ((1, 3) each), and the tissue counts (int64).  Fewer than two tissue
         pixels: a row of NaN."""
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Reinhard")
         rows = n if per_tile else 1
         mean = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
         std = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
         counts = torch.zeros((rows,), dtype=torch.int64, device=self.device)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return mean.fill_(float("nan")), std.fill_(float("nan")), counts
         mask = _mask_bytes(mask, self.device)
         with _native.on_device(self.device):
-            ws = self._masked_workspace(n, h, w, _dtype_code(images))
-            rc = self._lib.sx_reinhard_stats_masked(images.data_ptr(), _dtype_code(images), n, h, w, None if mask is None else mask.data_ptr(), float(luminosity_threshold),
-                                                    int(per_tile), mean.data_ptr(), std.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_stats_masked")
+            ws = self._masked_scratch.get(int(self._lib.sx_reinhard_masked_workspace_bytes(code, n, h, w)), self.device)
+            self._call("sx_reinhard_stats_masked", images, code, n, h, w, mask, float(luminosity_threshold), int(per_tile), mean, std, counts, ws, ws.numel())
         return mean, std, counts
 
     def transform_masked(self, images: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float, *,
                          per_tile: bool, return_statistics: bool = False):
         """Tissue pixels normalised with the statistics of the tissue (per tile, or pooled over the batch), background pixels copied: two
         streaming launches.  With ``return_statistics`` also mean, std and the tissue counts."""
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
+        images, n, h, w, code = self._images(images, False, "Reinhard")
+        _reference_statistics(reference_mean, reference_std)
         mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
-        if mean.numel() != 3 or std.numel() != 3:
-            raise ValueError("reference_mean / reference_std must have 3 elements")
-        n, _, h, w = images.shape
         rows = n if per_tile else 1
         out = torch.empty_like(images)
         src_mean = src_std = counts = None
@@ -1622,62 +1283,37 @@ class ReinhardHIP(TorchHIPBackendBase):
             src_mean = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
             src_std = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
             counts = torch.zeros((rows,), dtype=torch.int64, device=self.device)
-        if images.numel() != 0:
+        if n * h * w != 0:
             mask = _mask_bytes(mask, self.device)
             with _native.on_device(self.device):
-                ws = self._masked_workspace(n, h, w, _dtype_code(images))
-                rc = self._lib.sx_reinhard_transform_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, mean.data_ptr(), std.data_ptr(),
-                                                            None if mask is None else mask.data_ptr(), float(luminosity_threshold), int(per_tile),
-                                                            None if src_mean is None else src_mean.data_ptr(), None if src_std is None else src_std.data_ptr(),
-                                                            None if counts is None else counts.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_reinhard_transform_masked")
+                ws = self._masked_scratch.get(int(self._lib.sx_reinhard_masked_workspace_bytes(code, n, h, w)), self.device)
+                self._call("sx_reinhard_transform_masked", images, out, code, n, h, w, mean, std, mask, float(luminosity_threshold), int(per_tile), src_mean, src_std, counts,
+                           ws, ws.numel())
         return (out, src_mean, src_std, counts) if return_statistics else out
 
     def apply_statistics_masked(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, reference_mean: torch.Tensor, reference_std: torch.Tensor,
                                 mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
         """``apply_statistics`` with a tissue mask: one launch; background pixels, and tiles whose row of statistics holds a NaN, are copied."""
-        images = images.to(self.device)
-        self._check(images)
-        n, _, h, w = images.shape
-        if source_mean.dim() == 1:
-            source_mean = source_mean.unsqueeze(0)
-        if source_std.dim() == 1:
-            source_std = source_std.unsqueeze(0)
-        for name, t in (("source_mean", source_mean), ("source_std", source_std)):
-            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
-                raise ValueError(f"{name} must be (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
-        if source_mean.shape[0] != source_std.shape[0]:
-            raise ValueError(f"source_mean and source_std must have the same number of rows, got {source_mean.shape[0]} and {source_std.shape[0]}")
-        images = images.contiguous()
+        return self._apply_statistics(images, source_mean, source_std, reference_mean, reference_std, (mask, luminosity_threshold))
+
+    def _apply_statistics(self, images, source_mean, source_std, reference_mean, reference_std, masking):
+        images, n, h, w, code = self._images(images, False, "Reinhard")
+        src_mean, src_std = _statistics_rows(source_mean, source_std, n, "source", "(1, 3)")
+        src_mean, src_std = self._f32(src_mean), self._f32(src_std)
+        _reference_statistics(reference_mean, reference_std)
         mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
-        if mean.numel() != 3 or std.numel() != 3:
-            raise ValueError("reference_mean / reference_std must have 3 elements")
-        src_mean, src_std = self._f32(source_mean), self._f32(source_std)
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
-        mask = _mask_bytes(mask, self.device)
         with _native.on_device(self.device):
-            rc = self._lib.sx_reinhard_apply_stats_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, src_mean.data_ptr(), src_std.data_ptr(),
-                                                          int(src_mean.shape[0]), mean.data_ptr(), std.data_ptr(), None if mask is None else mask.data_ptr(),
-                                                          float(luminosity_threshold), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_apply_stats_masked")
+            if masking is None:
+                self._call("sx_reinhard_apply_stats", images, out, code, n, h, w, src_mean, src_std, int(src_mean.shape[0]), mean, std)
+            else:
+                self._call("sx_reinhard_apply_stats_masked", images, out, code, n, h, w, src_mean, src_std, int(src_mean.shape[0]), mean, std, _mask_bytes(masking[0], self.device),
+                           float(masking[1]))
         return out
 
     # ---- a target per tile (include/stainx_hip.h: sx_reinhard_apply_targets ...) --------------------------
-    @staticmethod
-    def _rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str) -> tuple[torch.Tensor, torch.Tensor]:
-        if mean.dim() == 1:
-            mean = mean.unsqueeze(0)
-        if std.dim() == 1:
-            std = std.unsqueeze(0)
-        for name, t in ((f"{what}_mean", mean), (f"{what}_std", std)):
-            if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] not in (1, n):
-                raise ValueError(f"{name} must be (3,), (1, 3) or ({n}, 3) for {n} tiles, got shape {tuple(t.shape)}")
-        if mean.shape[0] != std.shape[0]:
-            raise ValueError(f"{what}_mean and {what}_std must have the same number of rows, got {mean.shape[0]} and {std.shape[0]}")
-        return mean, std
-
     def apply_targets(self, images: torch.Tensor, source_mean: torch.Tensor, source_std: torch.Tensor, target_mean: torch.Tensor, target_std: torch.Tensor) -> torch.Tensor:
         """``apply_statistics`` with a row of TARGET statistics per tile as well -- (1, 3) or (N, 3) each: one launch, no workspace.  A
         tile any of whose rows holds a NaN is copied bit for bit."""
@@ -1689,64 +1325,46 @@ class ReinhardHIP(TorchHIPBackendBase):
         return self._apply_targets(images, source_mean, source_std, target_mean, target_std, (mask, luminosity_threshold))
 
     def _apply_targets(self, images, source_mean, source_std, target_mean, target_std, masking):
-        images = images.to(self.device)
-        self._check(images)
-        n, _, h, w = images.shape
-        source_mean, source_std = self._rows(source_mean, source_std, n, "source")
-        target_mean, target_std = self._rows(target_mean, target_std, n, "target")
-        code = _dtype_code(images)
-        images = images.contiguous()
+        images, n, h, w, code = self._images(images, False, "Reinhard")
+        source_mean, source_std = _statistics_rows(source_mean, source_std, n, "source")
+        target_mean, target_std = _statistics_rows(target_mean, target_std, n, "target")
         sm, ss, tm, ts = self._f32(source_mean), self._f32(source_std), self._f32(target_mean), self._f32(target_std)
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
-        stream = _native.stream_ptr(self.device)
         with _native.on_device(self.device):
             if masking is None:
-                rc = self._lib.sx_reinhard_apply_targets(images.data_ptr(), out.data_ptr(), code, n, h, w, sm.data_ptr(), ss.data_ptr(), int(sm.shape[0]),
-                                                         tm.data_ptr(), ts.data_ptr(), int(tm.shape[0]), stream)
-                _native.check(rc, "sx_reinhard_apply_targets")
+                self._call("sx_reinhard_apply_targets", images, out, code, n, h, w, sm, ss, int(sm.shape[0]), tm, ts, int(tm.shape[0]))
             else:
-                mask = _mask_bytes(masking[0], self.device)
-                rc = self._lib.sx_reinhard_apply_targets_masked(images.data_ptr(), out.data_ptr(), code, n, h, w, sm.data_ptr(), ss.data_ptr(), int(sm.shape[0]),
-                                                                tm.data_ptr(), ts.data_ptr(), int(tm.shape[0]), None if mask is None else mask.data_ptr(),
-                                                                float(masking[1]), stream)
-                _native.check(rc, "sx_reinhard_apply_targets_masked")
+                self._call("sx_reinhard_apply_targets_masked", images, out, code, n, h, w, sm, ss, int(sm.shape[0]), tm, ts, int(tm.shape[0]), _mask_bytes(masking[0], self.device),
+                           float(masking[1]))
         return out
 
     # ---- batch statistics pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_sums(self, images: torch.Tensor) -> torch.Tensor:
         """6 fp64 values: per channel sum and sum of squares of (LAB - 128) over this rank's pixels."""
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
-        n, _, h, w = images.shape
+        images, n, h, w, code = self._images(images, False, "Reinhard")
         sums = torch.empty(6, dtype=torch.float64, device=self.device)
         with _native.on_device(self.device):
             ws = self._workspace(n, h, w)
-            rc = self._lib.sx_reinhard_sums(images.data_ptr(), _dtype_code(images), n, h, w, sums.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_sums")
+            self._call("sx_reinhard_sums", images, code, n, h, w, sums, ws, ws.numel())
         return sums
 
     def apply_with_sums(self, images: torch.Tensor, sums: torch.Tensor, n_total_pixels: int, reference_mean: torch.Tensor, reference_std: torch.Tensor) -> torch.Tensor:
-        images = images.to(self.device)
-        self._check(images)
-        images = images.contiguous()
+        images, n, h, w, code = self._images(images, False, "Reinhard")
         mean, std = self._f32(reference_mean).flatten(), self._f32(reference_std).flatten()
         sums = sums.to(self.device, torch.float64).contiguous()
-        n, _, h, w = images.shape
         out = torch.empty_like(images)
         with _native.on_device(self.device):
             ws = self._workspace(n, h, w)
-            rc = self._lib.sx_reinhard_apply(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, sums.data_ptr(), float(n_total_pixels),
-                                             mean.data_ptr(), std.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_reinhard_apply")
+            self._call("sx_reinhard_apply", images, out, code, n, h, w, sums, float(n_total_pixels), mean, std, ws, ws.numel())
         return out
 
 
 class HistogramMatchingHIP(TorchHIPBackendBase):
     """Histogram matching on the GPU (numerics of HistogramMatchingTorch, torch_backend.py:134-301)."""
+
+    _ref_cache: tuple | None = None      # (a class default: a test of the cache builds the object without its device checks)
 
     def __init__(self, device: str | torch.device | None = None, channel_axis: int = 1, diag: bool = False):
         super().__init__(device)
@@ -1757,12 +1375,13 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         # the workspace is zero-filled when it is made and every library call leaves it zeroed again: the sx_hm_*_ready entry
         # points, which have no clearing launch in front of the histogram pass (include/stainx_hip.h)
         self._scratch = _native.Scratch(zeroed=True)
+        # workspaces of their own (their calls clear what they need): the zeroed scratch of the pooled calls is not touched
+        self._tile_scratch = _native.Scratch()
+        self._masked_scratch = _native.Scratch()
         self._status_offset = int(self._lib.sx_hm_workspace_status_offset())
 
-    def _check_ready_call(self, rc: int, what: str) -> None:
-        if rc != 0:
-            self._scratch.drop(self.device)      # (a failed call may have left counters behind)
-        _native.check(rc, what)
+    def _drop_workspace(self) -> None:
+        self._scratch.drop(self.device)      # (a failed call may have left counters behind)
 
     def workspace_status(self) -> int:
         """Bit 0: a call found the workspace not in its ready state (synchronises; for tests and diagnosis)."""
@@ -1772,26 +1391,23 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
     def _channels_last(self, images: torch.Tensor) -> bool:
         return self.channel_axis == -1 or (self.channel_axis == 3 and images.ndim == 4)      # torch_backend.py:182
 
-    def _dims(self, images: torch.Tensor) -> tuple[int, int, int, bool]:
-        if images.dim() != 4:
-            raise ValueError(f"HistogramMatching expects 4D images, got shape {tuple(images.shape)}")
-        last = self._channels_last(images)
-        chans = images.shape[-1] if last else images.shape[1]
-        if chans != 3:
-            raise ValueError(f"HistogramMatching expects 3 channels, got {chans} with shape {tuple(images.shape)}")
-        n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if last else (images.shape[0], images.shape[2], images.shape[3])
-        return n, h, w, last
+    def _workspace(self, n: int, h: int, w: int) -> torch.Tensor:
+        return self._scratch.get(self._lib.sx_hm_workspace_bytes(n, h, w), self.device)
+
+    def _tiles_workspace(self, n: int, h: int, w: int) -> torch.Tensor:
+        return self._tile_scratch.get(int(self._lib.sx_hm_tiles_workspace_bytes(n, h, w)), self.device)
+
+    def _masked_workspace(self, n: int, h: int, w: int) -> torch.Tensor:
+        return self._masked_scratch.get(int(self._lib.sx_hm_masked_workspace_bytes(n, h, w)), self.device)
 
     def compute_reference_histograms(self, images: torch.Tensor) -> list[torch.Tensor]:
         """Three normalised 256-bin histograms, what ``transform`` receives (torch_backend.py:139-160)."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         hists = torch.empty((3, 256), dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_hm_workspace_bytes(n, h, w), self.device)
-            rc = self._lib.sx_hm_fit_ready(images.data_ptr(), _dtype_code(images), n, h, w, int(last), hists.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _native.stream_ptr(self.device))
-        self._check_ready_call(rc, "sx_hm_fit_ready")
+            ws = self._workspace(n, h, w)
+            self._call("sx_hm_fit_ready", images, code, n, h, w, last, hists, ws, ws.numel(), on_failure=self._drop_workspace)
         return [hists[c] for c in range(3)]
 
     def _stack_reference(self, reference_histogram, chans: int) -> torch.Tensor:
@@ -1806,7 +1422,7 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         if not cacheable:
             return self._stack_reference_uncached(reference_histogram, chans)
         stamp = tuple((p.data_ptr(), tuple(p.shape), p._version) for p in parts)
-        cached = getattr(self, "_ref_cache", None)
+        cached = self._ref_cache
         if (cached is not None and cached[0] == chans and len(cached[1]) == len(parts)
                 and all(p is q for p, q in zip(parts, cached[1])) and cached[2] == stamp):
             return cached[3]
@@ -1835,17 +1451,15 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         return ref.to(torch.float32).contiguous()
 
     def transform(self, images: torch.Tensor, reference_histogram) -> torch.Tensor:
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         ref = self._stack_reference(reference_histogram, 3)
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_hm_workspace_bytes(n, h, w), self.device)
-            rc = self._lib.sx_hm_transform_ready(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), ref.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        self._check_ready_call(rc, "sx_hm_transform_ready")
+            ws = self._workspace(n, h, w)
+            self._call("sx_hm_transform_ready", images, out, code, n, h, w, last, ref, ws, ws.numel(), on_failure=self._drop_workspace)
         self.last_workspace = ws
         return out
 
@@ -1853,21 +1467,15 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
     def transform_tiles(self, images: torch.Tensor, reference_histogram) -> torch.Tensor:
         """Every tile matched to the reference with its OWN histogram: three launches for the batch, tile t's bits those of
         ``transform(images[t:t+1])``."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         ref = self._stack_reference(reference_histogram, 3)
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
         with _native.on_device(self.device):
-            # a workspace of its own (the call clears what it needs): the zeroed scratch of the pooled calls is not touched
-            scratch = self.__dict__.get("_tile_scratch")
-            if scratch is None:
-                scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
-            ws = scratch.get(int(self._lib.sx_hm_tiles_workspace_bytes(n, h, w)), self.device)
-            rc = self._lib.sx_hm_transform_tiles(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), ref.data_ptr(), None, None,
-                                                 ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_transform_tiles")
+            ws = self._tiles_workspace(n, h, w)
+            self._call("sx_hm_transform_tiles", images, out, code, n, h, w, last, ref, None, None, ws, ws.numel())
         self._last_tiles = (ws, int(n), int(self._lib.sx_hm_workspace_bytes(n, h, w)))
         return out
 
@@ -1880,24 +1488,16 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         return {"counts": counts, "lut": lut}
 
     # ---- tissue masks (include/stainx_hip.h: sx_hm_fit_masked, sx_hm_transform_masked) ----------------------
-    def _masked_workspace(self, n: int, h: int, w: int) -> torch.Tensor:
-        scratch = self.__dict__.get("_masked_scratch")
-        if scratch is None:
-            scratch = self.__dict__.setdefault("_masked_scratch", _native.Scratch())
-        return scratch.get(int(self._lib.sx_hm_masked_workspace_bytes(n, h, w)), self.device)
-
     def compute_reference_histograms_masked(self, images: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> list[torch.Tensor]:
         """``compute_reference_histograms`` over TISSUE pixels only (``mask`` (N, H, W) uint8, or None: the luminosity rule)."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         hists = torch.empty((3, 256), dtype=torch.float32, device=self.device)
         count = torch.zeros((1,), dtype=torch.int64, device=self.device)
         mask = _mask_bytes(mask, self.device)
         with _native.on_device(self.device):
             ws = self._masked_workspace(n, h, w)
-            rc = self._lib.sx_hm_fit_masked(images.data_ptr(), _dtype_code(images), n, h, w, int(last), None if mask is None else mask.data_ptr(), float(luminosity_threshold),
-                                            hists.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_fit_masked")
+            self._call("sx_hm_fit_masked", images, code, n, h, w, last, mask, float(luminosity_threshold), hists, count, ws, ws.numel())
         self.last_workspace = ws
         self.last_tissue_count = count
         return [hists[c] for c in range(3)]
@@ -1907,24 +1507,21 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         """Tissue pixels matched with the histogram(s) of the tissue -- one per tile, or one pooled over the batch --, background pixels
         copied with the bits of the input.  With ``return_tables`` also a dict: ``counts`` (sets, 3, 256) int32 histograms as counted,
         ``lut`` (sets, 3, 256) float LUTs, ``tissue`` (sets,) int64 tissue pixels (sets = N per tile, 1 pooled)."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         ref = self._stack_reference(reference_histogram, 3)
         out = torch.empty_like(images)
         sets = n if per_tile else 1
-        tables = None
+        tables = {"counts": None, "lut": None, "tissue": None}
         if return_tables:
             tables = {"counts": torch.zeros((sets, 3, 256), dtype=torch.int32, device=self.device), "lut": torch.zeros((sets, 3, 256), dtype=torch.float32, device=self.device),
                       "tissue": torch.zeros((sets,), dtype=torch.int64, device=self.device)}
-        if images.numel() != 0:
+        if n * h * w != 0:
             mask = _mask_bytes(mask, self.device)
             with _native.on_device(self.device):
                 ws = self._masked_workspace(n, h, w)
-                rc = self._lib.sx_hm_transform_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), ref.data_ptr(),
-                                                      None if mask is None else mask.data_ptr(), float(luminosity_threshold), int(per_tile),
-                                                      None if tables is None else tables["counts"].data_ptr(), None if tables is None else tables["lut"].data_ptr(),
-                                                      None if tables is None else tables["tissue"].data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-            _native.check(rc, "sx_hm_transform_masked")
+                self._call("sx_hm_transform_masked", images, out, code, n, h, w, last, ref, mask, float(luminosity_threshold), int(per_tile), tables["counts"], tables["lut"],
+                           tables["tissue"], ws, ws.numel())
             self.last_workspace = ws
         return (out, tables) if return_tables else out
 
@@ -1933,27 +1530,21 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
                             luminosity_threshold: float = 0.8) -> tuple[torch.Tensor, torch.Tensor]:
         """The histogram pass alone: ``counts`` (sets, 3, 256) int64 and ``pixels`` (sets,) int64 on the device, sets = N per tile or 1
         pooled over the batch.  ``masked``: tissue pixels only (``mask`` (N, H, W) uint8, or None: the luminosity rule)."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         sets = n if per_tile else 1
         counts = torch.zeros((sets, 3, 256), dtype=torch.int64, device=self.device)
         pixels = torch.zeros((sets,), dtype=torch.int64, device=self.device)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return counts, pixels
         mask = _mask_bytes(mask, self.device) if masked else None
         with _native.on_device(self.device):
             if masked:
                 ws = self._masked_workspace(n, h, w)
-                rc = self._lib.sx_hm_estimate_masked(images.data_ptr(), _dtype_code(images), n, h, w, int(last), int(per_tile), None if mask is None else mask.data_ptr(),
-                                                     float(luminosity_threshold), counts.data_ptr(), pixels.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
+                self._call("sx_hm_estimate_masked", images, code, n, h, w, last, int(per_tile), mask, float(luminosity_threshold), counts, pixels, ws, ws.numel())
             else:
-                scratch = self.__dict__.get("_tile_scratch")
-                if scratch is None:
-                    scratch = self.__dict__.setdefault("_tile_scratch", _native.Scratch())
-                ws = scratch.get(int(self._lib.sx_hm_tiles_workspace_bytes(n, h, w)), self.device)
-                rc = self._lib.sx_hm_estimate(images.data_ptr(), _dtype_code(images), n, h, w, int(last), int(per_tile), counts.data_ptr(), pixels.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_estimate_masked" if masked else "sx_hm_estimate")
+                ws = self._tiles_workspace(n, h, w)
+                self._call("sx_hm_estimate", images, code, n, h, w, last, int(per_tile), counts, pixels, ws, ws.numel())
         self.last_workspace = ws
         return counts, pixels
 
@@ -1969,8 +1560,7 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
         ref = self._stack_reference(reference_histogram, 3)
         lut = torch.empty(tuple(counts.shape), dtype=torch.float32, device=self.device)
         with _native.on_device(self.device):
-            rc = self._lib.sx_hm_tables(counts.data_ptr(), pixels.data_ptr(), int(counts.shape[0]), ref.data_ptr(), lut.data_ptr(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_tables")
+            self._call("sx_hm_tables", counts, pixels, int(counts.shape[0]), ref, lut)
         return lut
 
     def _given_tables(self, tables: torch.Tensor, n: int) -> torch.Tensor:
@@ -1984,56 +1574,45 @@ class HistogramMatchingHIP(TorchHIPBackendBase):
 
     def apply_tables(self, images: torch.Tensor, tables: torch.Tensor) -> torch.Tensor:
         """Normalise with GIVEN float lookup tables, (1, 3, 256) for the whole batch or (N, 3, 256) per tile: one launch, no workspace."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
-        tables = self._given_tables(tables, n)
-        out = torch.empty_like(images)
-        if images.numel() == 0:
-            return out
-        with _native.on_device(self.device):
-            rc = self._lib.sx_hm_apply_tables(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), tables.data_ptr(), int(tables.shape[0]),
-                                              _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_apply_tables")
-        return out
+        return self._apply_tables(images, tables, None)
 
     def apply_tables_masked(self, images: torch.Tensor, tables: torch.Tensor, mask: torch.Tensor | None, luminosity_threshold: float) -> torch.Tensor:
         """``apply_tables`` with a tissue mask: one launch; background pixels are copied with the bits of the input."""
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        return self._apply_tables(images, tables, (mask, luminosity_threshold))
+
+    def _apply_tables(self, images, tables, masking):
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         tables = self._given_tables(tables, n)
         out = torch.empty_like(images)
-        if images.numel() == 0:
+        if n * h * w == 0:
             return out
-        mask = _mask_bytes(mask, self.device)
         with _native.on_device(self.device):
-            rc = self._lib.sx_hm_apply_tables_masked(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), tables.data_ptr(), int(tables.shape[0]),
-                                                     None if mask is None else mask.data_ptr(), float(luminosity_threshold), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_apply_tables_masked")
+            if masking is None:
+                self._call("sx_hm_apply_tables", images, out, code, n, h, w, last, tables, int(tables.shape[0]))
+            else:
+                self._call("sx_hm_apply_tables_masked", images, out, code, n, h, w, last, tables, int(tables.shape[0]), _mask_bytes(masking[0], self.device), float(masking[1]))
         return out
 
     # ---- source histogram pooled across ranks (see stainx_amd/distributed.py) --------------------------
     def local_counts(self, images: torch.Tensor) -> torch.Tensor:
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         counts = torch.empty((3, 256), dtype=torch.int64, device=self.device)
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_hm_workspace_bytes(n, h, w), self.device)
-            rc = self._lib.sx_hm_counts_ready(images.data_ptr(), _dtype_code(images), n, h, w, int(last), counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              _native.stream_ptr(self.device))
-        self._check_ready_call(rc, "sx_hm_counts_ready")
+            ws = self._workspace(n, h, w)
+            self._call("sx_hm_counts_ready", images, code, n, h, w, last, counts, ws, ws.numel(), on_failure=self._drop_workspace)
         return counts
 
     def apply_with_counts(self, images: torch.Tensor, counts: torch.Tensor, n_total_pixels: int, reference_histogram) -> torch.Tensor:
-        images = images.to(self.device).contiguous()
-        n, h, w, last = self._dims(images)
+        last = int(self._channels_last(images))
+        images, n, h, w, code = self._images(images, last, "HistogramMatching")
         ref = self._stack_reference(reference_histogram, 3)
         counts = counts.to(self.device, torch.int64).contiguous()
         out = torch.empty_like(images)
         with _native.on_device(self.device):
-            ws = self._scratch.get(self._lib.sx_hm_workspace_bytes(n, h, w), self.device)
-            rc = self._lib.sx_hm_apply(images.data_ptr(), out.data_ptr(), _dtype_code(images), n, h, w, int(last), counts.data_ptr(), float(n_total_pixels),
-                                       ref.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_ptr(self.device))
-        _native.check(rc, "sx_hm_apply")
+            ws = self._workspace(n, h, w)
+            self._call("sx_hm_apply", images, out, code, n, h, w, last, counts, float(n_total_pixels), ref, ws, ws.numel())
         self.last_workspace = ws
         return out
 

@@ -99,3 +99,24 @@ def test_degenerate_batches(be, dev):
     x = synth.he_batch(48, 512, 512, seed0=5500).to(dev)
     x[:, 1] = 255      # a constant channel beside two ordinary ones
     assert torch.equal(be.transform(x, ref), _two_kernels(be, x, ref))
+
+
+def test_a_refused_diagnostic_call_reports_the_diagnostic_librarys_error(dev):
+    """The status of a call is read against the library that was called: an object on the diagnostic build reports that build's
+    ``sx_last_error_string``, not the product library's (which holds another, older message here).  The call is refused by its
+    arguments before anything is enqueued (include/stainx_hip.h: sx_hm_apply, n_total_pixels >= 1)."""
+    from stainx_amd import _native
+    from stainx_amd.backends.torch_hip_backend import HistogramMatchingHIP
+
+    be = HistogramMatchingHIP(dev, diag=True)
+    product = _native.require()
+    assert be._lib is not product
+    assert product.sx_hm_tables(None, None, 0, None, None, None) == _native.SX_ERR_BAD_ARG      # the product library's last error: a null pointer
+    stale = _native.last_error(product)
+    x = synth.he_batch(1, 8, 8, seed0=5400).to(dev)
+    counts = torch.ones((3, 256), dtype=torch.int64, device=dev)
+    with pytest.raises(RuntimeError) as caught:
+        be.apply_with_counts(x, counts, 0, _ref_hist(dev))
+    own = _native.last_error(be._lib)
+    assert own == "n_total_pixels must be >= 1" and own != stale and _native.last_error(product) == stale
+    assert str(caught.value) == f"sx_hm_apply failed (status {_native.SX_ERR_BAD_ARG}): {own}"
