@@ -386,6 +386,37 @@ int sx_deconv_moments_masked(const void* images_dev, int dtype, int64_t n_tiles,
                              const float* basis_dev, int64_t n_bases, int per_tile, long long* out_dev,
                              const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- HSV colour jitter: per-tile hue, saturation and value (Tellez et al.'s HSV-light / HSV-strong; RandStainNA's third space) ----
+ * An extension: no statistics and no estimate, one row of five floats per tile.  All arithmetic is float32 on 0-255 levels; r, g, b are
+ * the input levels (uint8: the byte; floats: 255 x) clamped to [0, 255]:
+ *   M = max, m = min, C = M - m;   s = C / M (0 where M <= 0)
+ *   h6 in [0, 6): 0 where C == 0; (g - b) / C, plus 6 if negative, where M == r; 2 + (b - r) / C where M == g; 4 + (r - g) / C otherwise
+ *   h6' = h6 + 6 dh, reduced into [0, 6) by x - 6 floor(x / 6);   s' = clamp(a_s s + b_s, 0, 1);   V' = 255 clamp(a_v M / 255 + b_v, 0, 1)
+ *   for n = 5, 3, 1 (r, g, b):  k = h6' + n, minus 6 where k >= 6;  t = clamp(min(k, 4 - k), 0, 1);  out = V' - V' s' t
+ *   rows_dev   n_rows x 5 floats (dh, a_s, b_s, a_v, b_v), dh in turns; n_rows is 1 (one row for the batch) or n_tiles (row t serves
+ *              tile t).  (0, 1, 0, 1, 0) is the identity.
+ * Output: a float element gets the level by sx_macenko_transform's rules (SX_MACENKO_NORMALIZE_0_1 fuses / 255).  An 8-bit level -- uint8
+ * output, and the level a uint8 tile's result is quantised to before SX_MACENKO_OUT_BF16 / _OUT_F16 / the / 255 -- is ROUNDED TO NEAREST,
+ * unlike the stain calls, which truncate: with rounding the identity row returns every one of the 2^24 uint8 colours exactly (the
+ * float32 round trip is off by up to 1.8e-4 of a level, which truncation turns into a level).
+ * Copies: a pixel with a NaN in any channel, and every pixel of a tile whose row has a non-finite member (NaN, Inf: "leave this tile"),
+ * are copied by sx_macenko_transform_masked's background rule -- the input level through the clamp, the cast and / 255 (uint8 in, uint8
+ * out is byte-identical there).
+ * Each call is ONE kernel launch on `stream`: nothing else enqueued, no workspace, no host synchronisation, capturable.  Rows and masks
+ * are DEVICE memory read by the kernel (a captured graph replayed after new values were written into the same buffers uses the new
+ * values).  Flags: SX_MACENKO_NORMALIZE_0_1, SX_MACENKO_CHANNELS_LAST, SX_MACENKO_OUT_BF16 / SX_MACENKO_OUT_F16 (uint8 input, one of the
+ * two) with their meaning in sx_deconv_apply, SX_MACENKO_CLASSIC (a no-op); any other bit is SX_ERR_BAD_ARG.  All argument errors -- a
+ * NULL pointer, a non-positive size, n_rows not 1 or n_tiles, bad flags, SX_MACENKO_CHANNELS_LAST on the masked call -- are
+ * SX_ERR_BAD_ARG with a message, an unknown dtype is SX_ERR_DTYPE, before anything is enqueued. */
+int sx_hsv_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                 const float* rows_dev, int64_t n_rows, unsigned flags, void* stream);
+/* sx_hsv_apply_masked: the same under an explicit mask (N, H, W), one byte per pixel, non-zero = in (what sx_tissue_mask writes); planar
+ * tiles only.  A masked-out pixel is copied by the background rule; values under masked-out pixels never matter (every use is a select).
+ * The mask is read in packs as wide as the pixel packs where the image pointers, the tile size AND the mask pointer allow it.  All ones:
+ * sx_hsv_apply's bits. */
+int sx_hsv_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                        const float* rows_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

@@ -81,6 +81,9 @@ SIGNATURES = {
     # statistics of the stain space: integer sums, sums of squares and counted pixels of the three concentrations -- a memset and one launch
     "sx_deconv_moments": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _uint, _vp]),
     "sx_deconv_moments_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _vp, _uint, _vp]),
+    # HSV colour jitter: rows of (dh, a_s, b_s, a_v, b_v) per tile in device memory, one launch
+    "sx_hsv_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
+    "sx_hsv_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,6 +58,8 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
+        if family == "HSV":
+            raise ValueError(f"HSV {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
         if len(shape) != 4:
@@ -122,6 +124,16 @@ def _basis_rows(basis: torch.Tensor, n: int, what: str) -> int:
     if len(shape) == 3 and shape[1:] == (3, 3) and shape[0] in (1, n):
         return shape[0]
     raise ValueError(f"{what} must have shape (3, 3), (1, 3, 3) or (N, 3, 3) = ({n}, 3, 3), got {shape}")
+
+
+def _hsv_rows(rows: torch.Tensor, n: int) -> int:
+    """Rows of an HSV jitter, (5,), (1, 5) or (N, 5): the number of rows, 1 or N."""
+    shape = tuple(getattr(rows, "shape", ()))
+    if isinstance(rows, torch.Tensor) and shape == (5,):
+        return 1
+    if isinstance(rows, torch.Tensor) and len(shape) == 2 and shape[1] == 5 and shape[0] in (1, n):
+        return shape[0]
+    raise ValueError(f"rows must be a tensor of shape (5,), (1, 5) or (N, 5) = ({n}, 5) holding (dh, a_s, b_s, a_v, b_v), got {shape}")
 
 
 def _statistics_rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str, accepted: str = "(3,), (1, 3)") -> tuple[torch.Tensor, torch.Tensor]:
@@ -1159,6 +1171,33 @@ class DeconvHIP(TorchHIPBackendBase):
         launch, no map.  ``masking`` as in ``apply``."""
         out = self._sums("moments", images, basis, (), self.MOMENT_WORDS, per_tile, channels_last, masking)
         return out[:, 0:3], out[:, 3:6], out[:, 6]
+
+
+class HsvHIP(TorchHIPBackendBase):
+    """HSV colour jitter (include/stainx_hip.h: sx_hsv_apply): one kernel launch per call, no estimate, no workspace, no host
+    synchronisation.  Rows and masks are read on the device: a captured call replayed after new rows are copied into the same tensor
+    uses the new rows."""
+
+    def apply(self, images: torch.Tensor, rows: torch.Tensor, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False,
+              masking: tuple | None = None) -> torch.Tensor:
+        """``rows``: (5,), (1, 5) or (N, 5) floats ``(dh, a_s, b_s, a_v, b_v)``; a row with a non-finite member leaves its tile as it
+        is.  ``masking``: None, or ``(explicit mask or None, luminosity threshold)`` -- the masked call (planar tiles only); the rule's
+        mask is an ``sx_tissue_mask`` launch in front."""
+        if masking is not None and channels_last:
+            raise ValueError("a masked HSV jitter takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "HSV", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _hsv_rows(rows, n)
+        r = self._f32(rows)
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n * h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            if masking is None:
+                self._call("sx_hsv_apply", images, out, code, n, h, w, r, n_rows, flags)
+            else:
+                self._call("sx_hsv_apply_masked", images, out, code, n, h, w, r, n_rows, self._mask_for(images, *masking), flags)
+        return out
 
 
 class ReinhardHIP(TorchHIPBackendBase):

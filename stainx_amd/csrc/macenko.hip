@@ -5227,5 +5227,8 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 // Three-stain colour deconvolution with a given basis (sx_deconv_*): kernels, launchers and entry points, on the helpers above.
 #include "deconv.hpp"
 
+// HSV colour jitter, per-tile hue / saturation / value rows (sx_hsv_apply, sx_hsv_apply_masked): one streaming kernel on the same helpers.
+#include "hsv.hpp"
+
 // Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
 #include "vahadane.hpp"
