@@ -783,6 +783,47 @@ int sx_level_histogram(const uint8_t* levels_dev, int64_t n_tiles, int64_t heigh
 int sx_level_mask_tiles(const uint8_t* levels_dev, int64_t n_tiles, int64_t height, int64_t width, const int32_t* tile_thresholds_dev,
                         uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
 
+/* ---- Focus measurement: grey maps, Laplacian variance and Tenengrad as integer sums, cell grids as pixel masks ----
+ * The focus filter that HistoQC-, CLAM- and tiatoolbox-style pipelines run between "find the tissue" and "estimate the stain".  The
+ * score is a ratio of integer sums, so the sums are the result: exact, independent of the order of adding, and poolable over batches,
+ * slides and ranks.  images_dev, dtype, channels_last as sx_tissue_mask; NULL pointers and non-positive sizes are SX_ERR_BAD_ARG, an
+ * unknown dtype SX_ERR_DTYPE; a refused call writes nothing.
+ *
+ * The grey level of a pixel with 8-bit levels r, g, b (the level rule of the saturation section above):
+ *   Y = (4899 r + 9617 g + 1868 b + 8192) >> 14, in 0..255 (the weights sum to 16384): the fixed-point rule of an 8-bit RGB -> grey
+ *   conversion.  A pixel with a NaN in any channel has Y = 0.
+ * The stencils on Y, per tile, in int32, the border reflected without repeating the edge (-1 -> 1, H -> H - 2; an axis of length 1 maps
+ *   to 0: OpenCV's BORDER_REFLECT_101, scipy's mode="mirror", numpy's pad mode "reflect"); tiles never see each other:
+ *   L = Y[y-1,x] + Y[y+1,x] + Y[y,x-1] + Y[y,x+1] - 4 Y[y,x]  (cv2.Laplacian with ksize = 1), |L| <= 1020;
+ *   Gx, Gy the 3 x 3 Sobel responses ([1 2 1] smoothing, [-1 0 1] derivative), T = Gx^2 + Gy^2 <= 2 080 800.
+ * sx_grey_map: levels_out_dev[pixel] = Y, n_tiles x height x width bytes, one streaming launch.  It replaces a float RGB -> grey
+ *   conversion in torch or cv2.cvtColor on the CPU; sx_median_filter_u8, sx_level_histogram and sx_level_mask_tiles take its output.
+ * sx_focus_statistics / sx_focus_statistics_masked: statistics_out_dev = four planes of int64 words, in this order: pixels, sum L
+ *   (signed), sum L^2, sum T; a plane holds one word per cell, n_tiles x grid_h x grid_w.  It replaces cv2.Laplacian(gray,
+ *   CV_64F).var() per tile on the CPU, or a float conv2d and var() in torch with their temporaries.
+ *   block_h, block_w   the cell: 0, 0 is the whole tile (grid 1 x 1); otherwise each side is 8, 16, 32, 64 or a multiple of 64 and the
+ *                      grid is ceil(height / block_h) x ceil(width / block_w), edge cells partial.  Anything else is SX_ERR_BAD_ARG.
+ *   pooled             != 0: one cell for the whole batch (each plane one word); with block 0, 0 only, else SX_ERR_BAD_ARG.
+ *   mask_dev           (the masked twin) n_tiles x height x width bytes: a pixel enters its cell iff its byte is non-zero; neighbours
+ *                      are read whatever their bytes say.  NULL is SX_ERR_BAD_ARG.  Without a mask every pixel enters.
+ *   One launch that reads the tile once and writes nothing but the words.  Cells with both sides <= 64 are written with plain
+ *   stores; larger cells (the whole tile, the batch) take 64-bit integer adds into words cleared first: a memset, or a clearing
+ *   launch while the stream is being captured.  No floating-point atomics, no workspace, no synchronisation.
+ * sx_cells_mask: mask_out_dev[tile][y][x] = 1 iff cells_dev[tile][y / block_h][x / block_w] != 0 and (mask_dev given) the pixel's
+ *   mask byte != 0, else 0; tile_counts_out_dev the set pixels per tile (n_tiles uint64).  It replaces np.repeat / F.interpolate of a
+ *   cell grid and the AND with a tissue mask.  cells_dev is n_tiles x grid_h x grid_w bytes, the grid as above (block sides as
+ *   above, no 0); mask_dev may be NULL; mask_out_dev, tile_counts_out_dev: either may be NULL, not both.  One streaming launch and
+ *   the clear of the counts. */
+int sx_grey_map(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                uint8_t* levels_out_dev, void* stream);
+int sx_focus_statistics(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                        int64_t block_h, int64_t block_w, int pooled, long long* statistics_out_dev, void* stream);
+int sx_focus_statistics_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last,
+                               int64_t block_h, int64_t block_w, int pooled, const unsigned char* mask_dev,
+                               long long* statistics_out_dev, void* stream);
+int sx_cells_mask(const uint8_t* cells_dev, int64_t n_tiles, int64_t height, int64_t width, int64_t block_h, int64_t block_w,
+                  const unsigned char* mask_dev, uint8_t* mask_out_dev, unsigned long long* tile_counts_out_dev, void* stream);
+
 /* Reinhard.  per_tile != 0: every tile its own statistics (N rows, a tile's result does not depend on its neighbours); per_tile == 0: one
  * set pooled over the tissue of the whole batch (one row).  Workspace: sx_reinhard_masked_workspace_bytes(); any contents are accepted
  * and a workspace that was READY (sx_reinhard_transform_ready) is left ready, so the calls may alternate with that one and with

@@ -144,6 +144,11 @@ SIGNATURES = {
     "sx_median_filter_u8": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp]),
     "sx_level_histogram": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp]),
     "sx_level_mask_tiles": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    # focus measurement: grey maps, the integer sums of the Laplacian and the Sobel gradient per tile, cell or batch, cell grids as pixel masks
+    "sx_grey_map": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp]),
+    "sx_focus_statistics": (_int, [_vp, _int, _i64, _i64, _i64, _int, _i64, _i64, _int, _vp, _vp]),
+    "sx_focus_statistics_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _i64, _i64, _int, _vp, _vp, _vp]),
+    "sx_cells_mask": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sx_reinhard_masked_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "sx_reinhard_stats_masked": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sx_reinhard_transform_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _c.c_double, _int, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -335,6 +335,47 @@ def saturation_map_native(images: torch.Tensor, channels_last: bool) -> torch.Te
     return out
 
 
+def grey_map_native(images: torch.Tensor, channels_last: bool) -> torch.Tensor:
+    """``stainx_amd.grey_map`` behind its checks: (N, H, W) uint8 grey levels on the device (include/stainx_hip.h: sx_grey_map)."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images, n, h, w, code = base._images(images, channels_last, None)
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=base.device)
+    if n * h * w != 0:
+        with _native.on_device(base.device):
+            base._call("sx_grey_map", images, code, n, h, w, int(channels_last), out)
+    return out
+
+
+def focus_statistics_native(images: torch.Tensor, block: tuple[int, int] | None, mask: torch.Tensor | None, pooled: bool, channels_last: bool) -> torch.Tensor:
+    """``stainx_amd.focus_statistics`` behind its checks: (4, N, gh, gw) int64 -- pixels, sum L, sum L^2, sum T -- on the device, (4, 1, 1, 1) pooled
+    (include/stainx_hip.h: sx_focus_statistics, sx_focus_statistics_masked).  ``mask``: None or an explicit (N, H, W) uint8 / bool tensor."""
+    base = TorchHIPBackendBase(images.device if images.device.type == "cuda" else None)
+    images, n, h, w, code = base._images(images, channels_last, None)
+    bh, bw = block if block is not None else (0, 0)
+    cells = (1, 1, 1) if pooled else (n, -(-h // bh) if bh else 1, -(-w // bw) if bw else 1)
+    if n * h * w == 0:
+        return torch.zeros((4, *cells), dtype=torch.int64, device=base.device)
+    out = torch.empty((4, *cells), dtype=torch.int64, device=base.device)      # (the library clears what it adds into)
+    with _native.on_device(base.device):
+        if mask is None:
+            base._call("sx_focus_statistics", images, code, n, h, w, int(channels_last), bh, bw, int(pooled), out)
+        else:
+            base._call("sx_focus_statistics_masked", images, code, n, h, w, int(channels_last), bh, bw, int(pooled), _explicit_mask(mask, n, h, w, base.device), out)
+    return out
+
+
+def cells_mask_native(cells: torch.Tensor, height: int, width: int, block: tuple[int, int], mask: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``stainx_amd.cells_mask`` behind its checks: (N, H, W) uint8 mask, 1 / 0, and (N,) int64 set pixels per tile (sx_cells_mask)."""
+    base, src, n, _, _ = _for_levels(cells)
+    out = torch.empty((n, height, width), dtype=torch.uint8, device=base.device)
+    counts = torch.zeros((n,), dtype=torch.int64, device=base.device) if n * height * width == 0 else torch.empty((n,), dtype=torch.int64, device=base.device)
+    if n * height * width != 0:
+        given = None if mask is None else _explicit_mask(mask, n, height, width, base.device)
+        with _native.on_device(base.device):
+            base._call("sx_cells_mask", src, n, height, width, int(block[0]), int(block[1]), given, out, counts)
+    return out, counts
+
+
 def median_filter_native(levels: torch.Tensor, size: int) -> torch.Tensor:
     """``stainx_amd.median_filter`` behind its checks: (N, H, W) uint8 medians of the size x size windows (sx_median_filter_u8)."""
     base, src, n, h, w = _for_levels(levels)

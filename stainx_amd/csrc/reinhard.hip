@@ -1056,5 +1056,8 @@ extern "C" int sx_reinhard_apply_targets_masked(const void* images, void* out, i
 // ---- saturation-channel tissue detection: saturation maps, the median filter, level histograms and level thresholds ------------------------
 #include "saturation.hpp"
 
+// ---- focus measurement: grey maps, the integer sums of the Laplacian and the Sobel gradient per tile, cell or batch, cell grids as masks -------
+#include "focus.hpp"
+
 // ---- luminosity standardisation: the exact percentile of the luminance, the one-launch L* map ------------------------------------------------
 #include "luminosity.hpp"
