@@ -15,7 +15,7 @@ from typing import Any
 import torch
 import torch.nn as nn
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 from stainx_amd.normalizers import Macenko
 
 
@@ -46,9 +46,7 @@ class MacenkoAugment(nn.Module):
         if reference is not None and normalizer is not None:
             raise ValueError("pass either reference= or normalizer=, not both")
         self.sigma1, self.sigma2 = sigma1, sigma2
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise ValueError(f"MacenkoAugment runs on a CUDA (ROCm) device, got {self.device}")
+        self.device = fe.cuda_only(device, "MacenkoAugment")
         self.normalize_to_0_1 = bool(normalize_to_0_1)
         self.generator = generator
         self._engines: dict[torch.device, Any] = {}
@@ -58,8 +56,8 @@ class MacenkoAugment(nn.Module):
             if not getattr(normalizer, "_is_fitted", False):
                 raise ValueError("normalizer must be fitted (call fit() first)")
         elif reference is not None:
-            ref = self._batch(reference)
-            target = self._target_device(ref)
+            ref = fe.image_batch(reference, False, "MacenkoAugment")[0]
+            target = fe.run_device(self.device, ref.device, "MacenkoAugment", fe.ON_TENSOR)
             normalizer = Macenko(device=target, backend="torch_hip").fit(ref.to(target))
         self.normalizer = normalizer
         # (the source's rows are checked against the batch in forward(); here: its kind, and that normalising has maxC to scale with)
@@ -73,36 +71,11 @@ class MacenkoAugment(nn.Module):
         shape = tuple(getattr(he, "shape", ()))
         return shape[0] if len(shape) == 3 else 1
 
-    @staticmethod
-    def _batch(img: torch.Tensor) -> torch.Tensor:
-        if img.dim() == 3:
-            img = img.unsqueeze(0)
-        if img.dim() != 4 or img.shape[1] != 3:
-            raise ValueError(f"MacenkoAugment expects CHW / NCHW tensors with C=3, got shape {tuple(img.shape)}")
-        return img
-
-    def _target_device(self, batch: torch.Tensor) -> torch.device:
-        device = self.device if self.device is not None else batch.device
-        if device.type != "cuda":
-            raise ValueError(f"MacenkoAugment runs on a CUDA (ROCm) device; got a tensor on {device} (pass device='cuda' or move it there)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return device
-
-    def _engine(self, device: torch.device):
-        engine = self._engines.get(device)
-        if engine is None:
-            from stainx_amd.backends.torch_hip_backend import MacenkoHIP
-
-            engine = self._engines[device] = MacenkoHIP(device)
-        return engine
-
     def sample_factors(self, n: int, device: str | torch.device | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(alpha, beta)``, each (n, 2) float32 on ``device``: ``alpha ~ U[1 - sigma1, 1 + sigma1]``, ``beta ~ U[-sigma2, sigma2]``
         (exactly 1 and 0 for sigma = 0), drawn with the module's generator (on the generator's device, then moved)."""
-        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
-        draw_on = self.generator.device if self.generator is not None else device
-        u = torch.rand((2, n, 2), generator=self.generator, device=draw_on, dtype=torch.float32).to(device)
+        device = fe.draw_device(device, self.device)
+        u = fe.draw(self.generator, (2, n, 2), device).to(device)
         alpha = 1.0 + self.sigma1 * (2.0 * u[0] - 1.0)
         beta = self.sigma2 * (2.0 * u[1] - 1.0)
         return alpha, beta
@@ -110,17 +83,13 @@ class MacenkoAugment(nn.Module):
     def forward(self, img: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
         """``mask``: an explicit uint8 / bool tensor (N, H, W) or (N, 1, H, W) on the device, or ``"luminosity"``, for this call; it wins
         over the module's rule.  All argument errors are raised before any GPU work."""
-        single = img.dim() == 3
-        batch = self._batch(img)
-        n, _, h, w = batch.shape
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
+        batch, single, (n, h, w) = fe.image_batch(img, False, "MacenkoAugment")
+        masked, explicit = fe.call_mask(self.mask, mask, single, (n, h, w), self.device or batch.device)
         given = None if self.source is None else Macenko._check_source(self.source, n, need_max_c=self.normalizer is not None)
         for name, factor in (("alpha", alpha), ("beta", beta)):
             if factor is not None and tuple(getattr(factor, "shape", ())) != (n, 2):
                 raise ValueError(f"{name} must have shape (N, 2) = ({n}, 2), got {tuple(getattr(factor, 'shape', ()))}")
-        device = self._target_device(batch)
+        device = fe.run_device(self.device, batch.device, "MacenkoAugment", fe.ON_TENSOR)
         if alpha is None or beta is None:
             drawn = self.sample_factors(n, device)
             alpha = drawn[0] if alpha is None else alpha
@@ -128,7 +97,7 @@ class MacenkoAugment(nn.Module):
         sm = tmc = None
         if self.normalizer is not None:
             sm, tmc = self.normalizer._stain_matrix.to(device), self.normalizer._target_max_conc.to(device)
-        engine = self._engine(device)
+        engine = fe.held(self._engines, device, fe.engine, "MacenkoHIP")
         batch = batch.to(device)
         if given is not None:      # (a given source basis: one launch, no estimate)
             he, max_c = given

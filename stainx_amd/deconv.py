@@ -19,7 +19,7 @@ from typing import Any, NamedTuple
 import torch
 import torch.nn as nn
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 
 # (H, E or DAB, third) as Ruifrok & Johnston tabulate them; a missing third vector is the complement of the first two
 _NAMED = {
@@ -92,11 +92,8 @@ class DeconvSeparation:
 
 
 def _check_binning(bin_log2: Any, zero_bin: Any) -> tuple[int, int]:
-    if isinstance(bin_log2, bool) or not isinstance(bin_log2, int) or not 0 <= bin_log2 <= 8:
-        raise ValueError(f"bin_log2 must be an integer in [0, 8] (bins of width 2^-bin_log2), got {bin_log2!r}")
-    if isinstance(zero_bin, bool) or not isinstance(zero_bin, int) or not 0 <= zero_bin <= 255:
-        raise ValueError(f"zero_bin must be an integer in [0, 255] (the bin whose lower edge is concentration 0), got {zero_bin!r}")
-    return bin_log2, zero_bin
+    return (fe.whole_number(bin_log2, "bin_log2 must be an integer in [0, 8] (bins of width 2^-bin_log2)", 0, 8),
+            fe.whole_number(zero_bin, "zero_bin must be an integer in [0, 255] (the bin whose lower edge is concentration 0)", 0, 255))
 
 
 class StainHistograms(NamedTuple):
@@ -164,9 +161,7 @@ class StainHistograms(NamedTuple):
 
     @staticmethod
     def _stain(stain: Any) -> int:
-        if isinstance(stain, bool) or not isinstance(stain, int) or not 0 <= stain <= 2:
-            raise ValueError(f"stain must be 0, 1 or 2 (a column of the basis), got {stain!r}")
-        return stain
+        return fe.whole_number(stain, "stain must be 0, 1 or 2 (a column of the basis)", 0, 2)
 
     def _at_least(self, stain: int, edge: int) -> torch.Tensor:
         return self.counts[:, stain, edge:].sum(dim=-1)
@@ -267,17 +262,7 @@ def _statistics_rows(value: Any, n: int, what: str) -> tuple[torch.Tensor, torch
         if len(rows) != 1 or rows[0] not in (1, n) or tuple(value.sums.shape) != (rows[0], 3) or tuple(value.squares.shape) != (rows[0], 3):
             raise ValueError(f"{what} holds {rows} sets for a batch of {n} tiles (one set, or one per tile)")
         return value._mean_std()
-    if not isinstance(value, (tuple, list)) or len(value) != 2:
-        raise ValueError(f"{what} must be a ConcentrationStatistics or a (mean, std) pair")
-    shapes = []
-    for name, t in (("mean", value[0]), ("std", value[1])):
-        shape = tuple(getattr(t, "shape", ()))
-        if not isinstance(t, torch.Tensor) or not (shape == (3,) or (len(shape) == 2 and shape[1] == 3 and shape[0] in (1, n))):
-            raise ValueError(f"{what} {name} must be a tensor of shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
-        shapes.append(1 if len(shape) == 1 else shape[0])
-    if shapes[0] != shapes[1]:
-        raise ValueError(f"{what} mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
-    return value[0], value[1]
+    return fe.mean_std_rows(value, n, what, "ConcentrationStatistics")
 
 
 def check_gain_range(gain_range: Any) -> tuple[float, float]:
@@ -302,15 +287,6 @@ def match_factors(source_mean: torch.Tensor, source_std: torch.Tensor, target_me
     return alpha.masked_fill(leave, 1.0), beta.masked_fill(leave, 0.0)
 
 
-def _cuda_device(device: Any, fallback: torch.device, who: str) -> torch.device:
-    device = torch.device(device) if device is not None else fallback
-    if device.type != "cuda":
-        raise ValueError(f"{who} runs on a CUDA (ROCm) device; got {device} (pass device='cuda' or move the tensor there)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
 def _check_factor(name: str, factor: Any, n: int) -> None:
     if factor is not None and (not isinstance(factor, torch.Tensor) or tuple(factor.shape) != (n, 3)):
         raise ValueError(f"{name} must be a tensor of shape (N, 3) = ({n}, 3), got {tuple(getattr(factor, 'shape', ()))}")
@@ -332,67 +308,45 @@ class ColorDeconvolution:
         self.target = None if target is None else stain_basis(target)
         self.mask = masks.check_mask_mode(mask)
         self.luminosity_threshold = masks.check_threshold(luminosity_threshold)
-        if channel_axis in (-1, 3):
-            self.channels_last = True
-        elif channel_axis in (1, -3):
-            self.channels_last = False
-        else:
-            raise ValueError(f"Unsupported channel_axis={channel_axis}")
+        self.channels_last = fe.channels_last(channel_axis)
         if self.channels_last and self.mask is not None:
             raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
         self.channel_axis = channel_axis
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise ValueError(f"ColorDeconvolution runs on a CUDA (ROCm) device, got {self.device}")
+        self.device = fe.cuda_only(device, "ColorDeconvolution")
         self.normalize_to_0_1 = bool(normalize_to_0_1)
         self._engines: dict[torch.device, Any] = {}
         self._device_bases: dict[torch.device, tuple[torch.Tensor, torch.Tensor | None]] = {}
 
+    def _upload(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor | None]:
+        return tuple(None if b is None else b.to(device=device, dtype=torch.float32).contiguous() for b in (self.basis, self.target))
+
     def _bases_on(self, device: torch.device) -> tuple[torch.Tensor, torch.Tensor | None]:
         """The basis and the target as float32 tensors on ``device``, uploaded ONCE per device (a host basis copied in front of every
         call would put a pageable copy before the one launch, and keep a call from being captured)."""
-        held = self._device_bases.get(device)
-        if held is None:
-            def put(b):
-                return None if b is None else b.to(device=device, dtype=torch.float32).contiguous()
-
-            held = self._device_bases[device] = (put(self.basis), put(self.target))
-        return held
+        return fe.held(self._device_bases, device, self._upload)
 
     def _engine(self, device: torch.device):
-        engine = self._engines.get(device)
-        if engine is None:
-            from stainx_amd.backends.torch_hip_backend import DeconvHIP
+        return fe.held(self._engines, device, fe.engine, "DeconvHIP")
 
-            engine = self._engines[device] = DeconvHIP(device)
-        return engine
+    def _batch(self, x: Any, what: str) -> tuple[torch.Tensor, bool, tuple[int, int, int]]:
+        return fe.image_batch(x, self.channels_last, what)
 
-    def _batch(self, x: Any, what: str) -> tuple[torch.Tensor, bool]:
-        if not isinstance(x, torch.Tensor):
-            raise ValueError(f"{what} expects a tensor, got {type(x).__name__}")
-        single = x.dim() == 3
-        if single:
-            x = x.unsqueeze(0)
-        axis = 3 if self.channels_last else 1
-        if x.dim() != 4 or x.shape[axis] != 3:
-            layout = "HWC / NHWC" if self.channels_last else "CHW / NCHW"
-            raise ValueError(f"{what} expects {layout} tensors with C=3, got shape {tuple(x.shape)}")
-        return x, single
+    def _masking(self, mask: Any, single: bool, dims: tuple[int, int, int], batch: torch.Tensor) -> tuple[torch.Tensor | None, float] | None:
+        """The engine's ``masking=`` for a call -- ``(explicit mask or None, threshold)``, None when unmasked -- after the mask's checks."""
+        masked, explicit = fe.call_mask(self.mask, mask, single, dims, self.device or batch.device, self.channels_last, "deconvolution")
+        return (explicit, self.luminosity_threshold) if masked else None
 
     def _rows_ok(self, n: int) -> None:
         for name, b in (("basis", self.basis), ("target", self.target)):
             if b is not None and b.dim() == 3 and b.shape[0] not in (1, n):
                 raise ValueError(f"{name} holds {b.shape[0]} bases for a batch of {n} tiles (one basis, or one per tile)")
 
-    def _dims(self, x: torch.Tensor) -> tuple[int, int, int]:
-        return (x.shape[0], x.shape[1], x.shape[2]) if self.channels_last else (x.shape[0], x.shape[2], x.shape[3])
-
     def separate(self, x: torch.Tensor, stains: bool = True, concentrations: bool = False) -> DeconvSeparation:
-        batch, single = self._batch(x, "separate")
+        batch, single, _ = self._batch(x, "separate")
         if not stains and not concentrations:
             raise ValueError("separate: ask for the stain images (stains=True), the concentrations, or both")
         self._rows_ok(batch.shape[0])
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         imgs, conc = self._engine(device).separate(batch, self._bases_on(device)[0], stains=stains, concentrations=concentrations, normalize_to_0_1=self.normalize_to_0_1,
                                                    channels_last=self.channels_last)
         if single:
@@ -403,21 +357,16 @@ class ColorDeconvolution:
     def apply(self, x: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
         """``alpha`` / ``beta``: (N, 3) per-tile factors of the three concentrations, both or neither.  ``mask``: an explicit uint8 /
         bool tensor (N, H, W) or (N, 1, H, W) on the device, or ``"luminosity"``, for this call."""
-        batch, single = self._batch(x, "apply")
-        n, h, w = self._dims(batch)
+        batch, single, (n, h, w) = self._batch(x, "apply")
         if (alpha is None) != (beta is None):
             raise ValueError("alpha and beta go together: both or neither")
         _check_factor("alpha", alpha, n)
         _check_factor("beta", beta, n)
         self._rows_ok(n)
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
-        if masked and self.channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        masking = self._masking(mask, single, (n, h, w), batch)
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         out = self._engine(device).apply(batch, *self._bases_on(device), alpha=alpha, beta=beta, normalize_to_0_1=self.normalize_to_0_1, channels_last=self.channels_last,
-                                         masking=(explicit, self.luminosity_threshold) if masked else None)
+                                         masking=masking)
         return out.squeeze(0) if single else out
 
     def quantify(self, x: torch.Tensor, *, pooled: bool = False, bin_log2: int = 5, zero_bin: int = 64, mask: Any = None) -> StainHistograms:
@@ -426,18 +375,13 @@ class ColorDeconvolution:
         batch -- in ONE streaming launch that reads a pixel once and writes no map.  Bins are ``2^-bin_log2`` wide and bin ``zero_bin``
         starts at concentration 0 (defaults: 1/32 over [-2, 6)).  ``mask``: as in ``apply`` -- only masked-in pixels count.  Pixels with a
         non-finite concentration (NaN / Inf input, ``255 x + 1 <= 0``) are not counted.  See ``StainHistograms`` for the figures."""
-        batch, single = self._batch(x, "quantify")
-        n, h, w = self._dims(batch)
+        batch, single, (n, h, w) = self._batch(x, "quantify")
         bin_log2, zero_bin = _check_binning(bin_log2, zero_bin)
         self._rows_ok(n)
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
-        if masked and self.channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        masking = self._masking(mask, single, (n, h, w), batch)
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         counts, sums, pixels = self._engine(device).quantify(batch, self._bases_on(device)[0], bin_log2=bin_log2, zero_bin=zero_bin, per_tile=not pooled,
-                                                             channels_last=self.channels_last, masking=(explicit, self.luminosity_threshold) if masked else None)
+                                                             channels_last=self.channels_last, masking=masking)
         return StainHistograms(counts, sums, pixels, bin_log2, zero_bin)
 
     def estimate(self, x: torch.Tensor, *, pooled: bool = False, mask: Any = None) -> ConcentrationStatistics:
@@ -445,17 +389,12 @@ class ColorDeconvolution:
         ``separate(x, concentrations=True)`` would write (bit for bit those values) and the counted pixels -- a set per tile, or one set
         ``pooled`` over the batch -- in ONE streaming launch that reads a pixel once and writes no map (include/stainx_hip.h:
         sx_deconv_moments).  ``mask``: as in ``apply`` -- only masked-in pixels count.  See ``ConcentrationStatistics``."""
-        batch, single = self._batch(x, "estimate")
-        n, h, w = self._dims(batch)
+        batch, single, (n, h, w) = self._batch(x, "estimate")
         self._rows_ok(n)
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
-        if masked and self.channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        masking = self._masking(mask, single, (n, h, w), batch)
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         return ConcentrationStatistics(*self._engine(device).moments(batch, self._bases_on(device)[0], per_tile=not pooled, channels_last=self.channels_last,
-                                                                     masking=(explicit, self.luminosity_threshold) if masked else None))
+                                                                     masking=masking))
 
     def match(self, x: torch.Tensor, source: Any, target: Any, *, mask: Any = None, gain_range: tuple[float, float] = (0.1, 2.5)) -> torch.Tensor:
         """Mean / standard deviation matching of the concentrations ("Reinhard in stain space"): ``C' = alpha * C + beta`` with
@@ -464,23 +403,19 @@ class ColorDeconvolution:
         (3,), (1, 3) or (N, 3) tensors.  The factors are computed in float32 on the device: no synchronisation, the call is capturable.  A
         tile whose source row holds a NaN or a zero standard deviation (or whose target row holds a NaN) is mapped with ``alpha = 1,
         beta = 0``."""
-        batch, single = self._batch(x, "match")
-        n, h, w = self._dims(batch)
+        batch, single, (n, h, w) = self._batch(x, "match")
         gain_range = check_gain_range(gain_range)
         self._rows_ok(n)
-        masked, _ = masks.resolve(self.mask, mask.unsqueeze(0) if single and isinstance(mask, torch.Tensor) and mask.dim() == 2 else mask, n, h, w,
-                                  self.device if self.device is not None else batch.device)
-        if masked and self.channels_last:
-            raise ValueError("a masked deconvolution takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
+        self._masking(mask, single, (n, h, w), batch)
         sm, ss = _statistics_rows(source, n, "source")
         tm, ts = _statistics_rows(target, n, "target")
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         alpha, beta = match_factors(sm.to(device), ss.to(device), tm.to(device), ts.to(device), n, gain_range)
         return self.apply(x, alpha, beta, mask=mask)
 
     def combine(self, concentrations: torch.Tensor, out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
         """``separate``'s inverse: (N, 3, H, W) float32 concentrations -> tiles of ``out_dtype``, rebuilt with ``basis``."""
-        batch, single = self._batch(concentrations, "combine")
+        batch, single, _ = self._batch(concentrations, "combine")
         if batch.dtype != torch.float32:
             raise ValueError(f"concentrations must be float32, got {batch.dtype}")
         if out_dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32, torch.float64):
@@ -488,7 +423,7 @@ class ColorDeconvolution:
         if self.normalize_to_0_1 and out_dtype == torch.uint8:
             raise ValueError("normalize_to_0_1 needs a float out_dtype in combine (uint8 output stays on 0-255)")
         self._rows_ok(batch.shape[0])
-        device = _cuda_device(self.device, batch.device, "ColorDeconvolution")
+        device = fe.run_device(self.device, batch.device, "ColorDeconvolution")
         out = self._engine(device).combine(batch, self._bases_on(device)[0], out_dtype=out_dtype, normalize_to_0_1=self.normalize_to_0_1, channels_last=self.channels_last)
         return out.squeeze(0) if single else out
 
@@ -533,29 +468,21 @@ class HEDAugment(nn.Module):
     def sample_factors(self, n: int, device: str | torch.device | None = None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(alpha, beta)``, each (n, 3) float32 on ``device`` (exactly 1 and 0 for sigma = 0), drawn with the module's generator (on
         the generator's device, then moved), as ``MacenkoAugment.sample_factors`` draws them."""
-        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
-        draw_on = self.generator.device if self.generator is not None else device
-        u = torch.rand((2, n, 3), generator=self.generator, device=draw_on, dtype=torch.float32).to(device)
-        held = self._sigmas.get(device)
-        if held is None:
-            held = self._sigmas[device] = (torch.tensor(self.sigma1, dtype=torch.float32, device=device), torch.tensor(self.sigma2, dtype=torch.float32, device=device))
-        s1, s2 = held
+        device = fe.draw_device(device, self.device)
+        u = fe.draw(self.generator, (2, n, 3), device).to(device)
+        s1, s2 = fe.held(self._sigmas, device, lambda device: tuple(torch.tensor(s, dtype=torch.float32, device=device) for s in (self.sigma1, self.sigma2)))
         return 1.0 + s1 * (2.0 * u[0] - 1.0), s2 * (2.0 * u[1] - 1.0)
 
     def forward(self, img: torch.Tensor, alpha: torch.Tensor | None = None, beta: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
-        batch, single = self.deconv._batch(img, "HEDAugment")
-        n = batch.shape[0]
+        batch, _, (n, _, _) = self.deconv._batch(img, "HEDAugment")
         _check_factor("alpha", alpha, n)
         _check_factor("beta", beta, n)
         if alpha is None or beta is None:
-            device = _cuda_device(self.device, batch.device, "HEDAugment")
+            device = fe.run_device(self.device, batch.device, "HEDAugment")
             drawn = self.sample_factors(n, device)
             alpha = drawn[0] if alpha is None else alpha
             beta = drawn[1] if beta is None else beta
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        out = self.deconv.apply(batch, alpha, beta, mask=mask)
-        return out.squeeze(0) if single else out
+        return self.deconv.apply(img, alpha, beta, mask=mask)      # (a single tile: apply adds and drops the batch axis, of the tile and of its mask)
 
     def extra_repr(self) -> str:
         return f"sigma1={self.sigma1}, sigma2={self.sigma2}, normalize_to_0_1={self.deconv.normalize_to_0_1}, mask={self.deconv.mask!r}"

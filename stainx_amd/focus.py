@@ -30,7 +30,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from stainx_amd import masks as _masks
+from stainx_amd import _frontend as fe, masks as _masks
 
 CELL_SIDES = (8, 16, 32, 64)      # include/stainx_hip.h: sx_focus_statistics; and every multiple of 64
 
@@ -98,15 +98,11 @@ def _check_variance(value: Any) -> float:
 
 
 def _check_count(value: Any, name: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
-        raise ValueError(f"{name} must be a non-negative integer, got {value!r}")
-    return value
+    return fe.whole_number(value, f"{name} must be a non-negative integer", 0)
 
 
 def _check_size(value: Any, name: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
-        raise ValueError(f"{name} must be a positive integer, got {value!r}")
-    return value
+    return fe.whole_number(value, f"{name} must be a positive integer", 1)
 
 
 def check_block(block: Any, allow_none: bool = True) -> tuple[int, int] | None:
@@ -123,19 +119,19 @@ def grey_map(images: torch.Tensor, *, channel_axis: int = 1) -> torch.Tensor:
     """The grey level of a batch: (N, H, W) uint8 on the device, ``Y = (4899 r + 9617 g + 1868 b + 8192) >> 14`` of the pixel's 8-bit levels, one
     streaming kernel (include/stainx_hip.h: sx_grey_map).  ``images`` as for :func:`stainx_amd.tissue_mask`.  A pixel with a NaN in any
     channel has Y = 0.  :func:`stainx_amd.median_filter`, :func:`stainx_amd.level_histogram` and :func:`stainx_amd.level_mask` take the result."""
-    last = _masks._check_images(images, channel_axis, "grey_map")
+    last = fe.image_4d(images, channel_axis, "grey_map")[0]
     from stainx_amd.backends.torch_hip_backend import grey_map_native
 
     return grey_map_native(images, last)
 
 
-def _statistics(images: torch.Tensor, block: tuple[int, int] | None, mask: Any, pooled: bool, last: bool, threshold: float) -> tuple[FocusStatistics, torch.Tensor | None]:
+def _statistics(images: torch.Tensor, block: tuple[int, int] | None, mask: Any, pooled: bool, last: bool, dims: tuple[int, int, int],
+                threshold: float) -> tuple[FocusStatistics, torch.Tensor | None]:
     from stainx_amd.backends.torch_hip_backend import focus_statistics_native, tissue_mask_native
 
-    n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if last else (images.shape[0], images.shape[2], images.shape[3])
     if isinstance(mask, torch.Tensor) and images.device.type != "cuda":
         raise ValueError(f"an explicit mask goes with images on the GPU, got images on {images.device}")
-    masked, explicit = _masks.resolve(None, mask, n, h, w, images.device)
+    masked, explicit = _masks.resolve(None, mask, *dims, images.device)
     if masked and explicit is None:      # the luminosity rule: the tissue_mask launch in front, on the same stream
         explicit = tissue_mask_native(images, threshold, last)[0]
     words = focus_statistics_native(images, block, explicit, pooled, last)
@@ -157,8 +153,8 @@ def focus_statistics(images: torch.Tensor, *, block: tuple[int, int] | None = No
     if pooled and block is not None:
         raise ValueError(f"pooled=True pools whole tiles: it goes with block=None, got block={block!r}")
     threshold = _masks.check_threshold(luminosity_threshold)
-    last = _masks._check_images(images, channel_axis, "focus_statistics")
-    return _statistics(images, block, mask, bool(pooled), last, threshold)[0]
+    last, dims = fe.image_4d(images, channel_axis, "focus_statistics")
+    return _statistics(images, block, mask, bool(pooled), last, dims, threshold)[0]
 
 
 def cells_mask(cells: torch.Tensor, height: int, width: int, block: tuple[int, int], *, mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -193,8 +189,7 @@ def focus_mask(images: torch.Tensor, min_variance: float, *, block: tuple[int, i
     block = check_block(block, allow_none=False)
     min_pixels = (block[0] * block[1]) // 4 if min_pixels is None else _check_count(min_pixels, "min_pixels")
     threshold = _masks.check_threshold(luminosity_threshold)
-    last = _masks._check_images(images, channel_axis, "focus_mask")
-    stats, explicit = _statistics(images, block, mask, False, last, threshold)
-    n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if last else (images.shape[0], images.shape[2], images.shape[3])
+    last, (n, h, w) = fe.image_4d(images, channel_axis, "focus_mask")
+    stats, explicit = _statistics(images, block, mask, False, last, (n, h, w), threshold)
     out, counts = cells_mask(stats.sharp(min_variance, min_pixels=min_pixels), h, w, block, mask=explicit)
     return FocusDetection(out, counts, stats)

@@ -17,40 +17,10 @@ from typing import Any
 import torch
 import torch.nn as nn
 
-from stainx_amd import masks
-from stainx_amd.deconv import _cuda_device
+from stainx_amd import _frontend as fe, masks
 
 IDENTITY_ROW = (0.0, 1.0, 0.0, 1.0, 0.0)      # (dh, a_s, b_s, a_v, b_v)
-_ENGINES: dict[torch.device, Any] = {}
-
-
-def _engine(device: torch.device):
-    engine = _ENGINES.get(device)
-    if engine is None:
-        from stainx_amd.backends.torch_hip_backend import HsvHIP
-
-        engine = _ENGINES[device] = HsvHIP(device)
-    return engine
-
-
-def _channels_last(channel_axis: int) -> bool:
-    if channel_axis in (-1, 3):
-        return True
-    if channel_axis in (1, -3):
-        return False
-    raise ValueError(f"Unsupported channel_axis={channel_axis}")
-
-
-def _batch(x: Any, channels_last: bool, who: str) -> tuple[torch.Tensor, bool]:
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{who} expects a tensor, got {type(x).__name__}")
-    single = x.dim() == 3
-    if single:
-        x = x.unsqueeze(0)
-    if x.dim() != 4 or x.shape[3 if channels_last else 1] != 3:
-        layout = "HWC / NHWC" if channels_last else "CHW / NCHW"
-        raise ValueError(f"{who} expects {layout} tensors with C=3, got shape {tuple(x.shape)}")
-    return x, single
+_ENGINES: dict[torch.device, Any] = {}      # (one engine per device for the module: the functional form has no object to keep it)
 
 
 def _check_rows(rows: Any, n: int) -> None:
@@ -62,16 +32,11 @@ def _check_rows(rows: Any, n: int) -> None:
 def _adjust(images: torch.Tensor, rows: torch.Tensor, who: str, *, mask: Any, mode: str | None, luminosity_threshold: float, channels_last: bool, normalize_to_0_1: bool,
             out_dtype: torch.dtype | None, device: torch.device | None) -> torch.Tensor:
     """The one path of both entry points; every argument error is raised before any GPU work."""
-    batch, single = _batch(images, channels_last, who)
-    n, h, w = (batch.shape[0], batch.shape[1], batch.shape[2]) if channels_last else (batch.shape[0], batch.shape[2], batch.shape[3])
-    _check_rows(rows, n)
-    if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-        mask = mask.unsqueeze(0)
-    masked, explicit = masks.resolve(mode, mask, n, h, w, device if device is not None else batch.device)
-    if masked and channels_last:
-        raise ValueError("a masked HSV jitter takes planar (NCHW) tiles only: mask= with channel_axis=-1 is not supported")
-    target = _cuda_device(device, batch.device, who)
-    out = _engine(target).apply(batch, rows, normalize_to_0_1=normalize_to_0_1, out_dtype=out_dtype, channels_last=channels_last,
+    batch, single, dims = fe.image_batch(images, channels_last, who)
+    _check_rows(rows, dims[0])
+    masked, explicit = fe.call_mask(mode, mask, single, dims, device or batch.device, channels_last, "HSV jitter")
+    engine = fe.held(_ENGINES, fe.run_device(device, batch.device, who), fe.engine, "HsvHIP")
+    out = engine.apply(batch, rows, normalize_to_0_1=normalize_to_0_1, out_dtype=out_dtype, channels_last=channels_last,
                                 masking=(explicit, luminosity_threshold) if masked else None)
     return out.squeeze(0) if single else out
 
@@ -83,20 +48,14 @@ def adjust_hsv(images: torch.Tensor, rows: torch.Tensor, *, mask: Any = None, ch
     (N, H, W) or (N, 1, H, W), or ``"luminosity"`` (the rule at ``luminosity_threshold``): only masked-in pixels change.
     ``normalize_to_0_1``: uint8 tiles come out as float32 in [0, 1], float tiles are divided by 255; ``out_dtype``: bfloat16 / float16
     written directly from uint8 tiles.  One launch, no synchronisation; the rows stay on the device."""
-    return _adjust(images, rows, "adjust_hsv", mask=mask, mode=None, luminosity_threshold=masks.check_threshold(luminosity_threshold), channels_last=_channels_last(channel_axis),
+    return _adjust(images, rows, "adjust_hsv", mask=mask, mode=None, luminosity_threshold=masks.check_threshold(luminosity_threshold), channels_last=fe.channels_last(channel_axis),
                    normalize_to_0_1=bool(normalize_to_0_1), out_dtype=out_dtype, device=None)
 
 
 def _magnitude(name: str, value: Any, upper: float | None, closed: bool) -> float:
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a number, got {value!r}") from None
-    inside = math.isfinite(v) and v >= 0.0 and (upper is None or (v <= upper if closed else v < upper))
-    if not inside:
-        bound = "be a finite value >= 0" if upper is None else f"lie in [0, {upper}{']' if closed else ')'}"
-        raise ValueError(f"{name} must {bound}, got {value!r}")
-    return v
+    bound = "be a finite value >= 0" if upper is None else f"lie in [0, {upper}{']' if closed else ')'}"
+    return fe.real_number(value, f"{name} must be a number", f"{name} must {bound}",
+                          lambda v: math.isfinite(v) and v >= 0.0 and (upper is None or (v <= upper if closed else v < upper)))
 
 
 class HSVAugment(nn.Module):
@@ -117,18 +76,10 @@ class HSVAugment(nn.Module):
         self.value = _magnitude("value", value, 1.0, False)
         self.saturation_shift = _magnitude("saturation_shift", saturation_shift, None, False)
         self.value_shift = _magnitude("value_shift", value_shift, None, False)
-        try:
-            p = float(p)
-        except (TypeError, ValueError):
-            raise ValueError(f"p must be a number in [0, 1], got {p!r}") from None
-        if not 0.0 <= p <= 1.0:      # (false for a NaN)
-            raise ValueError(f"p must lie in [0, 1], got {p}")
-        self.p = p
+        self.p = fe.real_number(p, "p must be a number in [0, 1]", "p must lie in [0, 1]", lambda v: 0.0 <= v <= 1.0, show=float)
         self.mask = masks.check_mask_mode(mask)
         self.luminosity_threshold = masks.check_threshold(luminosity_threshold)
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise ValueError(f"HSVAugment runs on a CUDA (ROCm) device, got {self.device}")
+        self.device = fe.cuda_only(device, "HSVAugment")
         self.normalize_to_0_1 = bool(normalize_to_0_1)
         self.generator = generator
         self._held: dict[torch.device, tuple[torch.Tensor, torch.Tensor]] = {}      # (the identity row and the magnitudes on a device: uploaded once)
@@ -138,30 +89,23 @@ class HSVAugment(nn.Module):
         device, then moved), as ``HEDAugment.sample_factors`` draws: ``identity + magnitude * (2 u - 1)``, ``u = rand((n, 5))`` -- exactly
         the identity row where every magnitude is 0.  ``p < 1``: one more draw, ``rand(n) < p``, in that order; a tile that is not chosen
         gets a NaN row."""
-        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
-        draw_on = self.generator.device if self.generator is not None else device
-        u = torch.rand((n, 5), generator=self.generator, device=draw_on, dtype=torch.float32).to(device)
-        held = self._held.get(device)
-        if held is None:
-            magnitudes = (self.hue, self.saturation, self.saturation_shift, self.value, self.value_shift)
-            held = self._held[device] = (torch.tensor(IDENTITY_ROW, dtype=torch.float32, device=device), torch.tensor(magnitudes, dtype=torch.float32, device=device))
-        rows = held[0] + held[1] * (2.0 * u - 1.0)
+        device = fe.draw_device(device, self.device)
+        u = fe.draw(self.generator, (n, 5), device).to(device)
+        magnitudes = (self.hue, self.saturation, self.saturation_shift, self.value, self.value_shift)
+        identity, scale = fe.held(self._held, device, lambda device: tuple(torch.tensor(row, dtype=torch.float32, device=device) for row in (IDENTITY_ROW, magnitudes)))
+        rows = identity + scale * (2.0 * u - 1.0)
         if self.p < 1.0:
-            chosen = (torch.rand((n,), generator=self.generator, device=draw_on, dtype=torch.float32) < self.p).to(device).unsqueeze(-1)
-            rows = torch.where(chosen, rows, torch.full_like(rows, float("nan")))
+            rows = torch.where(fe.chosen(self.generator, n, self.p, device), rows, torch.full_like(rows, float("nan")))
         return rows
 
     def forward(self, img: torch.Tensor, rows: torch.Tensor | None = None, mask: Any = None) -> torch.Tensor:
         """``rows``: explicit (5,), (1, 5) or (N, 5) rows instead of a draw.  ``mask``: an explicit uint8 / bool tensor (N, H, W) or
         (N, 1, H, W) on the device, or ``"luminosity"``, for this call; it wins over the module's rule."""
-        batch, single = _batch(img, False, "HSVAugment")
-        if rows is None:
-            rows = self.sample_rows(batch.shape[0], _cuda_device(self.device, batch.device, "HSVAugment"))
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        out = _adjust(batch, rows, "HSVAugment", mask=mask, mode=self.mask, luminosity_threshold=self.luminosity_threshold, channels_last=False,
-                      normalize_to_0_1=self.normalize_to_0_1, out_dtype=None, device=self.device)
-        return out.squeeze(0) if single else out
+        if rows is None:      # (the draw comes first: the device is resolved before the mask is looked at)
+            batch, _, (n, _, _) = fe.image_batch(img, False, "HSVAugment")
+            rows = self.sample_rows(n, fe.run_device(self.device, batch.device, "HSVAugment"))
+        return _adjust(img, rows, "HSVAugment", mask=mask, mode=self.mask, luminosity_threshold=self.luminosity_threshold, channels_last=False,
+                       normalize_to_0_1=self.normalize_to_0_1, out_dtype=None, device=self.device)
 
     def extra_repr(self) -> str:
         mask = "None" if self.mask is None else f"{self.mask!r} (luminosity_threshold={self.luminosity_threshold})"

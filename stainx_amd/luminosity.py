@@ -12,6 +12,8 @@ from typing import Any, NamedTuple
 import torch
 from torch import nn
 
+from stainx_amd import _frontend as fe
+
 
 class LuminosityEstimate(NamedTuple):
     """``luminance``: (rows,) float32 on the device, the percentile of the linear-light luminance Y (NaN for an empty set); ``pixels``:
@@ -44,70 +46,44 @@ class LuminosityStandardizer(nn.Module):
 
     def __init__(self, percentile: float = 95.0, statistics: str = "tile", device: str | torch.device | None = None):
         super().__init__()
-        try:
-            number = float(percentile)
-        except (TypeError, ValueError):
-            raise ValueError(f"percentile must be a number in (0, 100], got {percentile!r}") from None
-        if isinstance(percentile, bool) or not math.isfinite(number) or not 0.0 < number <= 100.0:
-            raise ValueError(f"percentile must be a number in (0, 100], got {percentile!r}")
+        rule = "percentile must be a number in (0, 100]"
+        self.percentile = fe.real_number(percentile, rule, rule, lambda v: not isinstance(percentile, bool) and math.isfinite(v) and 0.0 < v <= 100.0)
         if statistics not in ("tile", "batch"):
             raise ValueError(f"statistics must be 'tile' or 'batch', got {statistics!r}")
-        self.percentile = number
         self.statistics = statistics
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise ValueError(f"LuminosityStandardizer runs on a CUDA (ROCm) device, got {self.device}")
+        self.device = fe.cuda_only(device, "LuminosityStandardizer")
         self._engines: dict[torch.device, Any] = {}
 
     # ---- checks (all before any GPU work) ---------------------------------------------------------------------
     @staticmethod
     def _batch(images: Any) -> tuple[torch.Tensor, bool]:
-        if not isinstance(images, torch.Tensor):
-            raise ValueError(f"LuminosityStandardizer expects a torch.Tensor, got {type(images).__name__}")
-        single = images.dim() == 3
-        if single:
-            images = images.unsqueeze(0)
-        if images.dim() != 4 or images.shape[1] != 3:
-            raise ValueError(f"LuminosityStandardizer expects CHW / NCHW tensors with C=3, got shape {tuple(images.shape)}")
-        return images, single
+        return fe.image_batch(images, False, "LuminosityStandardizer", tensor="a torch.Tensor")[:2]
 
     @staticmethod
     def _check_mask(mask: Any, batch: torch.Tensor, single: bool) -> torch.Tensor | None:
+        """The standardiser's own mask rule: which pixels enter the set -- no ``"luminosity"`` mode and no (N, 1, H, W) shape."""
         if mask is None:
             return None
         if isinstance(mask, str):
             raise ValueError(f"mask must be an explicit uint8 / bool (N, H, W) tensor; the {mask!r} rule is not a mask mode of LuminosityStandardizer")
         if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
             raise ValueError(f"mask must be a uint8 / bool tensor, got {type(mask).__name__}" + (f" of {mask.dtype}" if isinstance(mask, torch.Tensor) else ""))
-        if single and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
+        mask = fe.tile_mask(mask, single)
         want = (batch.shape[0], batch.shape[2], batch.shape[3])
         if tuple(mask.shape) != want:
             raise ValueError(f"mask must have shape {want}, got {tuple(mask.shape)}")
         return mask
 
-    def _target_device(self, batch: torch.Tensor) -> torch.device:
-        device = self.device if self.device is not None else batch.device
-        if device.type != "cuda":
-            raise ValueError(f"LuminosityStandardizer runs on a CUDA (ROCm) device; got a tensor on {device} (pass device='cuda' or move it there)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return device
-
-    def _engine(self, device: torch.device):
-        engine = self._engines.get(device)
-        if engine is None:
-            from stainx_amd.backends.torch_hip_backend import LuminosityHIP
-
-            engine = self._engines[device] = LuminosityHIP(device)
-        return engine
+    def _engine(self, batch: torch.Tensor):
+        device = fe.run_device(self.device, batch.device, "LuminosityStandardizer", fe.ON_TENSOR)
+        return fe.held(self._engines, device, fe.engine, "LuminosityHIP")
 
     # ---- the public surface -----------------------------------------------------------------------------------
     def estimate(self, images: torch.Tensor, *, pooled: bool = False, mask: Any = None) -> LuminosityEstimate:
         """The percentile of every tile, or with ``pooled=True`` ONE over the batch (a slide's thumbnail, say)."""
         batch, single = self._batch(images)
         mask = self._check_mask(mask, batch, single)
-        engine = self._engine(self._target_device(batch))
+        engine = self._engine(batch)
         return LuminosityEstimate(*engine.percentile(batch, self.percentile, pooled=bool(pooled), mask=mask))
 
     def apply(self, images: torch.Tensor, estimate: Any) -> torch.Tensor:
@@ -117,7 +93,7 @@ class LuminosityStandardizer(nn.Module):
         if not isinstance(luminance, torch.Tensor) or luminance.dim() > 1 or luminance.numel() not in (1, batch.shape[0]):
             raise ValueError(f"estimate must be a LuminosityEstimate or a tensor of 1 or {batch.shape[0]} luminances, got "
                              f"{tuple(luminance.shape) if isinstance(luminance, torch.Tensor) else type(luminance).__name__}")
-        engine = self._engine(self._target_device(batch))
+        engine = self._engine(batch)
         out = engine.apply(batch, luminance)
         return out.squeeze(0) if single else out
 
@@ -125,7 +101,7 @@ class LuminosityStandardizer(nn.Module):
         """``estimate`` then ``apply`` on the current stream (``statistics="batch"``: a pooled estimate)."""
         batch, single = self._batch(images)
         mask = self._check_mask(mask, batch, single)
-        engine = self._engine(self._target_device(batch))
+        engine = self._engine(batch)
         batch = batch.to(engine.device).contiguous()
         luminance, _ = engine.percentile(batch, self.percentile, pooled=self.statistics == "batch", mask=mask)
         out = engine.apply(batch, luminance)

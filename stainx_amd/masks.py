@@ -16,23 +16,18 @@ luminosity rule asks "is the pixel dark".
 """
 from __future__ import annotations
 
-import math
 from typing import Any, NamedTuple
 
 import torch
+
+from stainx_amd import _frontend as fe
 
 MASK_MODES = ("luminosity",)
 DEFAULT_LUMINOSITY_THRESHOLD = 0.8
 
 
 def check_threshold(luminosity_threshold: Any) -> float:
-    try:
-        value = float(luminosity_threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"luminosity_threshold must be a number in (0, 1), got {luminosity_threshold!r}") from None
-    if math.isnan(value) or not 0.0 < value < 1.0:
-        raise ValueError(f"luminosity_threshold must lie in (0, 1), got {luminosity_threshold!r}")
-    return value
+    return fe.real_number(luminosity_threshold, "luminosity_threshold must be a number in (0, 1)", "luminosity_threshold must lie in (0, 1)", lambda v: 0.0 < v < 1.0)
 
 
 def check_mask_mode(mask: Any) -> str | None:
@@ -74,13 +69,7 @@ def tissue_mask(images: torch.Tensor, luminosity_threshold: float = DEFAULT_LUMI
     tile, both on the device.  ``images``: NCHW (``channel_axis=-1``: NHWC) with C = 3, any supported element type; a CPU tensor is moved
     to the current GPU.  One streaming kernel (include/stainx_hip.h: sx_tissue_mask)."""
     threshold = check_threshold(luminosity_threshold)
-    if not isinstance(images, torch.Tensor) or images.dim() != 4:
-        raise ValueError(f"tissue_mask expects a 4-D image tensor, got {type(images).__name__} with shape {tuple(getattr(images, 'shape', ()))}")
-    last = channel_axis in (-1, 3)
-    if not last and channel_axis not in (1, -3):
-        raise ValueError(f"Unsupported channel_axis={channel_axis}")
-    if images.shape[-1 if last else 1] != 3:
-        raise ValueError(f"tissue_mask expects 3 channels on axis {channel_axis}, got shape {tuple(images.shape)}")
+    last = fe.image_4d(images, channel_axis, "tissue_mask")[0]
     from stainx_amd.backends.torch_hip_backend import tissue_mask_native
 
     return tissue_mask_native(images, threshold, last)
@@ -153,22 +142,8 @@ def _check_histogram(hist: Any) -> tuple[torch.Tensor, torch.Tensor]:
     return counts, pixels
 
 
-def _check_images(images: Any, channel_axis: int, what: str) -> bool:
-    """The checks of :func:`tissue_mask` on its images; returns whether the channels come last."""
-    if not isinstance(images, torch.Tensor) or images.dim() != 4:
-        raise ValueError(f"{what} expects a 4-D image tensor, got {type(images).__name__} with shape {tuple(getattr(images, 'shape', ()))}")
-    last = channel_axis in (-1, 3)
-    if not last and channel_axis not in (1, -3):
-        raise ValueError(f"Unsupported channel_axis={channel_axis}")
-    if images.shape[-1 if last else 1] != 3:
-        raise ValueError(f"{what} expects 3 channels on axis {channel_axis}, got shape {tuple(images.shape)}")
-    return last
-
-
 def _check_radius(radius: Any, name: str, least: int) -> int:
-    if isinstance(radius, bool) or not isinstance(radius, int) or not least <= radius <= MAX_MORPHOLOGY_RADIUS:
-        raise ValueError(f"{name} must be an integer in {least}..{MAX_MORPHOLOGY_RADIUS}, got {radius!r}")
-    return radius
+    return fe.whole_number(radius, f"{name} must be an integer in {least}..{MAX_MORPHOLOGY_RADIUS}", least, MAX_MORPHOLOGY_RADIUS)
 
 
 def _check_element(element: Any) -> str:
@@ -178,15 +153,11 @@ def _check_element(element: Any) -> str:
 
 
 def _check_area(area: Any, name: str, least: int) -> int:
-    if isinstance(area, bool) or not isinstance(area, int) or area < least:
-        raise ValueError(f"{name} must be an integer of at least {least}, got {area!r}")
-    return area
+    return fe.whole_number(area, f"{name} must be an integer of at least {least}", least)
 
 
 def _check_connectivity(connectivity: Any) -> int:
-    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in CONNECTIVITIES:
-        raise ValueError(f"connectivity must be one of {list(CONNECTIVITIES)}, got {connectivity!r}")
-    return connectivity
+    return fe.whole_number(connectivity, f"connectivity must be one of {list(CONNECTIVITIES)}", among=CONNECTIVITIES)
 
 
 def _check_detection_mask(mask: Any) -> None:
@@ -202,7 +173,7 @@ def luminosity_histogram(images: torch.Tensor, *, pooled: bool = False, channel_
     """256-bin integer histograms of lightness, per tile or (``pooled=True``) one for the batch: a memset and one streaming kernel
     (include/stainx_hip.h: sx_luminosity_histogram).  ``images`` as for :func:`tissue_mask`.  See :class:`LuminosityHistogram` for what a
     bin is; a NaN pixel lands in bin 255."""
-    last = _check_images(images, channel_axis, "luminosity_histogram")
+    last = fe.image_4d(images, channel_axis, "luminosity_histogram")[0]
     from stainx_amd.backends.torch_hip_backend import luminosity_histogram_native
 
     counts = luminosity_histogram_native(images, bool(pooled), last)
@@ -345,7 +316,7 @@ def otsu_mask(images: torch.Tensor, *, pooled: bool = False, channel_axis: int =
     go, opening, closing, small holes are filled -- and its hazard: glass below ``min_hole_area`` is filled).  Without them tile i's mask has the bits of
     ``tissue_mask(images[i:i+1], thresholds[i])``.  One synchronisation point: :func:`otsu_threshold`, which also states the hazard --
     Otsu always splits, so per-tile thresholds are for tiles that hold both tissue and glass; otherwise pool, or threshold a thumbnail."""
-    last = _check_images(images, channel_axis, "otsu_mask")
+    last = fe.image_4d(images, channel_axis, "otsu_mask")[0]
     fallback = check_threshold(fallback)
     _check_radius(open_radius, "open_radius", 0)
     _check_radius(close_radius, "close_radius", 0)
@@ -410,15 +381,11 @@ def _check_levels(levels: Any, what: str) -> None:
 
 
 def _check_median_size(size: Any, name: str = "size") -> int:
-    if isinstance(size, bool) or not isinstance(size, int) or size not in MEDIAN_SIZES:
-        raise ValueError(f"{name} must be an odd integer in 3..{MEDIAN_SIZES[-1]}, got {size!r}")
-    return size
+    return fe.whole_number(size, f"{name} must be an odd integer in 3..{MEDIAN_SIZES[-1]}", among=MEDIAN_SIZES)
 
 
 def _check_level(level: Any, name: str) -> int:
-    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= 254:
-        raise ValueError(f"{name} must be an integer level in 0..254, got {level!r}")
-    return level
+    return fe.whole_number(level, f"{name} must be an integer level in 0..254", 0, 254)
 
 
 def saturation_map(images: torch.Tensor, *, channel_axis: int = 1) -> torch.Tensor:
@@ -432,7 +399,7 @@ def saturation_map(images: torch.Tensor, *, channel_axis: int = 1) -> torch.Tens
     smallest of a pixel's three levels, ``S = 0`` if ``M == 0``, else ``(510 * (M - m) + M) // (2 * M)``: 255 (M - m) / M rounded half up, in
     0..255.  A pixel with a NaN in any channel has S = 0: background, as under the luminosity rule.  This is the package's own exact
     rule; it is not pinned to OpenCV's table-based conversion."""
-    last = _check_images(images, channel_axis, "saturation_map")
+    last = fe.image_4d(images, channel_axis, "saturation_map")[0]
     from stainx_amd.backends.torch_hip_backend import saturation_map_native
 
     return saturation_map_native(images, last)
@@ -509,7 +476,7 @@ def saturation_mask(images: torch.Tensor, *, threshold: int | None = None, media
     Known hazards.  Near-black pixels have an unstable, often high, saturation -- (10, 10, 12) has S = 43 -- so BLACK MARKER PASSES this
     rule, as it does in CLAM: AND the result with :func:`tissue_mask` where that matters.  COLOURED PEN is saturated and passes too.  And
     with ``threshold=None`` Otsu ALWAYS splits (:func:`otsu_level`): per-tile thresholds are for tiles that hold both tissue and glass."""
-    last = _check_images(images, channel_axis, "saturation_mask")
+    fe.image_4d(images, channel_axis, "saturation_mask")
     if threshold is not None:
         _check_level(threshold, "threshold")
     if isinstance(median_size, bool) or not isinstance(median_size, int) or median_size != 0:

@@ -5,7 +5,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 from stainx_amd.normalizers._template import NormalizerTemplate
 
 
@@ -90,16 +90,17 @@ class HistogramMatching(NormalizerTemplate):
     def arguments(self) -> tuple:
         return (self._ref_histograms_256 if self._ref_histograms_256 else self._reference_histogram,)
 
-    def _masking(self, images: Any, mask: Any, what: str) -> tuple[bool, Any]:
-        """(masked call?, explicit mask or None), checked against the images before any GPU work."""
+    def _check_images(self, images: Any, what: str) -> tuple[int, int, int]:
+        """(n, h, w); ``channel_axis=3`` means channels-last for 4-D input only (on a 3-D image it is the reference's HWC axis)."""
+        last = self.channel_axis == -1 or (self.channel_axis == 3 and len(getattr(images, "shape", ())) == 4)
+        return fe.image_batch(images, last, "HistogramMatching", promote=False, tensor=None,
+                              refusal=f"HistogramMatching {what} expects 4D images with 3 channels on axis {self.channel_axis}")[2]
+
+    def _masking(self, images: Any, mask: Any, what: str, dims: tuple[int, int, int] | None = None) -> tuple[bool, Any]:
+        """(masked call?, explicit mask or None), checked against the images (``dims``: where the caller has checked them) before any GPU work."""
         if mask is None and self.mask is None:
             return False, None
-        shape = tuple(getattr(images, "shape", ()))
-        last = self.channel_axis == -1 or (self.channel_axis == 3 and len(shape) == 4)
-        if len(shape) != 4 or shape[-1 if last else 1] != 3:
-            raise ValueError(f"HistogramMatching {what} expects 4D images with 3 channels on axis {self.channel_axis}, got shape {shape}")
-        n, h, w = (shape[0], shape[1], shape[2]) if last else (shape[0], shape[2], shape[3])
-        return masks.resolve(self.mask, mask, n, h, w, self.device)
+        return fe.call_mask(self.mask, mask, False, dims or self._check_images(images, what), self.device)
 
     def fit(self, images: Any, mask: Any = None) -> "HistogramMatching":
         masked, explicit = self._masking(images, mask, "fit")
@@ -124,20 +125,12 @@ class HistogramMatching(NormalizerTemplate):
         return self._get_backend_impl().transform_tiles(images, *self.arguments())
 
     # ---- slide level: estimate once, apply given tables -----------------------------------------------------------
-    def _check_images(self, images: Any, what: str) -> int:
-        shape = tuple(getattr(images, "shape", ()))
-        last = self.channel_axis == -1 or (self.channel_axis == 3 and len(shape) == 4)
-        if len(shape) != 4 or shape[-1 if last else 1] != 3:
-            raise ValueError(f"HistogramMatching {what} expects 4D images with 3 channels on axis {self.channel_axis}, got shape {shape}")
-        return shape[0]
-
     def estimate(self, images: Any, *, pooled: bool = False, mask: Any = None) -> HistogramStatistics:
         """The integer histograms of ``images``, without transforming them: every tile's own, ``counts`` (N, 3, 256) and ``pixels`` (N,) --
         or with ``pooled=True`` ONE set over the batch, (1, 3, 256) and (1,).  The slide-level workflow: estimate batch by batch (a
         thumbnail, a sample of tissue tiles, the whole slide), ``HistogramStatistics.pool`` them, ``lookup_tables`` once, ``apply`` to
         every batch.  Needs no ``fit()``.  With a mask (the normaliser's rule, or ``mask=`` for this call) only tissue pixels count."""
-        self._check_images(images, "estimate")
-        masked, explicit = self._masking(images, mask, "estimate")
+        masked, explicit = self._masking(images, mask, "estimate", self._check_images(images, "estimate"))
         counts, pixels = self._get_backend_impl().estimate_histograms(images, per_tile=not pooled, masked=masked, mask=explicit, luminosity_threshold=self.luminosity_threshold)
         return HistogramStatistics(counts, pixels)
 
@@ -159,8 +152,9 @@ class HistogramMatching(NormalizerTemplate):
         unmasked result, background pixels the bits of the input."""
         if not self._is_fitted:
             raise ValueError("Must call fit() before transform()")
-        n = self._check_images(images, "apply")
-        masked, explicit = self._masking(images, mask, "apply")
+        dims = self._check_images(images, "apply")
+        n = dims[0]
+        masked, explicit = self._masking(images, mask, "apply", dims)
         if isinstance(source, torch.Tensor):
             shape = tuple(source.shape)
             if not (shape == (3, 256) or (len(shape) == 3 and shape[1:] == (3, 256) and shape[0] in (1, n))):

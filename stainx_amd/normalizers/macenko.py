@@ -5,7 +5,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 from stainx_amd.normalizers._template import NormalizerTemplate
 
 
@@ -99,14 +99,16 @@ class Macenko(NormalizerTemplate):
             options["out_dtype"] = self.output_dtype
         return options
 
+    @staticmethod
+    def _nchw(images: Any, who: str) -> tuple[int, int, int]:
+        """(n, h, w) of planar images -- anything with a ``shape`` --, or ``who``'s refusal."""
+        return fe.image_batch(images, False, who, promote=False, tensor=None, refusal=f"{who} expects NCHW images with C=3")[2]
+
     def _masking(self, images: Any, mask: Any, what: str) -> tuple[bool, Any]:
         """(masked call?, explicit mask or None) -- the call's ``mask=`` wins over the normaliser's rule --, checked before any GPU work."""
         if mask is None and self.mask is None:
             return False, None
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Macenko {what} expects NCHW images with C=3, got shape {shape}")
-        masked, explicit = masks.resolve(self.mask, mask, shape[0], shape[2], shape[3], self.device)
+        masked, explicit = fe.call_mask(self.mask, mask, False, self._nchw(images, f"Macenko {what}"), self.device)
         if masked and self._precision == "sampled":
             raise ValueError("precision='sampled' has no masked form: a mask runs the exact four-pass estimate")
         return masked, explicit
@@ -154,10 +156,8 @@ class Macenko(NormalizerTemplate):
             own_basis = not self._is_fitted
         elif not own_basis and not self._is_fitted:
             raise ValueError("own_basis=False separates with the fitted reference: call fit() first")
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Macenko separate expects NCHW images with C=3, got shape {shape}")
-        given = None if source is None else self._check_source(source, shape[0], need_max_c=not own_basis)
+        n = self._nchw(images, "Macenko separate")[0]
+        given = None if source is None else self._check_source(source, n, need_max_c=not own_basis)
         masked, explicit = self._masking(images, mask, "separate")
         reference = (None, None) if own_basis else (self._stain_matrix, self._target_max_conc)
         engine = self._get_backend_impl()
@@ -182,9 +182,7 @@ class Macenko(NormalizerTemplate):
         without an estimate gets NaN rows, which ``apply`` with a mask treats as "copy the tile through"."""
         if self._precision == "sampled":
             raise ValueError("estimate has no approximate form: use precision='stable' or 'fast' (both run the exact kernels)")
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Macenko estimate expects NCHW images with C=3, got shape {shape}")
+        self._nchw(images, "Macenko estimate")
         masked, explicit = self._masking(images, mask, "estimate")
         engine = self._get_backend_impl()
         if masked:
@@ -236,10 +234,7 @@ class Macenko(NormalizerTemplate):
             raise ValueError("alpha and beta go together: both or neither")
         if own_basis and alpha is None:
             raise ValueError("own_basis=True rebuilds every tile in the source's own basis: it needs the factors alpha and beta")
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Macenko apply expects NCHW images with C=3, got shape {shape}")
-        n = shape[0]
+        n = self._nchw(images, "Macenko apply")[0]
         he, max_c = self._check_source(source, n, need_max_c=not own_basis)
         for name, factor in (("alpha", alpha), ("beta", beta)):
             if factor is not None and tuple(getattr(factor, "shape", ())) != (n, 2):

@@ -5,7 +5,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 from stainx_amd.normalizers._template import NormalizerTemplate
 
 STATISTICS_MODES = ("batch", "tile")
@@ -53,8 +53,7 @@ class Reinhard(NormalizerTemplate):
         """(masked call?, explicit mask or None), checked against the images before any GPU work."""
         if mask is None and self.mask is None:
             return False, None
-        n, _, h, w = self._check_images(images, what)
-        return masks.resolve(self.mask, mask, n, h, w, self.device)
+        return fe.call_mask(self.mask, mask, False, self._check_images(images, what), self.device)
 
     def fit(self, images: Any, mask: Any = None) -> "Reinhard":
         """``mask``: the reference's tissue (a tensor), for this call; a normaliser built with ``mask="luminosity"`` applies the rule."""
@@ -80,11 +79,8 @@ class Reinhard(NormalizerTemplate):
         return self._get_backend_impl().transform_tiles(images, *self.arguments())
 
     @staticmethod
-    def _check_images(images: Any, what: str) -> tuple:
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Reinhard {what} expects NCHW images with C=3, got shape {shape}")
-        return shape
+    def _check_images(images: Any, what: str) -> tuple[int, int, int]:
+        return fe.image_batch(images, False, "Reinhard", promote=False, tensor=None, refusal=f"Reinhard {what} expects NCHW images with C=3")[2]
 
     def estimate(self, images: Any, *, pooled: bool = False, mask: Any = None) -> ColorStatistics:
         """The LAB statistics of ``images`` (NCHW), without transforming them: every tile's own, (N, 3) each, in one statistics pass --
@@ -103,22 +99,6 @@ class Reinhard(NormalizerTemplate):
             return ColorStatistics(mean.reshape(1, 3), std.reshape(1, 3))
         return ColorStatistics(*engine.tile_statistics(images))
 
-    @staticmethod
-    def _check_rows(pair: Any, n: int, what: str) -> tuple:
-        if isinstance(pair, (tuple, list)) and len(pair) == 2:      # (a ColorStatistics is a tuple of two)
-            mean, std = pair
-        else:
-            raise ValueError(f"{what} must be a ColorStatistics or a (mean, std) pair")
-        shapes = []
-        for name, value in (("mean", mean), ("std", std)):
-            shape = tuple(getattr(value, "shape", ()))
-            if not (shape == (3,) or (len(shape) == 2 and shape[1] == 3 and shape[0] in (1, n))):
-                raise ValueError(f"{what} {name} must have shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
-            shapes.append(1 if len(shape) == 1 else shape[0])
-        if shapes[0] != shapes[1]:
-            raise ValueError(f"{what} mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
-        return mean, std
-
     def apply(self, images: Any, source: Any, mask: Any = None, *, target: Any = None) -> Any:
         """Normalise ``images`` (NCHW) to the fitted reference with GIVEN source statistics: one kernel launch, a pixel read and a pixel
         written (include/stainx_hip.h: sx_reinhard_apply_stats).  ``source``: a ``ColorStatistics`` or a ``(mean, std)`` pair -- (3,),
@@ -133,9 +113,9 @@ class Reinhard(NormalizerTemplate):
             raise ValueError("Must call fit() before transform()")
         n = self._check_images(images, "apply")[0]
         masked, explicit = self._masking(images, mask, "apply")
-        mean, std = self._check_rows(source, n, "source")
+        mean, std = fe.mean_std_rows(source, n, "source", "ColorStatistics", tensors=False)
         if target is not None:
-            t_mean, t_std = self._check_rows(target, n, "target")
+            t_mean, t_std = fe.mean_std_rows(target, n, "target", "ColorStatistics", tensors=False)
             if masked:
                 return self._get_backend_impl().apply_targets_masked(images, mean, std, t_mean, t_std, explicit, self.luminosity_threshold)
             return self._get_backend_impl().apply_targets(images, mean, std, t_mean, t_std)

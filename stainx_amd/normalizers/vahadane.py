@@ -8,7 +8,7 @@ from typing import Any
 
 import torch
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 from stainx_amd.normalizers.macenko import Macenko, StainEstimate, StainSeparation
 
 MAX_ITERATIONS = 1000      # sx_vahadane_estimate: iterations in 1..1000
@@ -43,19 +43,12 @@ class Vahadane(Macenko):
     # ---- checks (all before any GPU work) ---------------------------------------------------------------------
     @staticmethod
     def _check_regularizer(value: Any) -> float:
-        try:
-            number = float(value)
-        except (TypeError, ValueError):
-            raise ValueError(f"regularizer must be a finite number >= 0, got {value!r}") from None
-        if not math.isfinite(number) or number < 0.0:
-            raise ValueError(f"regularizer must be a finite number >= 0, got {value!r}")
-        return number
+        rule = "regularizer must be a finite number >= 0"
+        return fe.real_number(value, rule, rule, lambda v: math.isfinite(v) and v >= 0.0)
 
     @staticmethod
     def _check_iterations(value: Any) -> int:
-        if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= MAX_ITERATIONS:
-            raise ValueError(f"iterations must be an integer in 1..{MAX_ITERATIONS}, got {value!r}")
-        return value
+        return fe.whole_number(value, f"iterations must be an integer in 1..{MAX_ITERATIONS}", 1, MAX_ITERATIONS)
 
     @staticmethod
     def _check_init(init: Any) -> Any:
@@ -87,14 +80,10 @@ class Vahadane(Macenko):
             self._init_cache[device] = init.to(device=device, dtype=torch.float32).contiguous()
         return self._init_cache[device]
 
-    @staticmethod
-    def _check_nchw(images: Any, what: str, channel_axis: int = 1) -> tuple:
+    def _check_nchw(self, images: Any, what: str, channel_axis: int = 1) -> tuple[int, int, int]:
         if channel_axis not in (1, -3):
             raise ValueError(f"Vahadane {what} takes planar NCHW images only (channel_axis=1), got channel_axis={channel_axis}")
-        shape = tuple(getattr(images, "shape", ()))
-        if len(shape) != 4 or shape[1] != 3:
-            raise ValueError(f"Vahadane {what} expects NCHW images with C=3, got shape {shape}")
-        return shape
+        return self._nchw(images, f"Vahadane {what}")
 
     def _dense_mask(self, engine, images: torch.Tensor, masked: bool, explicit: Any, luminosity_threshold: float) -> Any:
         """The mask of a masked call as ONE tensor for the calls that follow (the rule is evaluated once); None when unmasked."""

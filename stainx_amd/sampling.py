@@ -17,7 +17,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from stainx_amd import masks
+from stainx_amd import _frontend as fe, masks
 
 MAX_SAMPLE_SIZE = 1 << 24      # include/stainx_hip.h: sample_size
 MAX_GROUP_PIXELS = (1 << 31) - 1
@@ -89,10 +89,8 @@ def sample_pixels(images: torch.Tensor, size: Any, *, mask: Any = None, luminosi
     A slide: ``PixelSample.cat(*(sample_pixels(b, (64, 64), mask=otsu_mask(b).mask, pooled=True) for b in batches))``, then
     ``normaliser.estimate(s.pixels, pooled=True, mask=s.valid)`` once and ``apply`` per batch."""
     height, width = _check_size(size)
-    if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset < 1 << 63:
-        raise ValueError(f"offset must be an int in 0 .. 2^63 - 1, got {offset!r}")
-    last = masks._check_images(images, channel_axis, "sample_pixels")
-    n, h, w = (images.shape[0], images.shape[1], images.shape[2]) if last else (images.shape[0], images.shape[2], images.shape[3])
+    fe.whole_number(offset, "offset must be an int in 0 .. 2^63 - 1", 0, (1 << 63) - 1)
+    last, (n, h, w) = fe.image_4d(images, channel_axis, "sample_pixels")
     if images.dtype not in (torch.uint8, torch.float16, torch.bfloat16, torch.float32, torch.float64):
         raise ValueError(f"sample_pixels: unsupported image dtype {images.dtype}")
     if h * w * (n if pooled else 1) > MAX_GROUP_PIXELS:

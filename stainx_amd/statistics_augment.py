@@ -15,8 +15,8 @@ from typing import Any, NamedTuple
 import torch
 import torch.nn as nn
 
-from stainx_amd import masks
-from stainx_amd.deconv import ColorDeconvolution, ConcentrationStatistics, _cuda_device, check_gain_range
+from stainx_amd import _frontend as fe, masks
+from stainx_amd.deconv import ColorDeconvolution, ConcentrationStatistics, check_gain_range
 from stainx_amd.normalizers.reinhard import ColorStatistics, Reinhard
 
 SPACES = ("lab", "hed")
@@ -77,20 +77,6 @@ def _check_distribution(distribution: Any) -> StatisticsDistribution:
     return StatisticsDistribution(*fields)
 
 
-def _check_targets(targets: Any, n: int) -> tuple[torch.Tensor, torch.Tensor]:
-    if not isinstance(targets, (tuple, list)) or len(targets) != 2:
-        raise ValueError("targets must be a ColorStatistics or a (mean, std) pair")
-    shapes = []
-    for name, t in (("mean", targets[0]), ("std", targets[1])):
-        shape = tuple(getattr(t, "shape", ()))
-        if not isinstance(t, torch.Tensor) or not (shape == (3,) or (len(shape) == 2 and shape[1] == 3 and shape[0] in (1, n))):
-            raise ValueError(f"targets {name} must be a tensor of shape (3,), (1, 3) or (N, 3) = ({n}, 3), got {shape}")
-        shapes.append(1 if len(shape) == 1 else shape[0])
-    if shapes[0] != shapes[1]:
-        raise ValueError(f"targets mean and std must have the same number of rows, got {shapes[0]} and {shapes[1]}")
-    return targets[0], targets[1]
-
-
 class StatisticsAugment(nn.Module):
     """Random per-tile statistics matching of CHW / NCHW tensors on an MI355X (RandStainNA): every tile is moved from its own channel
     statistics to a target drawn from ``distribution``.
@@ -132,31 +118,15 @@ class StatisticsAugment(nn.Module):
         self.luminosity_threshold = masks.check_threshold(luminosity_threshold)
         self.normalize_to_0_1 = bool(normalize_to_0_1)
         self.generator = generator
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != "cuda":
-            raise ValueError(f"StatisticsAugment runs on a CUDA (ROCm) device, got {self.device}")
+        self.device = fe.cuda_only(device, "StatisticsAugment")
         # (`basis` and `normalize_to_0_1` belong to the HED space: the LAB space builds no deconvolution and does not look at them)
         self.deconv = None if space == "lab" else ColorDeconvolution(basis, device=device, normalize_to_0_1=self.normalize_to_0_1, mask=mask,
                                                                      luminosity_threshold=luminosity_threshold)
         self._reinhards: dict[torch.device, Reinhard] = {}
         self._fields: dict[torch.device, StatisticsDistribution] = {}      # (the distribution on a device: uploaded once)
 
-    @staticmethod
-    def _batch(img: Any) -> tuple[torch.Tensor, bool]:
-        if not isinstance(img, torch.Tensor):
-            raise ValueError(f"StatisticsAugment expects a tensor, got {type(img).__name__}")
-        single = img.dim() == 3
-        if single:
-            img = img.unsqueeze(0)
-        if img.dim() != 4 or img.shape[1] != 3:
-            raise ValueError(f"StatisticsAugment expects CHW / NCHW tensors with C=3, got shape {tuple(img.shape)}")
-        return img, single
-
     def _reinhard(self, device: torch.device) -> Reinhard:
-        held = self._reinhards.get(device)
-        if held is None:
-            held = self._reinhards[device] = Reinhard(device=device, backend="torch_hip", statistics="tile", mask=self.mask, luminosity_threshold=self.luminosity_threshold)
-        return held
+        return Reinhard(device=device, backend="torch_hip", statistics="tile", mask=self.mask, luminosity_threshold=self.luminosity_threshold)
 
     def sample_targets(self, n: int, device: str | torch.device | None = None, *, own: Any = None) -> tuple[torch.Tensor, torch.Tensor]:
         """``(target_mean, target_std)``, each (n, 3) float32 on ``device``, drawn with the module's generator (on the generator's
@@ -165,28 +135,25 @@ class StatisticsAugment(nn.Module):
         (``"uniform"``) --, then ``target_mean = mean_center + spread_scale * mean_spread * z[0]``, ``target_std = std_center +
         spread_scale * std_spread * z[1]``; zero spreads give the centres exactly.  With ``p < 1`` a ``rand(n) < p`` follows: a tile not
         selected gets row t of ``own = (mean, std)`` -- its own statistics, (n, 3) each -- which is then required."""
-        device = torch.device(device) if device is not None else (self.device or torch.device("cpu"))
+        device = fe.draw_device(device, self.device)
         if self.p < 1.0:
             if not isinstance(own, (tuple, list)) or len(own) != 2 or any(tuple(getattr(t, "shape", ())) != (n, 3) for t in own):
                 raise ValueError(f"sample_targets with p < 1 needs own=(mean, std), the tiles' own statistics of shape ({n}, 3) each")
-        draw_on = self.generator.device if self.generator is not None else device
-        if self.kind == "normal":
-            z = torch.randn((2, n, 3), generator=self.generator, device=draw_on, dtype=torch.float32)
+        if self.kind == "normal":      # (the law is computed where the draw was made, and then moved)
+            z = fe.draw(self.generator, (2, n, 3), device, "randn")
         else:
-            r = torch.rand((2, n, 3), generator=self.generator, device=draw_on, dtype=torch.float32)
+            r = fe.draw(self.generator, (2, n, 3), device)
             if self.kind == "uniform":
                 z = 2.0 * r - 1.0
             else:
                 u = r - 0.5
                 z = -torch.sign(u) * torch.log(torch.clamp(1.0 - 2.0 * torch.abs(u), min=torch.finfo(torch.float32).tiny))
         z = z.to(device)
-        held = self._fields.get(device)
-        if held is None:
-            held = self._fields[device] = StatisticsDistribution(*(t.to(device) for t in self.distribution))
+        held = fe.held(self._fields, device, lambda device: StatisticsDistribution(*(t.to(device) for t in self.distribution)))
         target_mean = held.mean_center + (self.spread_scale * held.mean_spread) * z[0]
         target_std = held.std_center + (self.spread_scale * held.std_spread) * z[1]
         if self.p < 1.0:
-            chosen = (torch.rand((n,), generator=self.generator, device=draw_on, dtype=torch.float32) < self.p).to(device).unsqueeze(-1)
+            chosen = fe.chosen(self.generator, n, self.p, device)
             target_mean = torch.where(chosen, target_mean, own[0].to(device, torch.float32))
             target_std = torch.where(chosen, target_std, own[1].to(device, torch.float32))
         return target_mean, target_std
@@ -194,17 +161,14 @@ class StatisticsAugment(nn.Module):
     def forward(self, img: torch.Tensor, targets: Any = None, mask: Any = None) -> torch.Tensor:
         """``targets``: an explicit ``(mean, std)`` pair -- (3,), (1, 3) or (N, 3) each, in the module's space -- instead of the draw.
         ``mask``: an explicit uint8 / bool tensor (N, H, W) or (N, 1, H, W) on the device, or ``"luminosity"``, for this call."""
-        batch, single = self._batch(img)
-        n, _, h, w = batch.shape
+        batch, single, (n, h, w) = fe.image_batch(img, False, "StatisticsAugment")
         if targets is not None:
-            targets = _check_targets(targets, n)
-        if single and isinstance(mask, torch.Tensor) and mask.dim() == 2:
-            mask = mask.unsqueeze(0)
-        masked, explicit = masks.resolve(self.mask, mask, n, h, w, self.device if self.device is not None else batch.device)
-        device = _cuda_device(self.device, batch.device, "StatisticsAugment")
+            targets = fe.mean_std_rows(targets, n, "targets", "ColorStatistics")
+        masked, explicit = fe.call_mask(self.mask, mask, single, (n, h, w), self.device or batch.device)
+        device = fe.run_device(self.device, batch.device, "StatisticsAugment")
         batch = batch.to(device)
         if self.space == "lab":
-            reinhard = self._reinhard(device)
+            reinhard = fe.held(self._reinhards, device, self._reinhard)
             call_mask = explicit if explicit is not None else ("luminosity" if masked else None)
             own = reinhard.estimate(batch, mask=call_mask)
             if targets is None:

@@ -1,5 +1,5 @@
-"""Host time of the Python binding per call: the microseconds a call of stainx_amd/backends/torch_hip_backend.py spends before it
-returns, for comparing two versions of the binding on the same shared objects.
+"""Host time of the Python layers per call: the microseconds a call of the binding (stainx_amd/backends/torch_hip_backend.py) or of a public
+front end above it spends before it returns, for comparing two versions of either layer on the same shared objects.
     PYTHONPATH=<checkout> python tools/binding_host_time.py --out FILE.json [--blocks 40] [--calls 250]
     python tools/binding_host_time.py --table PARENT1.json AFTER1.json PARENT2.json AFTER2.json [PARENT3.json AFTER3.json ...]
 Every case makes blocks of back-to-back calls at 2 x 3 x 48 x 48 (the device keeps up at that size: the clock sees the enqueue), one
@@ -12,6 +12,7 @@ import torch
 
 
 def cases(dev):
+    import stainx_amd as sx
     from stainx_amd import distributed as sxd, synth
     from stainx_amd.backends import torch_hip_backend as B
 
@@ -26,6 +27,13 @@ def cases(dev):
     rows_mean, rows_std = mean.expand(2, 3).contiguous(), std.expand(2, 3).contiguous()
     hist = hm.compute_reference_histograms(u8)
     tables = (torch.arange(256, dtype=torch.float32, device=dev) / 255).repeat(1, 3, 1).contiguous()
+    def gen():
+        return torch.Generator(device=dev).manual_seed(1)      # (on the device: a draw enqueues no host copy)
+
+    distribution = sx.StatisticsDistribution(mean, std / 4, std, std / 4)
+    deconv, hed_aug, hsv_aug, mac_aug = sx.ColorDeconvolution("hed"), sx.HEDAugment(generator=gen()), sx.HSVAugment(generator=gen()), sx.MacenkoAugment(generator=gen())
+    stat_aug, lum = sx.StatisticsAugment(distribution, "lab", generator=gen()), sx.LuminosityStandardizer()
+    reinhard, matching = sx.Reinhard(device=dev).fit(u8), sx.HistogramMatching(device=dev).fit(u8)
     return {
         "MacenkoHIP.transform uint8": lambda: mac.transform(u8, he, max_c),
         "MacenkoHIP.transform float32": lambda: mac.transform(f32, he, max_c),
@@ -38,6 +46,18 @@ def cases(dev):
         "HistogramMatchingHIP.apply_tables": lambda: hm.apply_tables(u8, tables),
         "tissue_mask_native": lambda: B.tissue_mask_native(u8, 0.8, False),
         "pooled fit_transform step (distributed, one rank)": lambda: sxd.macenko_fit_transform_pooled(f32, steps=mac),
+        # the front ends: their own checks in front of the binding's call(s)
+        "ColorDeconvolution.apply": lambda: deconv.apply(u8),
+        "HEDAugment": lambda: hed_aug(u8),
+        "HSVAugment": lambda: hsv_aug(u8),
+        "MacenkoAugment": lambda: mac_aug(u8),
+        "StatisticsAugment (lab)": lambda: stat_aug(u8),
+        "LuminosityStandardizer": lambda: lum(u8),
+        "Reinhard.apply": lambda: reinhard.apply(u8, (rows_mean, rows_std)),
+        "HistogramMatching.apply": lambda: matching.apply(u8, tables),
+        "tissue_mask": lambda: sx.tissue_mask(u8),
+        "focus_statistics": lambda: sx.focus_statistics(u8),
+        "sample_pixels": lambda: sx.sample_pixels(u8, 64),
     }
 
 
