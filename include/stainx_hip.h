@@ -417,6 +417,34 @@ int sx_hsv_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_til
 int sx_hsv_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                         const float* rows_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- Gaussian blur with a sigma per tile (the blur of Tellez et al.'s augmentation set; the other half of the focus measurement) ----
+ * An extension: the reference has none.  One float32 sigma per tile; each channel plane is filtered on its own, a pixel never sees
+ * another tile.
+ *   sigmas_dev n_rows floats; n_rows is 1 (one sigma for the batch) or n_tiles (sigma t serves tile t).
+ *   Radius     R = min((int)(4 sigma + 0.5), 16) of the float32 sigma, the sum taken exactly (scipy.ndimage.gaussian_filter, truncate = 4.0:
+ *              R = 0 for every sigma below 0.125).  SX_BLUR_MAX_SIGMA = 4:
+ *              a larger finite sigma is clamped to 4 (the rows are device memory: nothing is refused).
+ *   Taps       w_i = exp(-i^2 / (2 sigma^2)), i = -R..R, divided by their sum, in float32: all positive, a convex combination.
+ *   Borders    reflected without repeating the edge inside the pixel's own tile, folded as often as needed (period 2 (n - 1); an axis of
+ *              length 1 maps to 0): scipy's mode="mirror", torch's "reflect" padding.
+ *   Arithmetic separable, rows then columns, float32, on the values as the element type stores them: a uint8 byte is its level, a float
+ *              element is taken as it is (no x 255: the filter is linear).  Per pass acc = w_0 x_0, then acc = fma(w_i, x_-i + x_+i, acc).
+ * Output: the result through sx_macenko_transform's output rule (the cast; SX_MACENKO_NORMALIZE_0_1 fuses / 255; uint8 input may ask for
+ * SX_MACENKO_OUT_BF16 / _OUT_F16).  An 8-bit level is ROUNDED TO NEAREST, as in sx_hsv_apply: a blur that changes nothing returns the tile.
+ * Copies: a tile whose sigma is NaN, infinite or <= 0, or whose R is 0 (sigma < 0.125), is copied -- the stored element through the output
+ * rule, no clamp; where the output element is the input element and nothing is divided, the element's bits (NaN payloads, -0.0).
+ * Non-finite pixels are not special: a NaN pixel spreads over its (2 R + 1)^2 window as IEEE arithmetic takes it, and over nothing else.
+ * Each call is ONE kernel launch on `stream`: nothing else enqueued, no workspace, no host synchronisation, capturable; neither pass goes
+ * through device memory.  Sigmas and masks are DEVICE memory read by the kernel.  Flags and argument errors as sx_hsv_apply. */
+#define SX_BLUR_MAX_SIGMA 4.0f
+int sx_gaussian_blur(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                     const float* sigmas_dev, int64_t n_rows, unsigned flags, void* stream);
+/* sx_gaussian_blur_masked: the same under an explicit mask (N, H, W), one byte per pixel, non-zero = in; planar tiles only.  The mask
+ * selects which OUTPUT pixels are written from the blur -- a masked-out pixel is copied --; the taps read every pixel and the weights are
+ * not renormalised.  All ones: sx_gaussian_blur's bits. */
+int sx_gaussian_blur_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                            const float* sigmas_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

@@ -84,6 +84,9 @@ SIGNATURES = {
     # HSV colour jitter: rows of (dh, a_s, b_s, a_v, b_v) per tile in device memory, one launch
     "sx_hsv_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_hsv_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
+    # Gaussian blur: one float32 sigma per tile in device memory, one launch, both passes on chip
+    "sx_gaussian_blur": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
+    "sx_gaussian_blur_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

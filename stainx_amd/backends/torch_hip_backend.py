@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,8 +58,8 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
-        if family == "HSV":
-            raise ValueError(f"HSV {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
+        if family in ("HSV", "Gaussian blur"):
+            raise ValueError(f"{family} {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
         if len(shape) != 4:
@@ -134,6 +134,14 @@ def _hsv_rows(rows: torch.Tensor, n: int) -> int:
     if isinstance(rows, torch.Tensor) and len(shape) == 2 and shape[1] == 5 and shape[0] in (1, n):
         return shape[0]
     raise ValueError(f"rows must be a tensor of shape (5,), (1, 5) or (N, 5) = ({n}, 5) holding (dh, a_s, b_s, a_v, b_v), got {shape}")
+
+
+def _sigma_rows(sigmas: torch.Tensor, n: int) -> int:
+    """Sigmas of a Gaussian blur, (), (1,) or (N,): the number of rows, 1 or N."""
+    shape = tuple(getattr(sigmas, "shape", (-1, -1)))
+    if isinstance(sigmas, torch.Tensor) and (shape == () or (len(shape) == 1 and shape[0] in (1, n))):
+        return 1 if shape == () else shape[0]
+    raise ValueError(f"sigma must be a number or a tensor of shape (), (1,) or (N,) = ({n},), got {shape}")
 
 
 def _statistics_rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str, accepted: str = "(3,), (1, 3)") -> tuple[torch.Tensor, torch.Tensor]:
@@ -1238,6 +1246,33 @@ class HsvHIP(TorchHIPBackendBase):
                 self._call("sx_hsv_apply", images, out, code, n, h, w, r, n_rows, flags)
             else:
                 self._call("sx_hsv_apply_masked", images, out, code, n, h, w, r, n_rows, self._mask_for(images, *masking), flags)
+        return out
+
+
+class BlurHIP(TorchHIPBackendBase):
+    """Gaussian blur with a sigma per tile (include/stainx_hip.h: sx_gaussian_blur): one kernel launch per call, both passes on chip, no
+    workspace, no host synchronisation.  Sigmas and masks are read on the device: a captured call replayed after new sigmas are copied
+    into the same tensor uses the new sigmas."""
+
+    def apply(self, images: torch.Tensor, sigmas: torch.Tensor, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False,
+              masking: tuple | None = None) -> torch.Tensor:
+        """``sigmas``: (), (1,) or (N,) floats; a sigma that is NaN, infinite, ``<= 0`` or below 0.125 leaves its tile as it is, one above
+        4 is 4.  ``masking``: None, or ``(explicit mask or None, luminosity threshold)`` -- the masked call (planar tiles only); the
+        rule's mask is an ``sx_tissue_mask`` launch in front."""
+        if masking is not None and channels_last:
+            raise ValueError("a masked Gaussian blur takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "Gaussian blur", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _sigma_rows(sigmas, n)
+        s = self._f32(sigmas)
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n * h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            if masking is None:
+                self._call("sx_gaussian_blur", images, out, code, n, h, w, s, n_rows, flags)
+            else:
+                self._call("sx_gaussian_blur_masked", images, out, code, n, h, w, s, n_rows, self._mask_for(images, *masking), flags)
         return out
 
 

@@ -5230,5 +5230,8 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 // HSV colour jitter, per-tile hue / saturation / value rows (sx_hsv_apply, sx_hsv_apply_masked): one streaming kernel on the same helpers.
 #include "hsv.hpp"
 
+// Gaussian blur with a sigma per tile (sx_gaussian_blur, sx_gaussian_blur_masked): one launch, both passes on chip, on the same helpers.
+#include "blur.hpp"
+
 // Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
 #include "vahadane.hpp"
