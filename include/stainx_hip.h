@@ -445,6 +445,47 @@ int sx_gaussian_blur(const void* images_dev, void* out_dev, int dtype, int64_t n
 int sx_gaussian_blur_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                             const float* sigmas_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- Affine warp with a row per tile (the geometric half of Tellez et al.'s augmentation set: quarter turns, flips, rotation, scale,
+ * shear, translation; crop, pad and resize in the same launch) ----
+ * An extension: the reference has none.  The source tile is height x width, the output tile out_height x out_width.
+ *   rows_dev   n_rows x 6 floats (a, b, c, d, e, f); n_rows is 1 (one row for the batch) or n_tiles (row t serves tile t).  The row maps
+ *              an OUTPUT pixel to the SOURCE position, pixel centres at integers (scipy.ndimage.affine_transform, cv2.warpAffine with
+ *              WARP_INVERSE_MAP, grid_sample(align_corners=True) un-normalised): for output column x and row y, in float32,
+ *              sx = fmaf(a, x, fmaf(b, y, c)),  sy = fmaf(d, x, fmaf(e, y, f)).
+ *   Anchor     a row with a NaN or an infinity means "leave this tile": it is replaced by (1, 0, (W - OW) div 2, 0, 1, (H - OH) div 2),
+ *              floor division -- a copy where the sizes are equal, else the centre crop, or the centre pad by the border rule.
+ *   Limit      a coordinate that is not finite or exceeds SX_WARP_MAX_COORD = 2^22 in magnitude makes the pixel `fill`, in both border
+ *              modes (tested in float32 before any integer is formed).  No value of a row makes the kernel read outside the tile.
+ *   Borders    SX_WARP_MIRROR: reflected without repeating the edge inside the tile, folded as often as needed (period 2 (n - 1), an
+ *              axis of length 1 maps to 0): scipy's "mirror", torch's "reflection" with align_corners=True.  SX_WARP_CONSTANT: a tap
+ *              outside the tile is `fill` (scipy's "grid-constant", cv2's BORDER_CONSTANT).  `fill`: a finite float32 on the element's
+ *              own scale -- a level for uint8 tiles (clamped to 0..255), taken as it is for float tiles --, through the output rule.
+ *   Bilinear   x0 = floorf(sx), fx = sx - x0, y0 and fy likewise; the four taps through the border rule, as the element type stores
+ *              them (a uint8 byte is its level, a float element as it is; no x 255):
+ *              top = fmaf(fx, v01 - v00, v00), bot = fmaf(fx, v11 - v10, v10), v = fmaf(fy, bot - top, top).  fx == 0 and fy == 0:
+ *              the stored element, copied.  Non-finite pixels are not special.
+ *   Nearest    xi = floorf(sx + 0.5f), yi likewise (scipy's order=0): the stored element at (xi, yi) through the border rule, copied.
+ * Output: sx_gaussian_blur's rule (an 8-bit level ROUNDED TO NEAREST; SX_MACENKO_NORMALIZE_0_1; SX_MACENKO_OUT_BF16 / _OUT_F16 for
+ * uint8 input); a copied element keeps its bits where the output element is the input element and nothing is divided (NaN payloads,
+ * -0.0).  out_dev MUST NOT overlap images_dev.
+ * Each call is ONE kernel launch on `stream`: nothing else enqueued, no workspace, no host synchronisation, capturable.  Rows are DEVICE
+ * memory read by the kernel.  Flags as sx_gaussian_blur.  Argument errors, in this order and before anything is enqueued: null pointers,
+ * sizes not positive, N*H*W or N*OH*OW at or above 2^32, n_rows, interpolation / border, fill, flags, dtype. */
+#define SX_WARP_NEAREST 0
+#define SX_WARP_BILINEAR 1
+#define SX_WARP_MIRROR 0
+#define SX_WARP_CONSTANT 1
+#define SX_WARP_MAX_COORD 4194304.0f
+int sx_affine_warp(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                   int64_t out_height, int64_t out_width, const float* rows_dev, int64_t n_rows,
+                   int interpolation, int border, float fill, unsigned flags, void* stream);
+/* sx_affine_warp_mask: a mask (N, H, W), one byte per pixel, warped WITH its tile -- it does not select pixels --: nearest, bytes moved
+ * as bytes (labels 0..255 survive), SX_WARP_MIRROR or SX_WARP_CONSTANT with the byte `fill` (0..255).  The nearest sx_affine_warp of
+ * the same plane and rows gives the same bytes: an image and its mask warped by the same rows stay aligned. */
+int sx_affine_warp_mask(const unsigned char* mask_dev, unsigned char* out_dev, int64_t n_tiles, int64_t height, int64_t width,
+                        int64_t out_height, int64_t out_width, const float* rows_dev, int64_t n_rows,
+                        int border, int fill, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

@@ -42,6 +42,9 @@ MORPH_MAX_RADIUS = 31
 CONNECTIVITIES = (4, 8)      # sx_mask_components, sx_mask_area_filter
 MEDIAN_MAX_SIZE = 15         # sx_median_filter_u8: SX_MEDIAN_MAX_SIZE
 MAX_SAMPLE_SIZE = 1 << 24    # sx_sample_pixels: sample_size
+WARP_INTERPOLATIONS = {"nearest": 0, "bilinear": 1}      # sx_affine_warp: SX_WARP_NEAREST / _BILINEAR, SX_WARP_MIRROR / _CONSTANT, SX_WARP_MAX_COORD
+WARP_BORDERS = {"mirror": 0, "constant": 1}
+WARP_MAX_COORD = 4194304.0
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -87,6 +90,9 @@ SIGNATURES = {
     # Gaussian blur: one float32 sigma per tile in device memory, one launch, both passes on chip
     "sx_gaussian_blur": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_gaussian_blur_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
+    # affine warp: one row of six floats per tile in device memory, one launch; the mask warped with its tile
+    "sx_affine_warp": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _c.c_float, _uint, _vp]),
+    "sx_affine_warp_mask": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

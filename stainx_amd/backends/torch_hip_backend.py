@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_warp_rows``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,7 +58,7 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
-        if family in ("HSV", "Gaussian blur"):
+        if family in ("HSV", "Gaussian blur", "affine warp"):
             raise ValueError(f"{family} {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
@@ -142,6 +142,16 @@ def _sigma_rows(sigmas: torch.Tensor, n: int) -> int:
     if isinstance(sigmas, torch.Tensor) and (shape == () or (len(shape) == 1 and shape[0] in (1, n))):
         return 1 if shape == () else shape[0]
     raise ValueError(f"sigma must be a number or a tensor of shape (), (1,) or (N,) = ({n},), got {shape}")
+
+
+def _warp_rows(rows: torch.Tensor, n: int) -> int:
+    """Rows of an affine warp, (6,), (1, 6) or (N, 6): the number of rows, 1 or N."""
+    shape = tuple(getattr(rows, "shape", ()))
+    if isinstance(rows, torch.Tensor) and shape == (6,):
+        return 1
+    if isinstance(rows, torch.Tensor) and len(shape) == 2 and shape[1] == 6 and shape[0] in (1, n):
+        return shape[0]
+    raise ValueError(f"rows must be a tensor of shape (6,), (1, 6) or (N, 6) = ({n}, 6) holding (a, b, c, d, e, f), got {shape}")
 
 
 def _statistics_rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str, accepted: str = "(3,), (1, 3)") -> tuple[torch.Tensor, torch.Tensor]:
@@ -1273,6 +1283,42 @@ class BlurHIP(TorchHIPBackendBase):
                 self._call("sx_gaussian_blur", images, out, code, n, h, w, s, n_rows, flags)
             else:
                 self._call("sx_gaussian_blur_masked", images, out, code, n, h, w, s, n_rows, self._mask_for(images, *masking), flags)
+        return out
+
+
+class WarpHIP(TorchHIPBackendBase):
+    """Affine warp with a row per tile (include/stainx_hip.h: sx_affine_warp, sx_affine_warp_mask): one kernel launch per call, no
+    workspace, no host synchronisation.  Rows are read on the device: a captured call replayed after new rows are copied into the same
+    tensor uses the new rows."""
+
+    def apply(self, images: torch.Tensor, rows: torch.Tensor, size: tuple[int, int] | None = None, *, interpolation: str = "bilinear", border: str = "mirror", fill: float = 0.0,
+              normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False) -> torch.Tensor:
+        """``rows``: (6,), (1, 6) or (N, 6) floats, output pixel -> source position; a row with a NaN or an infinity leaves its tile
+        (copy, centre crop or centre pad).  ``size``: (OH, OW) of the result, default the input's."""
+        images, n, h, w, code = self._images(images, channels_last, "affine warp", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _warp_rows(rows, n)
+        oh, ow = (h, w) if size is None else size
+        r = self._f32(rows)
+        out = torch.empty((n, oh, ow, 3) if channels_last else (n, 3, oh, ow), dtype=out_dtype, device=self.device)
+        if n * h * w == 0 or oh * ow == 0:
+            return out
+        with _native.on_device(self.device):
+            self._call("sx_affine_warp", images, out, code, n, h, w, oh, ow, r, n_rows, _native.WARP_INTERPOLATIONS[interpolation], _native.WARP_BORDERS[border], float(fill), flags)
+        return out
+
+    def apply_mask(self, mask: torch.Tensor, rows: torch.Tensor, size: tuple[int, int] | None = None, *, border: str = "constant", fill: int = 0) -> torch.Tensor:
+        """``mask``: dense uint8 (N, H, W) -> uint8 (N, OH, OW): nearest, bytes moved as bytes."""
+        mask = _mask_bytes(mask, self.device)
+        n, h, w = mask.shape
+        n_rows = _warp_rows(rows, n)
+        oh, ow = (h, w) if size is None else size
+        r = self._f32(rows)
+        out = torch.empty((n, oh, ow), dtype=torch.uint8, device=self.device)
+        if n * h * w == 0 or oh * ow == 0:
+            return out
+        with _native.on_device(self.device):
+            self._call("sx_affine_warp_mask", mask, out, n, h, w, oh, ow, r, n_rows, _native.WARP_BORDERS[border], int(fill))
         return out
 
 

@@ -5233,5 +5233,8 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 // Gaussian blur with a sigma per tile (sx_gaussian_blur, sx_gaussian_blur_masked): one launch, both passes on chip, on the same helpers.
 #include "blur.hpp"
 
+// Affine warp with a row per tile (sx_affine_warp, sx_affine_warp_mask): one launch, a gather through the vector cache, on the same helpers.
+#include "warp.hpp"
+
 // Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
 #include "vahadane.hpp"
