@@ -486,6 +486,36 @@ int sx_affine_warp_mask(const unsigned char* mask_dev, unsigned char* out_dev, i
                         int64_t out_height, int64_t out_width, const float* rows_dev, int64_t n_rows,
                         int border, int fill, void* stream);
 
+/* ---- Elastic deformation with a control grid per tile (the other half of Tellez et al.'s "morphology" set), fused with the affine
+ * warp: scale, rotation, elastic deformation and the crop are ONE launch ----
+ * An extension: the reference has none.  Everything of sx_affine_warp holds; the coordinate alone gains a displacement.
+ *   grids_dev  n_grids x 2 x GH x GW floats, n_grids 1 (one grid for the batch) or n_tiles: plane 0 holds dx, plane 1 dy, in SOURCE
+ *              pixels.  GH = (out_height - 1) div cell + 4, GW = (out_width - 1) div cell + 4; control column j sits at output column
+ *              (j - 1) * cell, rows likewise.
+ *   cell       the control spacing in OUTPUT pixels, SX_ELASTIC_MIN_CELL (4) .. SX_ELASTIC_MAX_CELL (4096), one for the batch.
+ *   Displacement  for output pixel (x, y): jx = x div cell, tx = float(x - jx * cell) / float(cell), jy and ty likewise; with the
+ *              uniform cubic B-spline weights B0 = (1 - t)^3 / 6, B1 = (3 t^3 - 6 t^2 + 4) / 6, B2 = (-3 t^3 + 3 t^2 + 3 t + 1) / 6,
+ *              B3 = t^3 / 6:  dx = sum_l B_l(ty) * (sum_k B_k(tx) * P0[jy + l][jx + k]), dy from plane 1 -- float32, the x pass first,
+ *              every operation as stainx_amd/csrc/elastic.hpp writes it out.
+ *   Coordinates   sx = fmaf(a, x, fmaf(b, y, c)) + dx,  sy = fmaf(d, x, fmaf(e, y, f)) + dy; then sx_affine_warp's rule: a coordinate
+ *              that is not finite or beyond SX_WARP_MAX_COORD (a NaN, an infinite or a huge displacement) gives `fill`.
+ *   A row with a NaN or an infinity leaves its tile as in sx_affine_warp (copy, centre crop, centre pad); its grid is not read.
+ *   A grid of zeros gives sx_affine_warp's output bit for bit.  No grid and no row makes the kernel read outside the tile or the grid.
+ * ONE kernel launch on `stream`, nothing else enqueued, no workspace, capturable; rows and grids are DEVICE memory read by the kernel.
+ * Argument errors as sx_affine_warp's, with a null grids_dev, n_grids and cell after interpolation / border and before fill. */
+#define SX_ELASTIC_MIN_CELL 4
+#define SX_ELASTIC_MAX_CELL 4096
+int sx_elastic_warp(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                    int64_t out_height, int64_t out_width, const float* rows_dev, int64_t n_rows,
+                    const float* grids_dev, int64_t n_grids, int cell,
+                    int interpolation, int border, float fill, unsigned flags, void* stream);
+/* sx_elastic_warp_mask: the mask (N, H, W) warped WITH its tile, as sx_affine_warp_mask: nearest, bytes moved as bytes, the same
+ * coordinates as the nearest sx_elastic_warp of the same rows and grids. */
+int sx_elastic_warp_mask(const unsigned char* mask_dev, unsigned char* out_dev, int64_t n_tiles, int64_t height, int64_t width,
+                         int64_t out_height, int64_t out_width, const float* rows_dev, int64_t n_rows,
+                         const float* grids_dev, int64_t n_grids, int cell,
+                         int border, int fill, void* stream);
+
 /* Per-tile intermediates of the LAST sx_macenko_transform / sx_macenko_augment / sx_macenko_separate / sx_macenko_fit that used `workspace_dev`
  * (tests compare them with the oracle).  params_out_dev: n_groups x SX_MACENKO_PARAM_FLOATS floats:
  *   [0] n_selected  [1] used_all_pixels  [2..7] plane vectors (3,2)  [8] phi_lo  [9] phi_hi

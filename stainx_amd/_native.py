@@ -45,6 +45,7 @@ MAX_SAMPLE_SIZE = 1 << 24    # sx_sample_pixels: sample_size
 WARP_INTERPOLATIONS = {"nearest": 0, "bilinear": 1}      # sx_affine_warp: SX_WARP_NEAREST / _BILINEAR, SX_WARP_MIRROR / _CONSTANT, SX_WARP_MAX_COORD
 WARP_BORDERS = {"mirror": 0, "constant": 1}
 WARP_MAX_COORD = 4194304.0
+ELASTIC_MIN_CELL, ELASTIC_MAX_CELL = 4, 4096      # sx_elastic_warp: SX_ELASTIC_MIN_CELL / _MAX_CELL
 
 DTYPE_CODES = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3, torch.float64: 4}
 
@@ -93,6 +94,9 @@ SIGNATURES = {
     # affine warp: one row of six floats per tile in device memory, one launch; the mask warped with its tile
     "sx_affine_warp": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _c.c_float, _uint, _vp]),
     "sx_affine_warp_mask": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _vp]),
+    # elastic deformation: the affine row and a control grid (2, GH, GW) per tile in device memory, one launch; the mask warped with its tile
+    "sx_elastic_warp": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _int, _int, _c.c_float, _uint, _vp]),
+    "sx_elastic_warp_mask": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _int, _int, _vp]),
     "sx_macenko_tile_params": (_int, [_vp, _i64, _vp, _vp]),
     "sx_macenko_telemetry_offset": (_sz, []),
     "sx_macenko_takes_two_pass": (_int, [_int, _i64, _i64, _i64, _uint]),

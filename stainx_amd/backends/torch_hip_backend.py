@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_warp_rows``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_warp_rows``, ``_elastic_grids``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,7 +58,7 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
-        if family in ("HSV", "Gaussian blur", "affine warp"):
+        if family in ("HSV", "Gaussian blur", "affine warp", "elastic warp"):
             raise ValueError(f"{family} {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
@@ -152,6 +152,21 @@ def _warp_rows(rows: torch.Tensor, n: int) -> int:
     if isinstance(rows, torch.Tensor) and len(shape) == 2 and shape[1] == 6 and shape[0] in (1, n):
         return shape[0]
     raise ValueError(f"rows must be a tensor of shape (6,), (1, 6) or (N, 6) = ({n}, 6) holding (a, b, c, d, e, f), got {shape}")
+
+
+def _elastic_grids(grids: torch.Tensor, n: int, oh: int, ow: int, cell: int) -> int:
+    """Control grids of an elastic warp, (2, GH, GW), (1, 2, GH, GW) or (N, 2, GH, GW) for the output size and ``cell``: the number of
+    grids, 1 or N."""
+    if not isinstance(cell, int) or isinstance(cell, bool) or not _native.ELASTIC_MIN_CELL <= cell <= _native.ELASTIC_MAX_CELL:
+        raise ValueError(f"cell must be an int in {_native.ELASTIC_MIN_CELL}..{_native.ELASTIC_MAX_CELL}, got {cell!r}")
+    want = (2, (oh - 1) // cell + 4, (ow - 1) // cell + 4)
+    shape = tuple(getattr(grids, "shape", ()))
+    if isinstance(grids, torch.Tensor) and shape == want:
+        return 1
+    if isinstance(grids, torch.Tensor) and len(shape) == 4 and shape[1:] == want and shape[0] in (1, n):
+        return shape[0]
+    raise ValueError(f"grids must be a tensor of shape (2, GH, GW), (1, 2, GH, GW) or (N, 2, GH, GW) = ({n}, {want[0]}, {want[1]}, {want[2]}) for a {oh} x {ow} output at cell {cell}, "
+                     f"got {shape if isinstance(grids, torch.Tensor) else type(grids).__name__}")
 
 
 def _statistics_rows(mean: torch.Tensor, std: torch.Tensor, n: int, what: str, accepted: str = "(3,), (1, 3)") -> tuple[torch.Tensor, torch.Tensor]:
@@ -1319,6 +1334,44 @@ class WarpHIP(TorchHIPBackendBase):
             return out
         with _native.on_device(self.device):
             self._call("sx_affine_warp_mask", mask, out, n, h, w, oh, ow, r, n_rows, _native.WARP_BORDERS[border], int(fill))
+        return out
+
+
+class ElasticHIP(TorchHIPBackendBase):
+    """Elastic deformation fused with the affine warp (include/stainx_hip.h: sx_elastic_warp, sx_elastic_warp_mask): a row and a control
+    grid per tile, one kernel launch per call, no workspace, no host synchronisation.  Rows and grids are read on the device."""
+
+    def apply(self, images: torch.Tensor, rows: torch.Tensor, grids: torch.Tensor, cell: int, size: tuple[int, int] | None = None, *, interpolation: str = "bilinear",
+              border: str = "mirror", fill: float = 0.0, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None, channels_last: bool = False) -> torch.Tensor:
+        """``rows`` as ``WarpHIP.apply``; ``grids``: (2, GH, GW), (1, 2, GH, GW) or (N, 2, GH, GW) floats for ``size`` and ``cell``."""
+        images, n, h, w, code = self._images(images, channels_last, "elastic warp", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _warp_rows(rows, n)
+        oh, ow = (h, w) if size is None else size
+        n_grids = _elastic_grids(grids, n, oh, ow, cell)
+        r, g = self._f32(rows), self._f32(grids)
+        out = torch.empty((n, oh, ow, 3) if channels_last else (n, 3, oh, ow), dtype=out_dtype, device=self.device)
+        if n * h * w == 0 or oh * ow == 0:
+            return out
+        with _native.on_device(self.device):
+            self._call("sx_elastic_warp", images, out, code, n, h, w, oh, ow, r, n_rows, g, n_grids, int(cell), _native.WARP_INTERPOLATIONS[interpolation],
+                       _native.WARP_BORDERS[border], float(fill), flags)
+        return out
+
+    def apply_mask(self, mask: torch.Tensor, rows: torch.Tensor, grids: torch.Tensor, cell: int, size: tuple[int, int] | None = None, *, border: str = "constant",
+                   fill: int = 0) -> torch.Tensor:
+        """``mask``: dense uint8 (N, H, W) -> uint8 (N, OH, OW): nearest, bytes moved as bytes."""
+        mask = _mask_bytes(mask, self.device)
+        n, h, w = mask.shape
+        n_rows = _warp_rows(rows, n)
+        oh, ow = (h, w) if size is None else size
+        n_grids = _elastic_grids(grids, n, oh, ow, cell)
+        r, g = self._f32(rows), self._f32(grids)
+        out = torch.empty((n, oh, ow), dtype=torch.uint8, device=self.device)
+        if n * h * w == 0 or oh * ow == 0:
+            return out
+        with _native.on_device(self.device):
+            self._call("sx_elastic_warp_mask", mask, out, n, h, w, oh, ow, r, n_rows, g, n_grids, int(cell), _native.WARP_BORDERS[border], int(fill))
         return out
 
 

@@ -5236,5 +5236,8 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 // Affine warp with a row per tile (sx_affine_warp, sx_affine_warp_mask): one launch, a gather through the vector cache, on the same helpers.
 #include "warp.hpp"
 
+// Elastic deformation with a control grid per tile (sx_elastic_warp, sx_elastic_warp_mask): warp.hpp's rule with a cubic B-spline displacement added to the coordinate, one launch.
+#include "elastic.hpp"
+
 // Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
 #include "vahadane.hpp"
