@@ -417,6 +417,52 @@ int sx_hsv_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_til
 int sx_hsv_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                         const float* rows_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- Tone jitter: per-tile brightness, contrast, gamma and additive Gaussian noise (the "BC" member and the noise of Tellez et al.'s set) ----
+ * An extension: one row of four floats per tile, and one 64-bit seed per tile where noise is asked for.
+ *   rows_dev   n_rows x 4 floats (a, b, gamma, sigma); n_rows is 1 (one row for the batch) or n_tiles (row t serves tile t).
+ *              (1, 0, 1, 0) is the identity.
+ *   seeds_dev  NULL: no noise (a kernel without the generator), or n_tiles int64 in device memory.  A tile with sigma == 0 adds nothing.
+ * All arithmetic is float32 on 0-255 levels, every fused multiply-add written out; x is the input level (uint8: the byte; floats: 255 x)
+ * clamped to [0, 255].  For each channel of each pixel:
+ *   1. t = clamp(fma(a, x, 255 b), 0, 255): a = 1, b = 0 gives x exactly.  (255 b is carried as the float32 pair fl(255 b) and its exact
+ *      remainder, the remainder added after the fused sum: t is within two roundings of a x + 255 b even where the two cancel.)
+ *   2. where gamma != 1: t = 255 (t / 255)^gamma, 0 staying 0 -- 255 exp2f(gamma log2f(t / 255)); gamma == 1 is a select, not an evaluation.
+ *   3. where noise is on: t = clamp(t + 255 sigma z, 0, 255).
+ * The noise.  For pixel p = y W + x of a tile with seed s:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (p & 0xffffffff, p >> 32, 0, 0), key = (s & 0xffffffff, (s >> 32) & 0xffffffff))
+ *   u(w) = (2 (w >> 9) + 1) 2^-24, exact in float32 and strictly inside (0, 1)
+ *   rho = sqrt(-2 ln u(w0)),  z_r = rho cos(2 pi u(w1)),  z_g = rho sin(2 pi u(w1));  from (w2, w3) the same way z_b (cosine), z_s (sine)
+ *   shared_noise == 0: channels r, g, b get z_r, z_g, z_b;  shared_noise != 0: all three channels get z_s.
+ * One Philox call per pixel serves both modes.  The field depends on (seed, p) only: not on the layout, the pack width, the mask, the
+ * launch geometry or the tile's place in the batch.
+ * Output: sx_hsv_apply's rule -- an 8-bit level is ROUNDED TO NEAREST, so the identity row returns every byte; SX_MACENKO_NORMALIZE_0_1,
+ * SX_MACENKO_OUT_BF16 / _OUT_F16 (uint8 input) and SX_MACENKO_CHANNELS_LAST (unmasked only) as there.
+ * Copies, by sx_hsv_apply's background rule and with its bits: a pixel with a NaN in any channel; a masked-out pixel; every pixel of a
+ * tile whose row has a non-finite member, gamma <= 0 or sigma < 0 ("leave this tile"), whatever its seed.  Every use of a value that may be
+ * NaN is a select.
+ * Each call is ONE kernel launch on `stream`: no workspace, no atomics, no memset, capturable.  Rows, seeds and masks are DEVICE memory
+ * read by the kernel: a replayed graph uses whatever was written to them.  Flags, flag checks and argument errors are sx_hsv_apply's. */
+int sx_tone_apply(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                  const float* rows_dev, int64_t n_rows, const long long* seeds_dev, int shared_noise, unsigned flags, void* stream);
+/* sx_tone_apply_masked: the same under an explicit mask (N, H, W), one byte per pixel, non-zero = in; planar tiles only.  A masked-out
+ * pixel is copied; a masked-in pixel has sx_tone_apply's bits (the noise of a pixel does not depend on the mask). */
+int sx_tone_apply_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                         const float* rows_dev, int64_t n_rows, const long long* seeds_dev, int shared_noise,
+                         const unsigned char* mask_dev, unsigned flags, void* stream);
+
+/* ---- Grey statistics: pixels, sum Y, sum Y^2 per tile or per batch (brightness and RMS contrast; the pivot of a contrast change) ----
+ * statistics_out_dev: S x 3 int64 [pixels, sum Y, sum Y^2], S = n_tiles, or 1 with pooled != 0.  Y is sx_grey_map's level (a pixel with a
+ * NaN channel has Y = 0 and is counted).  Every pixel is counted; in the masked form only the pixels whose mask byte is non-zero (planar
+ * tiles only there: channels_last must be 0).  ONE streaming launch reads the tile once and writes no map: 32-bit lane sums over chunks
+ * that cannot overflow, a wave reduction, one 64-bit integer add per word and workgroup into words cleared first -- by a memset, or by a
+ * small clearing launch while the stream is being captured (sx_deconv_moments's rule).  Integers only: the result is independent of the
+ * order and poolable by addition.  Argument errors (a NULL pointer, a non-positive size, too many tiles) are SX_ERR_BAD_ARG, an unknown
+ * dtype SX_ERR_DTYPE, before anything is enqueued. */
+int sx_grey_statistics(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last, int pooled,
+                       long long* statistics_out_dev, void* stream);
+int sx_grey_statistics_masked(const void* images_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width, int channels_last, int pooled,
+                              const unsigned char* mask_dev, long long* statistics_out_dev, void* stream);
+
 /* ---- Gaussian blur with a sigma per tile (the blur of Tellez et al.'s augmentation set; the other half of the focus measurement) ----
  * An extension: the reference has none.  One float32 sigma per tile; each channel plane is filtered on its own, a pixel never sees
  * another tile.

@@ -151,6 +151,11 @@ def draw(generator: torch.Generator | None, shape: tuple, device: torch.device, 
     return getattr(torch, kind)(shape, generator=generator, device=generator.device if generator is not None else device, dtype=torch.float32)
 
 
+def draw_seeds(generator: torch.Generator | None, n: int, device: torch.device) -> torch.Tensor:
+    """(n,) int64 seeds, ``randint(0, 2^63 - 1)``, under ``draw``'s device rule; the caller moves them."""
+    return torch.randint(0, 2**63 - 1, (n,), generator=generator, device=generator.device if generator is not None else device, dtype=torch.int64)
+
+
 def chosen(generator: torch.Generator | None, n: int, p: float, device: torch.device) -> torch.Tensor:
     """The ``p < 1`` selection, (n, 1) bool on ``device``: one more draw, ``rand(n) < p``."""
     return (draw(generator, (n,), device) < p).to(device).unsqueeze(-1)

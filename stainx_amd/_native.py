@@ -88,6 +88,11 @@ SIGNATURES = {
     # HSV colour jitter: rows of (dh, a_s, b_s, a_v, b_v) per tile in device memory, one launch
     "sx_hsv_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_hsv_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
+    # tone jitter: rows of (a, b, gamma, sigma) and int64 seeds per tile in device memory, one launch; grey statistics: pixels, sum Y, sum Y^2
+    "sx_tone_apply": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _int, _uint, _vp]),
+    "sx_tone_apply_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _uint, _vp]),
+    "sx_grey_statistics": (_int, [_vp, _int, _i64, _i64, _i64, _int, _int, _vp, _vp]),
+    "sx_grey_statistics_masked": (_int, [_vp, _int, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp]),
     # Gaussian blur: one float32 sigma per tile in device memory, one launch, both passes on chip
     "sx_gaussian_blur": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_gaussian_blur_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),

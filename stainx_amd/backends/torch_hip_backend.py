@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_sigma_rows``, ``_warp_rows``, ``_elastic_grids``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_tone_rows``, ``_tone_seeds``, ``_sigma_rows``, ``_warp_rows``, ``_elastic_grids``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,7 +58,7 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
-        if family in ("HSV", "Gaussian blur", "affine warp", "elastic warp"):
+        if family in ("HSV", "tone jitter", "Gaussian blur", "affine warp", "elastic warp"):
             raise ValueError(f"{family} {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
@@ -1271,6 +1271,68 @@ class HsvHIP(TorchHIPBackendBase):
                 self._call("sx_hsv_apply", images, out, code, n, h, w, r, n_rows, flags)
             else:
                 self._call("sx_hsv_apply_masked", images, out, code, n, h, w, r, n_rows, self._mask_for(images, *masking), flags)
+        return out
+
+
+def _tone_rows(rows: torch.Tensor, n: int) -> int:
+    """Rows of a tone jitter, (4,), (1, 4) or (N, 4): the number of rows, 1 or N."""
+    shape = tuple(getattr(rows, "shape", ()))
+    if isinstance(rows, torch.Tensor) and shape == (4,):
+        return 1
+    if isinstance(rows, torch.Tensor) and len(shape) == 2 and shape[1] == 4 and shape[0] in (1, n):
+        return shape[0]
+    raise ValueError(f"rows must be a tensor of shape (4,), (1, 4) or (N, 4) = ({n}, 4) holding (a, b, gamma, sigma), got {shape}")
+
+
+def _tone_seeds(seeds: torch.Tensor | None, n: int) -> None:
+    """Seeds of a tone jitter: None, or (N,) int64."""
+    if seeds is None:
+        return
+    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.int64 or tuple(seeds.shape) != (n,):
+        raise ValueError(f"seeds must be None or an int64 tensor of shape (N,) = ({n},), got {getattr(seeds, 'dtype', type(seeds).__name__)} {tuple(getattr(seeds, 'shape', ()))}")
+
+
+class ToneHIP(TorchHIPBackendBase):
+    """Tone jitter and grey statistics (include/stainx_hip.h: sx_tone_apply, sx_grey_statistics): one kernel launch per call (a clearing
+    memset or launch in front of the statistics), no workspace, no host synchronisation.  Rows, seeds and masks are read on the device: a
+    captured call replayed after new values are copied into the same tensors uses the new values."""
+
+    def apply(self, images: torch.Tensor, rows: torch.Tensor, seeds: torch.Tensor | None = None, *, shared_noise: bool = False, normalize_to_0_1: bool = False,
+              out_dtype: torch.dtype | None = None, channels_last: bool = False, masking: tuple | None = None) -> torch.Tensor:
+        """``rows``: (4,), (1, 4) or (N, 4) floats ``(a, b, gamma, sigma)``; a row with a non-finite member, ``gamma <= 0`` or
+        ``sigma < 0`` leaves its tile as it is.  ``seeds``: None (no noise) or (N,) int64.  ``masking`` as ``HsvHIP.apply``."""
+        if masking is not None and channels_last:
+            raise ValueError("a masked tone jitter takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "tone jitter", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _tone_rows(rows, n)
+        _tone_seeds(seeds, n)
+        r = self._f32(rows)
+        s = None if seeds is None else seeds.to(self.device).contiguous()
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n * h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            if masking is None:
+                self._call("sx_tone_apply", images, out, code, n, h, w, r, n_rows, s, int(bool(shared_noise)), flags)
+            else:
+                self._call("sx_tone_apply_masked", images, out, code, n, h, w, r, n_rows, s, int(bool(shared_noise)), self._mask_for(images, *masking), flags)
+        return out
+
+    def statistics(self, images: torch.Tensor, *, pooled: bool = False, channels_last: bool = False, masking: tuple | None = None) -> torch.Tensor:
+        """(S, 3) int64 ``[pixels, sum Y, sum Y^2]``, S = N or 1 with ``pooled``; zeros for an empty batch.  ``masking`` as in ``apply``."""
+        if masking is not None and channels_last:
+            raise ValueError("masked grey statistics take planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, None)
+        sets = 1 if pooled else n
+        if n * h * w == 0:
+            return torch.zeros((sets, 3), dtype=torch.int64, device=self.device)
+        out = torch.empty((sets, 3), dtype=torch.int64, device=self.device)      # (the library clears what it adds into)
+        with _native.on_device(self.device):
+            if masking is None:
+                self._call("sx_grey_statistics", images, code, n, h, w, int(channels_last), int(bool(pooled)), out)
+            else:
+                self._call("sx_grey_statistics_masked", images, code, n, h, w, 0, int(bool(pooled)), self._mask_for(images, *masking), out)
         return out
 
 

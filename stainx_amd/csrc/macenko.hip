@@ -5241,3 +5241,6 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 
 // Vahadane stain estimation (sparse NMF with two atoms) and the percentile concentrations of a given basis (sx_vahadane_*, sx_stain_max_concentrations).
 #include "vahadane.hpp"
+
+// Tone jitter, per-tile brightness / contrast / gamma rows and counter-based Gaussian noise (sx_tone_apply, sx_tone_apply_masked): hsv.hpp's streaming kernel shape with a Philox generator inside.
+#include "tone.hpp"

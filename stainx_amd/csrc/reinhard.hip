@@ -1059,5 +1059,8 @@ extern "C" int sx_reinhard_apply_targets_masked(const void* images, void* out, i
 // ---- focus measurement: grey maps, the integer sums of the Laplacian and the Sobel gradient per tile, cell or batch, cell grids as masks -------
 #include "focus.hpp"
 
+// ---- grey statistics: pixels, sum Y and sum Y^2 per tile or batch in one launch, on focus.hpp's grey level (the pivot of tone.hpp's contrast) ----
+#include "tone_statistics.hpp"
+
 // ---- luminosity standardisation: the exact percentile of the luminance, the one-launch L* map ------------------------------------------------
 #include "luminosity.hpp"
