@@ -491,6 +491,62 @@ int sx_gaussian_blur(const void* images_dev, void* out_dev, int dtype, int64_t n
 int sx_gaussian_blur_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
                             const float* sigmas_dev, int64_t n_rows, const unsigned char* mask_dev, unsigned flags, void* stream);
 
+/* ---- JPEG compression round trip with a quality per tile (the compression artefacts every whole-slide pipeline meets: 8 x 8 blocks,
+ * smeared chroma) ----
+ * An extension: the reference has none.  The output is, BIT FOR BIT, what baseline JPEG as libjpeg implements it -- Pillow's
+ * Image.save(..., "JPEG", quality=q, subsampling=s) followed by Image.open -- decodes to.  The lossy part of that codec is 32-bit integer
+ * arithmetic and its entropy coder is lossless, so encode and decode are fused and no bitstream is produced.  A pixel never sees another tile.
+ * All arithmetic is int32, >> is arithmetic, D(x, n) = (x + (1 << (n - 1))) >> n.
+ *   qualities_dev n_rows floats; n_rows is 1 (one quality for the batch) or n_tiles.  q = min((int)quality, 100).  A quality that is NaN,
+ *              infinite or < 1 leaves its tile (see Copies).  Quality 100 is NOT the identity: its tables are all ones, the colour
+ *              conversion and the two transforms still round.
+ *   subsampling 0: 4:4:4, 2: 4:2:0 (Pillow's numbering), one value per call.
+ *   Input      a uint8 byte is its level; a float element x, converted to float32, is clamp(rint(255 x), 0, 255); a NaN is level 0
+ *              (sx_grey_statistics' rule).  A codec sees 8-bit levels: this quantisation is part of the feature.
+ *   Colour     (JFIF, libjpeg's 16-bit tables)  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *              Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,  Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16.
+ *   Planes     a plane that is not subsampled is extended to multiples of 8 by replicating its last column and row.  4:2:0, each chroma
+ *              plane, in this order: (1) the last column replicated up to a multiple of 16 columns; (2) the last row replicated to an even
+ *              height; (3) the 2 x 2 mean (a + b + c + d + bias) >> 2, bias 1 in even output columns and 2 in odd ones; (4) the last
+ *              DOWNSAMPLED row replicated down to a multiple of 8 rows.
+ *   Tables     scale = 5000 / q (integer division) for q < 50, else 200 - 2 q;  Q[i] = clamp((base[i] * scale + 50) / 100, 1, 255); base
+ *              is Annex K's luminance table for Y, its chrominance table for Cb and Cr, in row-major order:
+ *                luminance    16 11 10 16 24 40 51 61 / 12 12 14 19 26 58 60 55 / 14 13 16 24 40 57 69 56 / 14 17 22 29 51 87 80 62 /
+ *                             18 22 37 56 68 109 103 77 / 24 35 55 64 81 104 113 92 / 49 64 78 87 103 121 120 101 / 72 92 95 98 112 100 103 99
+ *                chrominance  17 18 24 47 99 99 99 99 / 18 21 26 66 99 99 99 99 / 24 26 56 99 99 99 99 99 / 47 66 99 99 99 99 99 99 / then 99
+ *   Forward    libjpeg's jfdctint on level - 128 per 8 x 8 block, rows then columns (CONST_BITS 13, PASS1_BITS 2).  With t0..t3 the sums
+ *              d0+d7, d1+d6, d2+d5, d3+d4 and t7..t4 the differences d0-d7 .. d3-d4:  t10 = t0+t3, t13 = t0-t3, t11 = t1+t2, t12 = t1-t2;
+ *              outputs 0 and 4 are (t10 +- t11) * 4 in the row pass, D(t10 +- t11, 2) in the column pass;  z1 = (t12+t13) * 4433, output 2
+ *              is D(z1 + t13 * 6270, n), output 6 D(z1 - t12 * 15137, n), n = 11 (rows) / 15 (columns).  Odd part:  z1 = t4+t7, z2 = t5+t6,
+ *              z3 = t4+t6, z4 = t5+t7, z5 = (z3+z4) * 9633;  t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;  z1 *= -7373, z2 *= -20995,
+ *              z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;  outputs 7, 5, 3, 1 are D(t4+z1+z3, n), D(t5+z2+z4, n), D(t6+z2+z3, n),
+ *              D(t7+z1+z4, n).  The result carries a factor of 8.
+ *   Quantise   k = sign(c) ((|c| + (8 Q >> 1)) / (8 Q)), integer division; dequantise k Q.
+ *   Inverse    jidctint, columns then rows, the same even / odd structure on the dequantised values: the even part starts from
+ *              (in0 +- in4) * 8192, the z of inputs 2 and 6 as above, the odd inputs taken in the order 7, 5, 3, 1 through the same twelve
+ *              constants; the column pass descales by D(., 11), the row pass by D(., 18); then clamp(. + 128, 0, 255).
+ *   Chroma up  (4:2:0) libjpeg's "fancy" triangle filter on the decoded chroma plane cropped to ceil(H/2) x ceil(W/2), edges replicated:
+ *              for the upper / lower output row of a pair t = 3 * row + (row above / row below); the even output column is
+ *              (3 t + t_left + 8) >> 4, the odd one (3 t + t_right + 7) >> 4 (first column (4 t + 8) >> 4, last (4 t + 7) >> 4).
+ *              NARROW TILES: where the cropped chroma plane is at most 2 columns wide (W <= 4) libjpeg does not filter: every chroma
+ *              sample is replicated 2 x 2 (checked against Pillow for every H in 1..19, W in 1..4).
+ *   RGB        with cb, cr minus 128:  R = Y + ((91881 cr + 32768) >> 16),  B = Y + ((116130 cb + 32768) >> 16),
+ *              G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), each clamped to 0..255.
+ * Output: the 8-bit level through sx_hsv_apply's output rule (the cast; SX_MACENKO_NORMALIZE_0_1 fuses / 255; uint8 input may ask for
+ * SX_MACENKO_OUT_BF16 / _OUT_F16); the level is an integer, nothing is rounded.
+ * Copies: a tile whose quality is NaN, infinite or < 1 is copied by sx_hsv_apply's copy rule -- the input level, clamped to [0, 255],
+ * through the output rule; uint8 in, uint8 out: the same bytes.
+ * Each call is ONE kernel launch on `stream`: nothing else enqueued, no bitstream, no workspace, no host synchronisation, capturable;
+ * nothing goes through device memory between the colour conversion and the final store.  Qualities and masks are DEVICE memory read by the
+ * kernel.  Flags as sx_gaussian_blur.  Argument errors, in this order and before anything is enqueued: null pointers, non-positive sizes,
+ * the 2^32 limit, n_rows, subsampling not 0 or 2 (SX_ERR_BAD_ARG), flags, the layout flag on the masked call, then the dtype. */
+int sx_jpeg_roundtrip(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                      const float* qualities_dev, int64_t n_rows, int subsampling, unsigned flags, void* stream);
+/* sx_jpeg_roundtrip_masked: the same under an explicit mask (N, H, W), one byte per pixel, non-zero = in; planar tiles only.  A masked-out
+ * pixel is copied by the copy rule above; the codec reads every pixel.  All ones: sx_jpeg_roundtrip's bits. */
+int sx_jpeg_roundtrip_masked(const void* images_dev, void* out_dev, int dtype, int64_t n_tiles, int64_t height, int64_t width,
+                             const float* qualities_dev, int64_t n_rows, int subsampling, const unsigned char* mask_dev, unsigned flags, void* stream);
+
 /* ---- Affine warp with a row per tile (the geometric half of Tellez et al.'s augmentation set: quarter turns, flips, rotation, scale,
  * shear, translation; crop, pad and resize in the same launch) ----
  * An extension: the reference has none.  The source tile is height x width, the output tile out_height x out_width.

@@ -96,6 +96,9 @@ SIGNATURES = {
     # Gaussian blur: one float32 sigma per tile in device memory, one launch, both passes on chip
     "sx_gaussian_blur": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _uint, _vp]),
     "sx_gaussian_blur_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _uint, _vp]),
+    # JPEG round trip: one float32 quality per tile in device memory, one launch, encode and decode fused on chip
+    "sx_jpeg_roundtrip": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _uint, _vp]),
+    "sx_jpeg_roundtrip_masked": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _uint, _vp]),
     # affine warp: one row of six floats per tile in device memory, one launch; the mask warped with its tile
     "sx_affine_warp": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _c.c_float, _uint, _vp]),
     "sx_affine_warp_mask": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _int, _int, _vp]),

@@ -8,7 +8,7 @@ statistics are computed on the device by the same library (reference: always tor
 torch_backend.py:463-466) -- there is no torch-op or CPU path in this package.
 
 Every rule of the binding is written once.  The shape and dtype rules are the module's pure functions (``_image_shape``,
-``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_tone_rows``, ``_tone_seeds``, ``_sigma_rows``, ``_warp_rows``, ``_elastic_grids``, ``_statistics_rows``,
+``_out_flags``, ``_reference_pair``, ``_source_rows``, ``_check_factors``, ``_basis_rows``, ``_hsv_rows``, ``_tone_rows``, ``_tone_seeds``, ``_sigma_rows``, ``_quality_rows``, ``_warp_rows``, ``_elastic_grids``, ``_statistics_rows``,
 ``_reference_statistics``, ``_explicit_mask``): they take CPU tensors as well, and a tensor moves to the device (``_f32``) after its
 check.  The base class holds the image preamble (``_images``), the mask of a masked call (``_mask_for``) and the call rule
 (``_call``, under one ``on_device`` guard per public call): the entry point is looked up on ``self._lib``, tensors become their
@@ -58,7 +58,7 @@ def _image_shape(images: torch.Tensor, channels_last: bool, family: str | None, 
             raise ValueError(f"Macenko {what} expects 3 channels in dim 1 (NCHW), got C={shape[1]} with shape {shape}")
         if family == "deconvolution":
             raise ValueError(f"deconvolution {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
-        if family in ("HSV", "tone jitter", "Gaussian blur", "affine warp", "elastic warp"):
+        if family in ("HSV", "tone jitter", "Gaussian blur", "JPEG round trip", "affine warp", "elastic warp"):
             raise ValueError(f"{family} {what} expects {'NHWC' if channels_last else 'NCHW'} tensors with 3 channels, got shape {shape}")
         if family == "Reinhard":
             raise ValueError(f"Reinhard expects NCHW images with C=3, got shape {shape}")
@@ -1360,6 +1360,43 @@ class BlurHIP(TorchHIPBackendBase):
                 self._call("sx_gaussian_blur", images, out, code, n, h, w, s, n_rows, flags)
             else:
                 self._call("sx_gaussian_blur_masked", images, out, code, n, h, w, s, n_rows, self._mask_for(images, *masking), flags)
+        return out
+
+
+def _quality_rows(qualities: torch.Tensor, n: int) -> int:
+    """Qualities of a JPEG round trip, (), (1,) or (N,): the number of rows, 1 or N."""
+    shape = tuple(getattr(qualities, "shape", (-1, -1)))
+    if isinstance(qualities, torch.Tensor) and (shape == () or (len(shape) == 1 and shape[0] in (1, n))):
+        return 1 if shape == () else shape[0]
+    raise ValueError(f"quality must be an int or a tensor of shape (), (1,) or (N,) = ({n},), got {shape}")
+
+
+class JpegHIP(TorchHIPBackendBase):
+    """JPEG compression round trip with a quality per tile (include/stainx_hip.h: sx_jpeg_roundtrip): one kernel launch per call, encode
+    and decode fused on chip, no bitstream, no workspace, no host synchronisation.  Qualities and masks are read on the device: a
+    captured call replayed after new qualities are copied into the same tensor uses the new qualities."""
+
+    def apply(self, images: torch.Tensor, qualities: torch.Tensor, subsampling: int = 2, *, normalize_to_0_1: bool = False, out_dtype: torch.dtype | None = None,
+              channels_last: bool = False, masking: tuple | None = None) -> torch.Tensor:
+        """``qualities``: (), (1,) or (N,) floats; a quality that is NaN, infinite or ``< 1`` leaves its tile as it is, one above 100 is
+        100.  ``subsampling``: 0 (4:4:4) or 2 (4:2:0).  ``masking``: None, or ``(explicit mask or None, luminosity threshold)`` -- the
+        masked call (planar tiles only); the rule's mask is an ``sx_tissue_mask`` launch in front."""
+        if subsampling not in (0, 2) or isinstance(subsampling, bool):
+            raise ValueError(f"subsampling must be 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+        if masking is not None and channels_last:
+            raise ValueError("a masked JPEG round trip takes planar (NCHW) tiles only")
+        images, n, h, w, code = self._images(images, channels_last, "JPEG round trip", "apply")
+        flags, out_dtype = _out_flags(images, out_dtype, normalize_to_0_1, channels_last)
+        n_rows = _quality_rows(qualities, n)
+        q = self._f32(qualities)
+        out = torch.empty(tuple(images.shape), dtype=out_dtype, device=self.device)
+        if n * h * w == 0:
+            return out
+        with _native.on_device(self.device):
+            if masking is None:
+                self._call("sx_jpeg_roundtrip", images, out, code, n, h, w, q, n_rows, subsampling, flags)
+            else:
+                self._call("sx_jpeg_roundtrip_masked", images, out, code, n, h, w, q, n_rows, subsampling, self._mask_for(images, *masking), flags)
         return out
 
 

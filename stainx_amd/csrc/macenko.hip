@@ -5233,6 +5233,10 @@ extern "C" int sx_macenko_pfit_finish(const unsigned* gathered_compact, const in
 // Gaussian blur with a sigma per tile (sx_gaussian_blur, sx_gaussian_blur_masked): one launch, both passes on chip, on the same helpers.
 #include "blur.hpp"
 
+// JPEG compression round trip with a quality per tile (sx_jpeg_roundtrip, sx_jpeg_roundtrip_masked): encode and decode fused in one launch, the planes kept on chip.
+#include "jpeg_block.hpp"
+#include "jpeg.hpp"
+
 // Affine warp with a row per tile (sx_affine_warp, sx_affine_warp_mask): one launch, a gather through the vector cache, on the same helpers.
 #include "warp.hpp"
 
