@@ -45,7 +45,7 @@ SX_JPEG_FN int jpeg_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi 
 // ---- the quality and the tables -----------------------------------------------------------------------------------------------------
 // The quality of a tile: 0 = leave the tile (NaN, infinite, < 1), else min((int)q, 100).
 SX_JPEG_FN int jpeg_quality(float q) {
-    if (!(q >= 1.0f) || q > 3.0e38f) return 0;      // (false for a NaN; +inf)
+    if (!(q >= 1.0f) || q == __builtin_huge_valf()) return 0;      // (false for a NaN; +inf -- every finite quality from 100 up, FLT_MAX included, is 100)
     return q >= 100.0f ? 100 : (int)q;
 }
 // Annex K's tables in natural (row-major) order; `chroma`: the chrominance table.
